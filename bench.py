@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput benchmark: radar frames/s end-to-end on 8ch x 128chirp x 512 cubes (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W --frames-per-step F]
+    python bench.py [--gpus N --steps K --warmup W --frames-per-step F] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 One step = one pass of the full per-frame chain (configs[2]: RDS + peak detection + MUSIC DoA argmax +
@@ -10,6 +10,12 @@ resident in HBM.  Frames shard across ranks (one process per GPU, weak scaling, 
 the only exchange is the trajectory reduction of the north star: each rank scans its block's poses on the
 device, the ranks all-gather 16-double block summaries over RCCL/xGMI and the per-frame poses are gathered to rank 0,
 which smooths them across block edges.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (the headline figure, the live per-kernel hipEvent
+times of the timed steps and the rooflines derived from them).  `--full` adds every measurement that takes runs of its
+own: the standalone per-kernel launches after the timed region, the configs[1] / configs[4]-frame sub-measurements, the
+PCIe-inclusive rate and the CPU baseline (`--no-extra`, `--no-pcie`, `--no-cpu-baseline` drop single ones of them).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (chain_outputs).
 """
 from __future__ import annotations
 
@@ -340,14 +346,16 @@ def _sync_max(elapsed, dev):
 SPEC_BUFFERS = 3  # configs[1]: spectrum output buffers the steps rotate through (placement-dependent rate)
 
 
-def measure_spectrum(ctx, dev, F, steps, warmup, rank, world, timing=True, collective=True, nbuf=SPEC_BUFFERS):
+def measure_spectrum(ctx, dev, F, steps, warmup, rank, world, timing=True, collective=True, nbuf=SPEC_BUFFERS,
+                     dump=False):
     """configs[1]: 8ch x 128chirp x 512 cube, F frames per step, range-Doppler FFT + peaks + the MUSIC spectrum of every
     unique cell (f32, cell-blocked [cells / 32, 361, 32]; the reference keeps spectrum f64[G] per target,
     angle_estimation.py:299).  One chain, no pipelining; the spectrum store dominates (51 MB per frame).  Step i writes
     its spectrum to output buffer i mod nbuf (nbuf separate 57 GB allocations, all held): the store rate depends on
     where the driver places a buffer physically (DRAM write-credit stalls), so the line averages over
     nbuf placements instead of depending on one.  Returns a dict: frames/s, per-step time, the spectrum scan's HBM
-    roofline and the FFT stage's, and the scan's ms per output buffer."""
+    roofline and the FFT stage's, and the scan's ms per output buffer; with `dump`, the last timed step's results
+    (chain_outputs) under "outputs"."""
     import torch
     import torch.distributed as dist
     import rsl
@@ -407,6 +415,8 @@ def measure_spectrum(ctx, dev, F, steps, warmup, rank, world, timing=True, colle
         out["fft_stage"] = {"bound": "hbm", "achieved": fb / tf / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                             "frac": fb / tf / 1e9 / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": fb}
         out["kernel_ms_per_step"] = {k: v[0] / max(v[1], 1) for k, v in kt.items() if v[1]}
+    if dump and steps > 0 and rank == 0:
+        out["outputs"] = chain_outputs([(ch, 0)], back=False)
     del ch, cubes, specs
     torch.cuda.empty_cache()
     return out
@@ -417,9 +427,12 @@ def run_spectrum(args, world, rank, local, dev):
     import rsl
     ctx = rsl.get_context(local)
     F = args.frames_per_step or 1000
-    r = measure_spectrum(ctx, dev, F, args.steps, args.warmup, rank, world, timing=not args.no_timing)
+    r = measure_spectrum(ctx, dev, F, args.steps, args.warmup, rank, world, timing=not args.no_timing,
+                         dump=bool(args.dump_outputs))
     if rank != 0:
         return
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, r.pop("outputs"))
     line = {"metric": "radar frames/sec, range-Doppler FFT + MUSIC spectrum (configs[1]), 8ch x 128chirp x 512",
             "value": r.pop("value"), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": r.pop("ms_per_step"), "higher_is_better": True,
@@ -458,10 +471,11 @@ def chain_traffic_per_frame():
 
 
 def measure_chain(ctx, dev, A, C, Tc, F, steps, warmup, rank, world, *, ridge=0.01, pipeline=True, streams=1,
-                  timing=True, standalone=True, collective=True):
+                  timing=True, standalone=True, collective=True, dump=False):
     """The full chain (RDS + peaks + MUSIC argmax + ESPRIT + LS velocity + trajectory) on batches of F frames already
     resident in HBM: `steps` timed steps after `warmup`, bracketed by barrier + synchronize (max over ranks when
-    `collective`).  Returns elapsed seconds, per-kernel timings (live and standalone), totals and the chain."""
+    `collective`).  Returns elapsed seconds, per-kernel timings (live and standalone), totals and the chain; with
+    `dump`, also the last timed step's results (chain_outputs), read before anything else runs on its buffers."""
     import torch
     import torch.distributed as dist
     import rsl
@@ -565,6 +579,11 @@ def measure_chain(ctx, dev, A, C, Tc, F, steps, warmup, rank, world, *, ridge=0.
         elapsed = _sync_max(elapsed, dev)
     kt = ctx.timing_read() if timing else {}
     spans = ctx.timing_spans() if timing else {}  # per launch [start, end] on one device clock (the live timeline)
+    outputs = None
+    if dump and steps > 0 and reducer.root:
+        last = (steps - 1) % len(chains)
+        outputs = chain_outputs([(chains[last], 0)] if pipeline else
+                                [(ch, k * ch.F) for k, ch in enumerate(chains)], reducer)
     ks = {}  # standalone kernel times: the pipelined timed region overlaps the two halves of consecutive batches
     if kt and pipeline and standalone:
         ctx.timing_reset()
@@ -577,7 +596,7 @@ def measure_chain(ctx, dev, A, C, Tc, F, steps, warmup, rank, world, *, ridge=0.
     ne = sum(ch.totals()[0] for ch in counted)
     nc = sum(ch.totals()[1] for ch in counted)
     return dict(elapsed=elapsed, kt=kt, ks=ks, spans=spans, ne=ne, nc=nc, NS=NS, G=len(chains[0].grid), cubes=cubes,
-                chains=chains, reducer=reducer)
+                chains=chains, reducer=reducer, outputs=outputs, pipelined=bool(pipeline))
 
 
 def live_timeline(spans, steps):
@@ -679,7 +698,8 @@ def chain_rooflines(r, A, C, S, F, config):
         "hipEvents over the timed region (pipelined: the scan co-runs with the next batch's K1 / K2, which stretches "
         "its span while the step gets shorter; the unshared rate is kernel_rooflines_standalone.doa_scan)" if ks
         else "hipEvents over the timed region")
-    out["kernel_rooflines_standalone"] = {k: entry(k, per_std(k)) for k in big if k in src_std}
+    if ks or not r.get('pipelined'):  # pipelined without standalone launches (a plain run): live times only
+        out["kernel_rooflines_standalone"] = {k: entry(k, per_std(k)) for k in big if k in src_std}
     out["kernel_ms_per_step"] = {k: v[0] / max(v[1], 1) * (NS if k not in fft_names else Fl * NS / Ff)
                                  for k, v in kt.items() if v[1]}
     if ks:
@@ -711,6 +731,92 @@ def configs_4_frame(ctx, dev, F=400, steps=313, warmup=2):
     del r
     torch.cuda.empty_cache()
     return out
+
+
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024  # --dump-outputs: upper bound on the bytes written
+
+
+def chain_outputs(parts, reducer=None, sample=None, back=True):
+    """What the timed path computed in its last step, as host float32 / float64 arrays of fixed shapes (so that two
+    builds can be compared array for array).  ``parts``: the (chain, first frame) pairs that hold the step's batch
+    (pipelined: the one chain the step ran on; else one chain per stream, consecutive frame slices).
+    Whole-batch arrays: velocity [F, 8] (the LS rows), peaks_per_frame [F], cells_per_frame [F] and, from the
+    trajectory reducer, poses [R F, 7] (x, y, z, qw, qx, qy, qz of every rank's block) and smoothed_positions (the
+    positions that became final in this step).  The per-cell and per-peak results are compacted lists whose order
+    shifts with every near-threshold decision, so they are written as dense maps of a fixed sample of frames
+    (``sample``: batch frame indices, default the first and the last frame; the first only when a frame's RDS exceeds
+    8 MB): rds [n, A, S, C, 2] f32 (re, im), peak_power_db [n, A, S, C] f32 (0 where the cell is no peak),
+    cell_antennas [n, S, C] f32 (the cell's antenna-detection bit mask, 0 = no peak), doa_azimuth, esprit_azimuth,
+    phase [n, S, C] f64 (0 outside the cells), sample_frames [n].  ``back`` False (a chain run without ESPRIT and
+    velocity, configs[1]): no velocity, esprit_azimuth and phase; instead spectrum [n, 2048, G] f32, the MUSIC
+    spectrum rows of each sampled frame's first 2048 cells (zero rows past the frame's last cell), and
+    spectrum_cells [n, 2048], their range_bin * C + doppler_bin (-1 past the last)."""
+    import torch
+    from rsl.runtime import unpack_coord
+    torch.cuda.synchronize()
+    F = sum(ch.F for ch, _ in parts)
+    out = {'velocity': torch.cat([ch.vel for ch, _ in parts]).cpu().numpy().astype(np.float64)} if back else {}
+    bases = []
+    for ch, _ in parts:
+        eb, cb = ch.offs['entry_base'].cpu().numpy(), ch.offs['cell_base'].cpu().numpy()
+        if eb[ch.F] > ch.entry_cap or cb[ch.F] > ch.cell_cap:
+            raise RuntimeError('peak capacity exceeded')
+        bases.append((eb, cb))
+    out['peaks_per_frame'] = np.concatenate([np.diff(eb) for eb, _ in bases]).astype(np.float64)
+    out['cells_per_frame'] = np.concatenate([np.diff(cb) for _, cb in bases]).astype(np.float64)
+    if reducer is not None and reducer.all_poses is not None:
+        out['poses'] = reducer.all_poses.cpu().numpy().astype(np.float64)
+        if reducer.smoothed is not None:
+            out['smoothed_positions'] = reducer.smoothed.cpu().numpy().astype(np.float64)
+    ch0 = parts[0][0]
+    A, S, C = ch0.A, ch0.S, ch0.C
+    if sample is None:
+        sample = sorted({0, F - 1}) if A * S * C * 8 <= 8 * 1024 * 1024 else [0]
+    n = len(sample)
+    rds = np.zeros((n, A, S, C, 2), np.float32)
+    pdb = np.zeros((n, A, S, C), np.float32)
+    ants = np.zeros((n, S * C), np.float32)
+    az, esp, ph = (np.zeros((n, S * C), np.float64) for _ in range(3))
+    NSPEC = 2048
+    spec = np.zeros((n, NSPEC, len(ch0.grid)), np.float32)
+    spec_rc = np.full((n, NSPEC), -1.0)
+    for i, f in enumerate(sample):
+        (ch, f0), (eb, cb) = [(p, b) for p, b in zip(parts, bases) if p[1] <= f < p[1] + p[0].F][0]
+        fl = f - f0
+        rds[i] = torch.view_as_real(ch.rds[fl]).cpu().numpy()
+        e0, e1, c0, c1 = int(eb[fl]), int(eb[fl + 1]), int(cb[fl]), int(cb[fl + 1])
+        ea, er, ed = unpack_coord(ch.lists['e_coord'][e0:e1].cpu().numpy())
+        pdb[i, ea, er, ed] = ch.lists['e_pdb'][e0:e1].cpu().numpy()
+        rc = ch.lists['c_rc'][c0:c1].cpu().numpy().astype(np.int64)
+        ants[i, rc] = ch.lists['c_amask'][c0:c1].cpu().numpy()
+        az[i, rc] = np.radians(ch.grid)[ch.gidx[c0:c1].cpu().numpy()]
+        if back:
+            esp[i, rc] = ch.ext['esprit'][c0:c1].cpu().numpy()
+            ph[i, rc] = ch.ext['phase'][c0:c1].cpu().numpy()
+        elif ch.spec is not None:
+            m = min(NSPEC, c1 - c0)
+            b0, b1 = c0 // 32, (c0 + m + 31) // 32  # the 32-cell blocks that hold cells c0 .. c0 + m - 1
+            rows = ch.spec[b0:b1].permute(0, 2, 1).reshape((b1 - b0) * 32, -1)
+            spec[i, :m] = rows[c0 - 32 * b0:c0 - 32 * b0 + m].cpu().numpy()
+            spec_rc[i, :m] = rc[:m]
+    out.update(sample_frames=np.asarray(sample, np.float64), rds=rds, peak_power_db=pdb,
+               cell_antennas=ants.reshape(n, S, C), doa_azimuth=az.reshape(n, S, C))
+    if back:
+        out.update(esprit_azimuth=esp.reshape(n, S, C), phase=ph.reshape(n, S, C))
+    else:
+        out.update(spectrum=spec, spectrum_cells=spec_rc)
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy (float32 / float64, DUMP_LIMIT_BYTES in all at most)."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit')
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def _free_port():
@@ -798,10 +904,18 @@ def main():
                          '(A16 C256 S1024); spectrum = configs[1] (A8 C128 S512, 1000 frames per step: RDS + peaks + '
                          'the full MUSIC spectrum of every cell, f32 [G, cells]); the last two are second '
                          'measurements, not the metric line')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-pcie', action='store_true', help='skip the PCIe-inclusive side measurement')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the measurements that take runs of their own: standalone per-kernel launches after '
+                         'the timed region, the configs[1] / configs[4]-frame sub-measurements, the PCIe-inclusive rate '
+                         'and the CPU baseline (a plain run times the steps and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / '
+                         'float64, at most 64 MB: whole-batch velocities, poses and counts, dense maps of sampled '
+                         'frames; chain_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-pcie', action='store_true', help='with --full: skip the PCIe-inclusive side measurement')
     ap.add_argument('--no-extra', action='store_true',
-                    help='skip the configs[1] / configs[4]-frame sub-measurements of the default cfg2 line')
+                    help='with --full: skip the configs[1] / configs[4]-frame sub-measurements of the cfg2 line')
     ap.add_argument('--cpu-peaks', type=int, default=3000,
                     help='peaks per frame through the loop-faithful CPU DoA (the bounded sample; <= 0: every peak)')
     ap.add_argument('--cpu-procs', type=int, default=0,
@@ -861,7 +975,7 @@ def main():
     else:
         A, C, S, Tc, F = 8, 128, 512, 51.2e-6, args.frames_per_step or 2000  # 5 steps = configs[2]'s 10 k frames
     ctx = rsl.get_context(local)
-    extras = not args.no_extra and world == 1 and args.config == 'cfg2'
+    extras = args.full and not args.no_extra and world == 1 and args.config == 'cfg2'
     spec_first = os.environ.get('RSL_BENCH_SPEC_FIRST', '1') != '0'
     spec = None
     if extras and spec_first:
@@ -870,7 +984,8 @@ def main():
         # placements, in untouched memory less often (not never: DESIGN §5)
         spec = _spectrum_sub(ctx, dev)
     r = measure_chain(ctx, dev, A, C, Tc, F, args.steps, args.warmup, rank, world, ridge=args.ridge,
-                      pipeline=bool(args.pipeline), streams=args.streams, timing=not args.no_timing)
+                      pipeline=bool(args.pipeline), streams=args.streams, timing=not args.no_timing,
+                      standalone=args.full, dump=bool(args.dump_outputs))
     elapsed, ne, nc, NS = r['elapsed'], r['ne'], r['nc'], r['NS']
     frames_total = F * args.steps * world
     fps = frames_total / elapsed
@@ -878,6 +993,8 @@ def main():
         if DIST:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, r['outputs'])
     G = r['G']
     line = {
         "metric": METRIC, "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -917,9 +1034,9 @@ def main():
             line["configs_4_frame"] = configs_4_frame(ctx, dev)
         except Exception as e:
             line["configs_4_frame"] = {"error": repr(e)}
-    if not args.no_pcie and world == 1 and args.config == 'cfg2':
+    if args.full and not args.no_pcie and world == 1 and args.config == 'cfg2':
         line["pcie_inclusive"] = pcie_inclusive(ctx, dev)
-    if not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed on rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed on rank 0 at N = 1 only
         try:
             line["cpu_baseline"] = cpu_baseline(args.cpu_procs, args.cpu_peaks, ridge=args.ridge)
         except Exception as e:  # the baseline is reported, never the target

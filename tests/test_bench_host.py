@@ -128,3 +128,21 @@ def test_launch_ranks_protocol(tmp_path, mode, capsys):
         assert rc == 3
     else:
         assert rc != 0 and took < 30
+
+
+def test_write_outputs(tmp_path):
+    """--dump-outputs writes every array as <name>.npy, float32 / float64 only, and refuses more than the limit."""
+    import numpy as np
+    import bench
+    arrays = {'a': np.arange(6, dtype=np.float64).reshape(2, 3), 'b': np.ones(4, np.float32)}
+    bench.write_outputs(str(tmp_path / 'd'), arrays)
+    assert sorted(os.listdir(tmp_path / 'd')) == ['a.npy', 'b.npy']
+    for k, v in arrays.items():
+        got = np.load(tmp_path / 'd' / (k + '.npy'), allow_pickle=False)
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / 'e'), {'i': np.zeros(3, np.int32)})
+    big = np.broadcast_to(np.zeros(1, np.float32), (bench.DUMP_LIMIT_BYTES // 4 + 1,))  # no memory behind it
+    with pytest.raises(RuntimeError):
+        bench.write_outputs(str(tmp_path / 'f'), {'big': big})
+    assert not os.path.exists(tmp_path / 'f')

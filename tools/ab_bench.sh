@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 for r in $(seq 1 "$ROUNDS"); do
   for v in A B; do
     if [ "$v" = A ]; then export RSL_LIBRARY=$PWD/radar-slam_amd/lib/librsl_ab.so; else unset RSL_LIBRARY; fi
-    timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-extra --no-pcie --no-cpu-baseline "$@" > "$OUT/${v}$r.json" 2> "$OUT/${v}$r.err"
+    timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-extra --no-pcie --no-cpu-baseline "$@" > "$OUT/${v}$r.json" 2> "$OUT/${v}$r.err"
   done
 done
 python3 - "$OUT" "$ROUNDS" <<'PY'
