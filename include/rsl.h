@@ -104,6 +104,28 @@ int rsl_rds(rsl_handle h, const void* cube, int F, int A, int C_total, int chirp
 int rsl_detect(rsl_handle h, const void* rds, int F, int A, int S, int C, double thr_power, int i_lo, int i_hi,
                void* mask, void* row_count, void* db_map, void* peak_pow);
 
+/* CA-CFAR detector: an alternative to rsl_detect's fixed threshold with the same outputs (mask, row_count, db_map,
+ *     peak_pow row-compact, group 1), so rsl_peak_offsets / rsl_peak_emit and everything after run unchanged.
+ *     2-D cell averaging on the fp32 power p = |rds|^2 of every (frame, antenna) map [S, C].  With half-sizes
+ *     guard (guard_r, guard_d) and training (train_r, train_d) in range and Doppler, hr = guard_r + train_r and
+ *     hd = guard_d + train_d, the training cells of cell (i, j) are the offsets |di| <= hr, |dj| <= hd without the
+ *     guard box |di| <= guard_r, |dj| <= guard_d (which holds the cell under test).  The Doppler axis wraps (column
+ *     (j + dj) mod C); the range axis truncates (rows outside [0, S) are skipped), so the mean divides by the number
+ *     n(i) of training cells that exist; no window reads another antenna's or frame's map.
+ *     Cell (i, j) is a peak iff  p > alpha * sum / n(i)  (strict: an all-zero map has no peak),  p >= every existing
+ *     3x3 neighbour (rsl_detect's rule and boundary),  i_lo <= i <= i_hi,  and  (double)p > thr_power (a negative
+ *     thr_power disables the floor).  alpha multiplies the training MEAN (for a false-alarm rate Pfa in exponential
+ *     noise: alpha = N (Pfa^(-1/N) - 1), N the full-window count).  The sum is formed by fp32 additions of
+ *     training-cell powers only (relative error < 7e-5).
+ *     RSL_ERR_INVALID: a negative half-size, train_r + train_d < 1, hr or hd > RSL_CFAR_MAX_HALF, 2 hd + 1 > C,
+ *     2 hr + 1 > S, alpha <= 0 or not finite, S > 8192.  RSL_ERR_UNSUPPORTED: C > RSL_CFAR_MAX_C.
+ *     F = 0 is valid and launches nothing.  Timed under RSL_K_DETECT. */
+#define RSL_CFAR_MAX_HALF 16
+#define RSL_CFAR_MAX_C 512
+int rsl_detect_cfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d, int train_r,
+                    int train_d, double alpha, double thr_power, int i_lo, int i_hi, void* mask, void* row_count,
+                    void* db_map, void* peak_pow);
+
 /* a7 + a8 fused: range FFT, then Doppler FFT + fftshift + RDS store + peak detection in one kernel (the RDS is
  *     not re-read for detection).  Arguments as rsl_rds and rsl_detect; falls back to the two calls when the
  *     shape is not covered (C not a power of two <= 1024, or its range-bin tiling does not divide S/2).

@@ -295,6 +295,30 @@ int rsl_detect(rsl_handle h, const void* rds, int F, int A, int S, int C, double
                    "detect");
 }
 
+int rsl_detect_cfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d, int train_r,
+                    int train_d, double alpha, double thr_power, int i_lo, int i_hi, void* mask, void* row_count,
+                    void* db_map, void* peak_pow) {
+  if (!h) return RSL_ERR_INVALID;
+  if (F < 0 || A <= 0 || S <= 0 || C <= 0 || S > 8192) return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: bad shape");
+  if (guard_r < 0 || guard_d < 0 || train_r < 0 || train_d < 0 || train_r + train_d < 1)
+    return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: bad window (half-sizes >= 0, at least one training cell)");
+  const int hr = guard_r + train_r, hd = guard_d + train_d;
+  if (hr > RSL_CFAR_MAX_HALF || hd > RSL_CFAR_MAX_HALF)
+    return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: window half-size above RSL_CFAR_MAX_HALF");
+  if (2 * hd + 1 > C || 2 * hr + 1 > S) return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: window larger than the map");
+  if (!(alpha > 0) || !std::isfinite(alpha)) return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: alpha must be finite, > 0");
+  if (C > RSL_CFAR_MAX_C || !rsl::detect_cfar_supported(C, hr, hd))
+    return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect_cfar: C above RSL_CFAR_MAX_C");
+  if (F == 0) return RSL_OK;
+  if (!rds || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: null pointer");
+  Scope sc(h, RSL_K_DETECT);
+  return hip_check(h,
+                   rsl::launch_detect_cfar(h->stream, (const float2*)rds, F, A, S, C, guard_r, guard_d, train_r,
+                                           train_d, (float)alpha, thr_power, i_lo, i_hi, (unsigned long long*)mask,
+                                           (int*)row_count, (float*)db_map, (float*)peak_pow),
+                   "detect_cfar");
+}
+
 int rsl_peak_offsets(rsl_handle h, const void* mask, const void* row_count, int F, int A, int S, int C,
                      void* entry_row_off, void* cell_row_off, void* scratch, void* entry_base, void* cell_base,
                      void* frame_counts, void* union_mask) {

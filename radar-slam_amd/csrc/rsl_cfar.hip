@@ -1,0 +1,206 @@
+// rsl_cfar.hip — 2-D cell-averaging CFAR peak detection for gfx950 (rsl_detect_cfar, include/rsl.h).
+//
+// A second detector next to k_detect (rsl_detect.hip), with the same outputs: per-antenna 64-bit ballot masks, row
+// counts, the optional dB map and the row-compact peak powers, so offsets / emit and everything after run unchanged.
+// Cell (i, j) of a (frame, antenna) power map p = |rds|^2 [S, C] is a peak iff
+//   p * n(i) > alpha * sum   (sum over the training cells: |di| <= hr, |dj| <= hd without the guard box |di| <= gr,
+//                             |dj| <= gd; Doppler wraps, range truncates, n(i) = the cells that exist)
+//   and p >= every existing 3x3 neighbour (k_detect's rule), i_lo <= i <= i_hi, (double)p > thr_p.
+//
+// The training sum is formed by additions only (a cell 100 dB above its neighbours makes "box minus guard box" or a
+// subtracting sliding window wrong by more than the whole noise sum): per row the side sum HS[j] (gd < |dj| <= hd) and
+// the full sum HF[j] = HS[j] + centre sum (|dj| <= gd), then sum = HF over the rows gr < |di| <= hr plus HS over the
+// rows |di| <= gr.  At most 33 * 33 - 1 = 1088 fp32 additions of non-negative terms: relative error < 1088 * 2^-24 =
+// 6.5e-5.
+//
+// One workgroup walks a strip of R range rows of one map, RB rows per step, three phases per step:
+//   A  load RB rows, power to a small LDS ring PW (RB + 2 rows, with the wrapped Doppler halo copied to both ends);
+//   B  HS / HF of the new rows into LDS rings of NR = RB + hr + max(hr, 1) rows; the 3x3 local-maximum ballots of the
+//      rows one behind into MX (64 bits per mask word);
+//   C  the rows whose last training row has arrived: vertical sum from the rings, decision, ballots, outputs (the
+//      cell's own power is re-read from the RDS, a row the same workgroup streamed hr + RB rows earlier).
+// The RDS is read (R + 2 max(hr, 1)) / R times for the window (1.16 at R = 128, hr = 10) plus the re-read of phase C.
+#include <cstdlib>
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+#include "rsl_common.h"
+#include "rsl_internal.h"
+
+namespace rsl {
+
+namespace {
+
+constexpr size_t kCfarLdsMax = 160 * 1024;  // LDS of one gfx950 CU
+
+// LDS bytes of k_detect_cfar with RB rows per step: HF + HS rings, the power ring, the local-maximum words
+size_t cfar_lds_bytes(int C, int hr, int hd, int RB) {
+  const int hh = hr > 1 ? hr : 1;
+  const size_t NR = (size_t)RB + hr + hh, NP = (size_t)RB + 2, W = ((size_t)C + 63) / 64;
+  return 4 * (2 * NR * C + NP * ((size_t)C + 2 * hd)) + 8 * NR * W;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ rds, int S, int C, int W, int gr,
+                                                     int gd, int tr, int td, float alpha, double thr_p, int i_lo,
+                                                     int i_hi, int R, int RB,
+                                                     unsigned long long* __restrict__ mask,
+                                                     int* __restrict__ row_count, float* __restrict__ dbmap,
+                                                     float* __restrict__ pk_pow) {
+  extern __shared__ float cf_lds[];
+  const int hr = gr + tr, hd = gd + td, hh = max(hr, 1);
+  const int NR = RB + hr + hh, NP = RB + 2, PS = C + 2 * hd;
+  float* HF = cf_lds;               // [NR][C]  row sums over |dj| <= hd
+  float* HS = HF + (size_t)NR * C;  // [NR][C]  row sums over gd < |dj| <= hd
+  float* PW = HS + (size_t)NR * C;  // [NP][PS] power rows, hd wrapped cells on both sides (-1: row outside the map)
+  unsigned long long* MX = reinterpret_cast<unsigned long long*>(PW + (size_t)NP * PS);  // [NR][W] 3x3 maxima
+
+  const int nstrip = (S + R - 1) / R;
+  const int strip = blockIdx.x % nstrip;
+  const size_t fa = blockIdx.x / nstrip;
+  const int i0 = strip * R;
+  const int Re = min(R, S - i0);
+  const int UL = Re + 2 * hh;  // rows the strip loads: u = 0 .. UL-1 is range row ibase + u
+  const int ibase = i0 - hh;
+  const float2* base = rds + fa * S * C;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nfull = 2 * hd + 1, nguard = 2 * gd + 1;
+
+  int done = hh;  // next row (u) to decide
+  for (int uk = 0; uk < UL; uk += RB) {
+    // A: powers of the step's rows
+    for (int r = wave; r < RB; r += 4) {
+      const int u = uk + r;
+      if (u >= UL) break;
+      const int i = ibase + u;
+      const bool valid = i >= 0 && i < S;
+      float* pr = PW + (size_t)(u % NP) * PS;
+      for (int j = lane; j < C; j += 64) {
+        const float p = valid ? cabs2(base[(size_t)i * C + j]) : -1.f;
+        pr[hd + j] = p;
+        if (j < hd) pr[hd + C + j] = p;         // right halo: columns 0 .. hd-1
+        if (j >= C - hd) pr[j - (C - hd)] = p;  // left halo: columns C-hd .. C-1
+      }
+    }
+    __syncthreads();
+    // B: row sums of the step's rows (rows of the map only)
+    for (int r = wave; r < RB; r += 4) {
+      const int u = uk + r;
+      if (u >= UL) break;
+      const int i = ibase + u;
+      if (i < 0 || i >= S) continue;
+      const float* pr = PW + (size_t)(u % NP) * PS + hd;
+      float* hf = HF + (size_t)(u % NR) * C;
+      float* hs = HS + (size_t)(u % NR) * C;
+      for (int j = lane; j < C; j += 64) {
+        float sl = 0.f, sr = 0.f;
+        for (int k = gd + 1; k <= hd; ++k) {
+          sl += pr[j - k];
+          sr += pr[j + k];
+        }
+        float c = pr[j];
+        for (int k = 1; k <= gd; ++k) c += pr[j - k] + pr[j + k];
+        const float s = sl + sr;
+        hs[j] = s;
+        hf[j] = s + c;
+      }
+    }
+    // B: 3x3 local maxima of the rows one behind the step (both neighbour rows are in the ring), output rows only
+    for (int r = wave; r < RB; r += 4) {
+      const int u = uk - 1 + r;
+      if (u < hh || u >= hh + Re) continue;
+      const float* up = PW + (size_t)((u - 1) % NP) * PS + hd;
+      const float* mid = PW + (size_t)(u % NP) * PS + hd;
+      const float* dn = PW + (size_t)((u + 1) % NP) * PS + hd;
+      for (int w = 0; w < W; ++w) {
+        const int j = w * 64 + lane;
+        bool pk = false;
+        if (j < C) {
+          const float p = mid[j];
+          const bool hasl = j > 0, hasr = j + 1 < C;
+          float m = fmaxf(up[j], dn[j]);
+          if (hasl) m = fmaxf(m, fmaxf(mid[j - 1], fmaxf(up[j - 1], dn[j - 1])));
+          if (hasr) m = fmaxf(m, fmaxf(mid[j + 1], fmaxf(up[j + 1], dn[j + 1])));
+          pk = p >= m;
+        }
+        const unsigned long long b = __ballot(pk);
+        if (lane == 0) MX[(size_t)(u % NR) * W + w] = b;
+      }
+    }
+    __syncthreads();
+    // C: decide the rows whose window is complete
+    const int loaded = min(uk + RB, UL);
+    const int end = min(loaded - hh, hh + Re);
+    for (int u = done + wave; u < end; u += 4) {
+      const int i = ibase + u;
+      const size_t orow = fa * S + i;
+      const bool gate = (i >= i_lo && i <= i_hi);
+      const int vh = min(i, hr) + 1 + min(S - 1 - i, hr), vg = min(i, gr) + 1 + min(S - 1 - i, gr);
+      const float fn = (float)(vh * nfull - vg * nguard);  // n(i) >= 1 (2 hr + 1 <= S), exact in fp32 (<= 1088)
+      const int dlo = -min(i, hr), dhi = min(S - 1 - i, hr);
+      int cnt = 0;
+      for (int w = 0; w < W; ++w) {
+        const int j = w * 64 + lane;
+        const unsigned long long mx = MX[(size_t)(u % NR) * W + w];
+        const bool in = j < C;
+        float p = 0.f;
+        if (in && (dbmap || (gate && mx))) p = cabs2(base[(size_t)i * C + j]);
+        bool pk = false;
+        if (gate && mx && in) {  // gate, mx: wave-uniform
+          float s = 0.f;
+          int slot = (u + dlo) % NR;
+          for (int di = dlo; di <= dhi; ++di) {
+            const float* src = (di >= -gr && di <= gr) ? HS : HF;
+            s += src[(size_t)slot * C + j];
+            if (++slot == NR) slot = 0;
+          }
+          pk = ((mx >> lane) & 1ull) && (p * fn > alpha * s) && ((double)p > thr_p);
+        }
+        if (dbmap && in) dbmap[orow * C + j] = 10.f * log10f(p + 1e-12f);
+        const unsigned long long b = __ballot(pk);
+        if (lane == 0) mask[orow * W + w] = b;
+        if (pk_pow && pk) pk_pow[orow * C + cnt + lanes_below(b)] = p;
+        cnt += __popcll(b);
+      }
+      if (lane == 0) row_count[orow] = cnt;
+    }
+    if (end > done) done = end;
+  }
+}
+
+bool detect_cfar_supported(int C, int hr, int hd) { return cfar_lds_bytes(C, hr, hd, 4) <= kCfarLdsMax; }
+
+hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, int gr, int gd, int tr,
+                              int td, float alpha, double thr_p, int i_lo, int i_hi, unsigned long long* mask,
+                              int* row_count, float* dbmap, float* pk_pow) {
+  if (F <= 0 || A <= 0 || S <= 0 || C <= 0) return hipSuccess;
+  const int hr = gr + tr, hd = gd + td;
+  const int W = (C + 63) / 64;
+  // rows per step: the largest of 16 / 8 / 4 whose rings leave room for three workgroups per CU, else 4
+  int RB = 4;
+  if (cfar_lds_bytes(C, hr, hd, 16) <= 48 * 1024) RB = 16;
+  else if (cfar_lds_bytes(C, hr, hd, 8) <= 48 * 1024) RB = 8;
+  const size_t lds = cfar_lds_bytes(C, hr, hd, RB);
+  if (lds > kCfarLdsMax) return hipErrorInvalidValue;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_detect_cfar),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  // strips of 128 rows (halo re-read 1.16x at hr = 10); 32 rows when that leaves the device short of workgroups
+  int R = 128;
+  if ((long long)F * A * ((S + R - 1) / R) < 1024) R = 32;
+  const long long nblk = (long long)F * A * ((S + R - 1) / R);
+  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_detect_cfar, dim3((unsigned)nblk), dim3(256), lds, st, rds, S, C, W, gr, gd, tr, td, alpha,
+                     thr_p, i_lo, i_hi, R, RB, mask, row_count, dbmap, pk_pow);
+  return hipGetLastError();
+}
+
+}  // namespace rsl
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif

@@ -43,6 +43,13 @@ bool work_packed_supported(int C, int S);
 // K3: 3x3 local max (reflect), threshold, range gate -> per-antenna bit masks + row counts.
 hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S, int C, double thr_p, int i_lo,
                          int i_hi, unsigned long long* mask, int* row_count, float* dbmap, float* pk_pow);
+// K3 alternative (rsl_cfar.hip): 2-D cell-averaging CFAR (guard gr x gd, training tr x td half-sizes; Doppler wraps,
+// range truncates) + 3x3 local max + range gate + power floor -> the same outputs as launch_detect, peak_pow
+// row-compact.  detect_cfar_supported: the rings of a window (hr, hd) = (gr + tr, gd + td) fit the CU's LDS at C.
+bool detect_cfar_supported(int C, int hr, int hd);
+hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, int gr, int gd, int tr,
+                              int td, float alpha, double thr_p, int i_lo, int i_hi, unsigned long long* mask,
+                              int* row_count, float* dbmap, float* pk_pow);
 // Per-frame offsets of peak entries (antenna-major) and union cells (range-major).
 hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const int* row_count, int F, int A, int S,
                           int C, int* entry_row_off, int* cell_row_off, int* cell_row_cnt, long long* entry_base,

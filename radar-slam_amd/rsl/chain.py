@@ -49,6 +49,17 @@ class ChainConfig:
     spectrum: bool = False                     # also write the MUSIC / beamforming spectrum of every cell, f32
                                                # cell-blocked [cells / 32, G, 32] (rsl.runtime.spectrum_rows)
                                                # (angle_estimation.py:299 stores spectrum f64[G] per target)
+    detector: str = 'threshold'                # 'threshold': the reference's rule (threshold_db + 3x3 maximum);
+                                               # 'cfar': 2-D CA-CFAR + 3x3 maximum, threshold_db kept as a floor
+                                               # (-inf switches the floor off)
+    cfar_guard: tuple = (2, 2)                 # guard half-sizes (range, doppler)
+    cfar_train: tuple = (8, 8)                 # training half-sizes (range, doppler)
+    cfar_pfa: float = 1e-4                     # false-alarm rate -> alpha (tables.cfar_alpha)
+    cfar_alpha: Optional[float] = None         # factor on the training mean; overrides cfar_pfa when set
+
+    def __post_init__(self):
+        if self.detector not in ('threshold', 'cfar'):
+            raise ValueError(f"detector must be 'threshold' or 'cfar', not {self.detector!r}")
 
     @property
     def S(self) -> int:
@@ -84,6 +95,10 @@ class RadarChain:
         self.table = ctx.to_dev(tab.astype(np.complex64))
         self.i_lo, self.i_hi = tables.range_gate(cfg.bandwidth, S, cfg.min_range, cfg.max_range)
         self.thr_p = tables.power_threshold(cfg.threshold_db)
+        self.cfar_alpha = None
+        if cfg.detector == 'cfar':
+            self.cfar_alpha = float(cfg.cfar_alpha) if cfg.cfar_alpha is not None else tables.cfar_alpha(
+                cfg.cfar_pfa, tables.cfar_training_cells(cfg.cfar_guard, cfg.cfar_train))
         d = cfg.antenna_spacing or cfg.lambda_c / 2
         self.grid = tables.azimuth_grid(cfg.search_range, cfg.search_resolution)
         self.steer = ctx.steering(tables.steering_matrix(self.grid, np.arange(A) * d, cfg.lambda_c))
@@ -170,6 +185,10 @@ class RadarChain:
                                mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow,
                                dc_removal=cfg.dc_removal)
         self._group = group
+        if cfg.detector == 'cfar':  # the CFAR detector rewrites the fused detector's mask, counts and peak powers
+            ctx.detect_cfar(self.rds, cfg.cfar_guard, cfg.cfar_train, self.cfar_alpha, self.thr_p, self.i_lo,
+                            self.i_hi, out=dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow))
+            self._group = 1
         if offsets:
             ctx.offsets(self.mask, self.row_count, self.C, bufs=self.offs)
         if emit:

@@ -105,6 +105,36 @@ def detect_peaks(rds, *, threshold_db=-20.0, i_lo=0, i_hi=1 << 30, want_db=True,
     return res
 
 
+def detect_peaks_cfar(rds, *, guard=(2, 2), train=(8, 8), pfa=1e-4, alpha=None, threshold_db=-math.inf, i_lo=0,
+                      i_hi=1 << 30, want_db=True, ctx: Optional[Context] = None):
+    """rds [A, S, C] -> the dictionary of detect_peaks, with the CA-CFAR detector (rsl_detect_cfar) in place of the
+    fixed threshold: guard / train (range, doppler) half-sizes, alpha on the training mean (default: from pfa and the
+    full-window count, tables.cfar_alpha); threshold_db remains as a floor (-inf: none)."""
+    c = _ctx(ctx)
+    d = as_dev_c64(c, rds)
+    if d.dim() == 3:
+        d = d.unsqueeze(0)
+    d = d.contiguous()
+    F, A, S, C = d.shape
+    if alpha is None:
+        alpha = tables.cfar_alpha(pfa, tables.cfar_training_cells(guard, train))
+    mask, rc, db = c.detect_cfar(d, guard, train, alpha, tables.power_threshold(threshold_db), i_lo, i_hi,
+                                 want_db=want_db)
+    offs = c.offsets(mask, rc, C)
+    ne = int(offs['entry_base'][F].item())
+    nc = int(offs['cell_base'][F].item())
+    lists = c.emit(d, mask, offs, ne, nc, want_pdb=True)
+    ant, rbin, dbin = unpack_coord(to_host(lists['e_coord'][:ne]))
+    res = dict(antenna=ant.astype(np.int64), range_bin=rbin.astype(np.int64), doppler_bin=dbin.astype(np.int64),
+               power_db=to_host(lists['e_pdb'][:ne], np.float64),
+               entry_base=to_host(offs['entry_base']), cells=nc)
+    if want_db:
+        res['power_spectrum_db'] = to_host(db, np.float64)
+        if F == 1:
+            res['power_spectrum_db'] = res['power_spectrum_db'][0]
+    return res
+
+
 # -- signatures as a pseudo-RDS [N, A, 1, 1] -------------------------------------------------------------
 def _sig_cells(c: Context, sigs: np.ndarray):
     torch = c.torch

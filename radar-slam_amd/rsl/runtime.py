@@ -215,6 +215,29 @@ class Context:
                                        _ptr(mask), _ptr(rc), _ptr(db), _ptr(pk)), 'rsl_detect')
         return mask, rc, db
 
+    def detect_cfar(self, rds, guard, train, alpha: float, thr_power: float, i_lo: int, i_hi: int,
+                    want_db: bool = False, out=None):
+        """CA-CFAR detector (rsl_detect_cfar): guard / train = (range, doppler) half-sizes, alpha on the training
+        mean, thr_power the power floor (negative: none).  Outputs as detect (peak_pow row-compact, group 1)."""
+        torch = self.torch
+        F, A, S, C = rds.shape
+        W = (C + 63) // 64
+        if out is None:
+            out = {}
+        mask = out.get('mask')
+        if mask is None:
+            mask = self.empty((F, A, S, W), torch.int64)
+        rc = out.get('row_count')
+        if rc is None:
+            rc = self.empty((F, A, S), torch.int32)
+        db = self.empty((F, A, S, C), torch.float32) if want_db else None
+        pk = out.get('peak_pow')
+        self._bind()
+        self.check(self.lib.rsl_detect_cfar(self.h, _ptr(rds), F, A, S, C, int(guard[0]), int(guard[1]),
+                                            int(train[0]), int(train[1]), float(alpha), float(thr_power), int(i_lo),
+                                            int(i_hi), _ptr(mask), _ptr(rc), _ptr(db), _ptr(pk)), 'rsl_detect_cfar')
+        return mask, rc, db
+
     def offsets(self, mask, row_count, C: int, bufs=None):
         torch = self.torch
         F, A, S, W = mask.shape

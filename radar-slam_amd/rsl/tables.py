@@ -67,6 +67,23 @@ def power_threshold(threshold_db: float) -> float:
     return float(10.0 ** (threshold_db / 10.0) - 1e-12)
 
 
+def cfar_training_cells(guard, train) -> int:
+    """Full-window training-cell count N of a 2-D CFAR window with half-sizes guard (range, doppler) and train
+    (range, doppler): the (2 hr + 1)(2 hd + 1) box without the (2 gr + 1)(2 gd + 1) guard box."""
+    gr, gd = int(guard[0]), int(guard[1])
+    tr, td = int(train[0]), int(train[1])
+    return (2 * (gr + tr) + 1) * (2 * (gd + td) + 1) - (2 * gr + 1) * (2 * gd + 1)
+
+
+def cfar_alpha(pfa: float, n_train: int) -> float:
+    """CA-CFAR factor on the training MEAN for false-alarm rate pfa: a square-law detector in exponential noise with
+    N training cells has Pfa = (1 + alpha / N)^-N, so alpha = N (pfa^(-1/N) - 1)."""
+    n = int(n_train)
+    if n < 1 or not (0.0 < pfa < 1.0):
+        raise ValueError('cfar_alpha: pfa must lie in (0, 1) and n_train be >= 1')
+    return float(n * (pfa ** (-1.0 / n) - 1.0))
+
+
 def azimuth_grid(search_range=(-90, 90), search_resolution=0.5):
     return np.arange(search_range[0], search_range[1] + search_resolution, search_resolution)
 
