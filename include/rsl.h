@@ -240,6 +240,43 @@ int rsl_velocity(rsl_handle h, const void* az, const void* gidx, const void* az_
                  const void* amask, const void* seg, long long n, int F, double k, double ridge, const double* bounds4,
                  void* out, void* resid, void* pred);
 
+/* Robust ego-velocity solve: Huber / Tukey iteratively re-weighted least squares (k_velocity_robust), an explicitly
+ *     selected alternative to rsl_velocity with the same model and inputs (az / gidx + az_table, y, amask, seg, n, k,
+ *     ridge, bounds4 as above).  Per frame, cell i has the direction (c_i, s_i) = (cos az_i, sin az_i), the
+ *     observation y_i, the multiplicity m_i = popcount(amask[i]) (1 when amask is null) and the residual
+ *     r_i(x) = y_i - k (x_0 c_i + x_1 s_i).
+ *     Losses, cut-off t = c sigma, both scaled so that rho(r) = r^2 for small r (costs compare with rsl_velocity's):
+ *       RSL_LOSS_HUBER  rho = r^2 if |r| <= t, else 2 t |r| - t^2;           u = 1 if |r| <= t, else t / |r|
+ *       RSL_LOSS_TUKEY  rho = (t^2/3)(1 - (1 - (r/t)^2)^3) if |r| < t, else t^2/3;  u = (1 - (r/t)^2)^2 if |r| < t, else 0
+ *     (t = 0: u = 1 where r = 0, else 0, and such cells count as inliers, for both losses).  The Python layers
+ *     default c to 1.345 (Huber) and 4.685 (Tukey).
+ *     Iteration: x^0 is exactly rsl_velocity's solution of the frame (same moments, ridge, box, and rule: the
+ *     interior solution if feasible, else the best edge).  For j = 1 .. iters: residuals at x^(j-1); sigma = scale
+ *     when scale > 0, else (scale <= 0) 1.4826 x the lower weighted median of (float)|r_i|, i.e. the smallest value a
+ *     such that the multiplicities of the cells with (float)|r_i| <= a sum to at least half the total (cells with
+ *     m_i = 0 do not count; the fp32 rounding is part of the definition, which makes the device's integer radix
+ *     select exact and order-independent); weights u_i; x^j = the box-constrained ridge LS with weights m_i u_i, by
+ *     the same 2x2 rule.  Stop after iteration j when max|x^j - x^(j-1)| <= tol (tol = 0: run exactly iters
+ *     iterations).  Also stop, keeping x and counting as converged, when sigma = 0, when sum m_i u_i = 0, or when the
+ *     segment is empty (or holds no multiplicity).
+ *     A given scale (the sensor's phase-noise sigma) with RSL_LOSS_TUKEY is the dependable configuration: it
+ *     recovered the inlier motion up to 45 % coherent outliers in the prototype.  The estimated scale starts from the
+ *     LS fit and breaks down beyond roughly 30 % coherent outliers.
+ *     out f64 [F, 8] = {v_x, v_y, cost, rmse_w, n_in, n, sigma, it}: cost = sum m_i rho(r_i) + ridge |v|^2;
+ *     rmse_w = sqrt(sum m_i u_i r_i^2 / sum m_i u_i) (0 when the denominator is 0); n_in = sum of m_i over the cells
+ *     with |r_i| <= t (Huber) or |r_i| < t (Tukey); n = sum m_i; sigma = the last sigma used; it = the number of
+ *     iterations run, negated when the stop rule was not met (never for tol = 0).  weight f32 [N] (nullable): u_i at
+ *     the returned x with the sigma of the last iteration; resid f64 [N] (nullable).  All at the returned x.
+ *     F = 0 launches nothing.  RSL_ERR_INVALID: loss not 1 or 2; c <= 0 or not finite; scale NaN or +inf; iters < 1
+ *     or > 1000; tol < 0 or NaN; ridge < 0; gidx with G > 2048 or without az_table; az and gidx both null; null y,
+ *     seg, out or bounds4.  Timed under RSL_K_VELOCITY. */
+#define RSL_LOSS_HUBER 1
+#define RSL_LOSS_TUKEY 2
+int rsl_velocity_robust(rsl_handle h, const void* az, const void* gidx, const void* az_table, int G,
+                        const void* y, const void* amask, const void* seg, long long n, int F, double k,
+                        double ridge, const double* bounds4, int loss, double c, double scale, int iters,
+                        double tol, void* out, void* weight, void* resid);
+
 /* a3-a6  SignalPreprocessor.dechirp_signal / apply_window / remove_dc / process_chirp (dechirp.py:85-166):
  *     out[r, s] = in[r, s] * table[s], then (dc != 0) minus the row's complex mean.  in/out c64 [rows, S]. */
 int rsl_preprocess_rows(rsl_handle h, const void* in, long long rows, int S, const void* table, int dc, void* out);

@@ -562,6 +562,35 @@ int rsl_velocity(rsl_handle h, const void* az, const void* gidx, const void* az_
                    "velocity");
 }
 
+int rsl_velocity_robust(rsl_handle h, const void* az, const void* gidx, const void* az_table, int G, const void* y,
+                        const void* amask, const void* seg, long long n, int F, double k, double ridge,
+                        const double* bounds4, int loss, double c, double scale, int iters, double tol, void* out,
+                        void* weight, void* resid) {
+  if (!h) return RSL_ERR_INVALID;
+  if (F < 0 || n < 0) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: bad argument");
+  if (loss != RSL_LOSS_HUBER && loss != RSL_LOSS_TUKEY)
+    return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: loss must be RSL_LOSS_HUBER or RSL_LOSS_TUKEY");
+  if (!(c > 0) || !std::isfinite(c)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: c must be finite, > 0");
+  if (std::isnan(scale) || (std::isinf(scale) && scale > 0))
+    return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: scale must be finite (<= 0: estimated)");
+  if (iters < 1 || iters > 1000) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: iters outside 1..1000");
+  if (!(tol >= 0)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: tol must be >= 0");
+  if (!(ridge >= 0)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: ridge must be >= 0");
+  if (F == 0) return RSL_OK;
+  if ((!az && !gidx) || !y || !seg || !bounds4 || !out)
+    return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: null pointer");
+  if (gidx && (!az_table || G <= 0 || G > 2048)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: bad grid table");
+  if (!(bounds4[0] <= bounds4[1]) || !(bounds4[2] <= bounds4[3]))
+    return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: bad bounds");
+  Scope sc(h, RSL_K_VELOCITY);
+  return hip_check(h,
+                   rsl::launch_velocity_robust(h->stream, (const double*)az, (const int*)gidx, (const double*)az_table,
+                                               G, (const double*)y, (const unsigned*)amask, (const long long*)seg, n, F,
+                                               k, ridge, bounds4, loss, c, scale, iters, tol, (double*)out,
+                                               (float*)weight, (double*)resid),
+                   "velocity_robust");
+}
+
 int rsl_preprocess_rows(rsl_handle h, const void* in, long long rows, int S, const void* table, int dc, void* out) {
   if (!h) return RSL_ERR_INVALID;
   if (rows < 0 || S <= 0 || !in || !table || !out) return fail(h, RSL_ERR_INVALID, "rsl_preprocess_rows: bad argument");

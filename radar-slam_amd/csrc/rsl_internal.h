@@ -98,6 +98,11 @@ hipError_t launch_velocity(hipStream_t st, const double* az, const int* gidx, co
                            const double* y, const unsigned* amask, const long long* seg, long long n, int F, double k,
                            double ridge,
                            const double* bounds4, double* out, double* resid, double* pred);
+// K8 alternative (rsl_vel_robust.hip): Huber / Tukey IRLS from the LS start, fixed or median-estimated scale.
+hipError_t launch_velocity_robust(hipStream_t st, const double* az, const int* gidx, const double* az_table, int G,
+                                  const double* y, const unsigned* amask, const long long* seg, long long n, int F,
+                                  double k, double ridge, const double* bounds4, int loss, double c, double scale,
+                                  int iters, double tol, double* out, float* weight, double* resid);
 
 // K9: greedy association and wrapped-phase multi-start solve (rsl_wrap.hip).
 // configs[3] pattern (rsl_scene.hip): per-cube top-k peak selection and the analyser's nearest association.

@@ -19,6 +19,9 @@ DOA_TOEPLITZ = 0x100
 DOA_SPEC_GMAJOR = 0x200
 DOA_SPEC_BLOCKED = 0x400
 STEER_TOEPLITZ = 1
+LOSS_HUBER, LOSS_TUKEY = 1, 2
+LOSS_IDS = {'huber': LOSS_HUBER, 'tukey': LOSS_TUKEY}
+LOSS_DEFAULT_C = {LOSS_HUBER: 1.345, LOSS_TUKEY: 4.685}  # 95 % efficiency at the normal distribution
 K_NAMES = ['range_fft', 'doppler_fft', 'detect', 'offsets', 'emit', 'doa_scan', 'cell_extras', 'confidence',
            'velocity', 'aux']
 
@@ -56,6 +59,8 @@ SIGNATURES = {
     'rsl_confidence': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_longlong, _P, _P, _P, _P]),
     'rsl_velocity': (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_longlong, c_int, c_double, c_double,
                              POINTER(c_double), _P, _P, _P]),
+    'rsl_velocity_robust': (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_longlong, c_int, c_double, c_double,
+                                    POINTER(c_double), c_int, c_double, c_double, c_int, c_double, _P, _P, _P]),
     'rsl_preprocess_rows': (c_int, [_P, _P, c_longlong, c_int, _P, c_int, _P]),
     'rsl_phase_model': (c_int, [_P, _P, _P, c_longlong, _P, c_double, _P, c_int, c_double, _P, _P, _P]),
     'rsl_associate': (c_int, [_P, _P, c_int, _P, c_int, c_double, _P, _P, _P]),

@@ -56,8 +56,18 @@ class ChainConfig:
     cfar_train: tuple = (8, 8)                 # training half-sizes (range, doppler)
     cfar_pfa: float = 1e-4                     # false-alarm rate -> alpha (tables.cfar_alpha)
     cfar_alpha: Optional[float] = None         # factor on the training mean; overrides cfar_pfa when set
+    velocity_loss: str = 'ls'                  # 'ls': rsl_velocity (plain box-constrained LS); 'huber' | 'tukey':
+                                               # rsl_velocity_robust (IRLS from the LS start, include/rsl.h)
+    velocity_scale: Optional[float] = None     # residual scale sigma (the sensor's phase-noise sigma, radians); None:
+                                               # estimated per iteration from the residuals' weighted median, which
+                                               # is dependable only below roughly 30 % coherent outliers
+    velocity_c: Optional[float] = None         # tuning constant; None: 1.345 (huber) / 4.685 (tukey)
+    velocity_iters: int = 30
+    velocity_tol: float = 1e-9
 
     def __post_init__(self):
+        if self.velocity_loss not in ('ls', 'huber', 'tukey'):
+            raise ValueError(f"velocity_loss must be 'ls', 'huber' or 'tukey', not {self.velocity_loss!r}")
         if self.detector not in ('threshold', 'cfar'):
             raise ValueError(f"detector must be 'threshold' or 'cfar', not {self.detector!r}")
 
@@ -126,6 +136,7 @@ class RadarChain:
         self.gidx = e((cc,), torch.int32)
         self.ext = dict(esprit=e((cc,), torch.float64), phase=e((cc,), torch.float64), az=e((cc,), torch.float64))
         self.vel = vel_out if vel_out is not None else e((F, 8), torch.float64)
+        self.vel_weight = e((cc,), torch.float32) if cfg.velocity_loss != 'ls' else None  # IRLS weight of every cell
         self.ncell_dev = self.offs['cell_base'][F:F + 1]
         # one signature gather for DoA + ESPRIT + phase when the Toeplitz path applies (uniform linear array)
         self.fused_doa = bool(self.steer['toeplitz']) and A >= 2 and not cfg.spectrum
@@ -221,7 +232,14 @@ class RadarChain:
                 ctx.cell_extras(self.rds, L['c_frame'], L['c_rc'], n=self.cell_cap, n_dev=self.ncell_dev,
                                 esprit_scale=self.esprit_scale, want_esprit=esprit, want_phase=velocity,
                                 bufs=self.ext)
-        if velocity:
+        if velocity and cfg.velocity_loss != 'ls':
+            # vel columns 2-7 become {cost, rmse_w, n_in, n, sigma, it} (include/rsl.h)
+            ctx.velocity_robust(None, self.ext['phase'], self.offs['cell_base'], k=self.k, loss=cfg.velocity_loss,
+                                c=cfg.velocity_c, scale=cfg.velocity_scale, iters=cfg.velocity_iters,
+                                tol=cfg.velocity_tol, ridge=cfg.ridge, bounds=cfg.bounds, amask=L['c_amask'],
+                                out=self.vel, gidx=self.gidx, az_table=self.az_table, n=self.cell_cap,
+                                want_weight=self.vel_weight)
+        elif velocity:
             ctx.velocity(None, self.ext['phase'], self.offs['cell_base'], k=self.k, ridge=cfg.ridge,
                          bounds=cfg.bounds, amask=L['c_amask'], out=self.vel, gidx=self.gidx, az_table=self.az_table,
                          n=self.cell_cap)
@@ -238,10 +256,11 @@ class RadarChain:
             raise RuntimeError(f"peak capacity exceeded: entries {ne}/{self.entry_cap}, cells {nc}/{self.cell_cap}")
         L = self.lists
         h = lambda t, n: t[:n].cpu().numpy()
+        extra = dict(vel_weight=h(self.vel_weight, nc)) if self.vel_weight is not None else {}
         return dict(entry_base=self.offs['entry_base'].cpu().numpy(), cell_base=self.offs['cell_base'].cpu().numpy(),
                     **dict(zip(('e_ant', 'e_rbin', 'e_dbin'), unpack_coord(h(L['e_coord'], ne)))),
                     e_cell=h(L['e_cell'], ne), e_pdb=h(L['e_pdb'], ne).astype(np.float64), c_frame=h(L['c_frame'], nc),
                     c_rc=h(L['c_rc'], nc), c_amask=h(L['c_amask'], nc), gidx=h(self.gidx, nc),
                     esprit=h(self.ext['esprit'], nc), phase=h(self.ext['phase'], nc),
                     az=np.radians(self.grid)[h(self.gidx, nc)],
-                    velocity=self.vel.cpu().numpy(), grid=self.grid)
+                    velocity=self.vel.cpu().numpy(), grid=self.grid, **extra)

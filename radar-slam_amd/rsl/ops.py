@@ -275,6 +275,36 @@ def bvls(pos, ang, y, k, lo, hi, ridge=0.0, ctx: Optional[Context] = None):
     return o[:nv], float(o[nv])
 
 
+def solve_velocity_robust(az, y, *, k, loss='tukey', c=None, scale=None, iters=30, tol=1e-9, ridge=0.0,
+                          bounds=(-50.0, 50.0, -50.0, 50.0), amask=None, ctx: Optional[Context] = None):
+    """Huber / Tukey IRLS solve of one host segment (rsl_velocity_robust, one frame): az radians [N], y observed phase
+    [N], amask optional antenna masks (multiplicity = popcount).  scale=None estimates sigma from the residuals'
+    median (dependable only below roughly 30 % coherent outliers); give the sensor's phase-noise sigma where it is
+    known.  Returns the out row by name (velocity [2], cost, rmse_w, num_inliers, num_targets, scale, iterations,
+    converged) plus weights and residuals [N]."""
+    cx = _ctx(ctx)
+    az = np.ascontiguousarray(np.asarray(az, np.float64).reshape(-1))
+    yy = np.ascontiguousarray(np.asarray(y, np.float64).reshape(-1))
+    if az.shape != yy.shape:
+        raise ValueError(f'az and y must have the same length, not {az.shape[0]} and {yy.shape[0]}')
+    n = yy.shape[0]
+    pad = lambda a: a if n else np.zeros(1, a.dtype)  # an empty segment still needs a valid pointer
+    d_az, d_y = cx.to_dev(pad(az)), cx.to_dev(pad(yy))
+    d_m = None
+    if amask is not None:
+        am = np.asarray(amask).astype(np.int64).reshape(-1)
+        if am.shape[0] != n:
+            raise ValueError('amask must have the length of y')
+        d_m = cx.to_dev(pad((am & 0xffffffff).astype(np.uint32).view(np.int32)))
+    seg = cx.to_dev(np.array([0, n], np.int64))
+    out, w, r = cx.velocity_robust(d_az, d_y, seg, k=k, loss=loss, c=c, scale=scale, iters=iters, tol=tol, ridge=ridge,
+                                   bounds=bounds, amask=d_m, n=n, want_weight=True, want_resid=True)
+    o = to_host(out)[0]
+    return dict(velocity=o[:2].copy(), cost=float(o[2]), rmse_w=float(o[3]), num_inliers=int(o[4]),
+                num_targets=int(o[5]), scale=float(o[6]), iterations=int(abs(o[7])), converged=bool(o[7] >= 0),
+                weights=to_host(w, np.float64)[:n], residuals=to_host(r)[:n])
+
+
 # -- a30 / a31: cross-frame association and wrapped-phase solve ------------------------------------------
 def associate(cur_xy, prev_xy, thr: float, ctx: Optional[Context] = None):
     """Greedy nearest-unused association (velocity_solver_improved.py:74-129) on the device.

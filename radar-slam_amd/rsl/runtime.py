@@ -423,6 +423,40 @@ class Context:
                    'rsl_velocity')
         return o, resid, pred
 
+    def velocity_robust(self, az, y, seg, *, k: float, loss, c: Optional[float] = None, scale: Optional[float] = None,
+                        iters: int = 30, tol: float = 1e-9, ridge: float = 0.0, bounds=(-50.0, 50.0, -50.0, 50.0),
+                        amask=None, gidx=None, az_table=None, n=None, out=None, want_weight=False, want_resid=False):
+        """Huber / Tukey IRLS velocity solve (rsl_velocity_robust; the estimator is specified in include/rsl.h).
+        loss: 'huber' | 'tukey' or the _lib.LOSS_* id; c=None: the loss's default tuning constant; scale=None: sigma
+        estimated per iteration from the residuals' weighted median (dependable only below roughly 30 % coherent
+        outliers; pass the sensor's phase-noise sigma where it is known).  want_weight: True, or a device f32 [N]
+        buffer to fill.  Returns (out f64 [F, 8], weight f32 [N] or None, resid f64 [N] or None)."""
+        torch = self.torch
+        if isinstance(loss, str):
+            if loss not in _lib.LOSS_IDS:
+                raise ValueError(f"loss must be 'huber' or 'tukey', not {loss!r}")
+            loss = _lib.LOSS_IDS[loss]
+        loss = int(loss)
+        if c is None:
+            c = _lib.LOSS_DEFAULT_C.get(loss, 1.0)  # an unknown id is rejected by the library
+        F = int(seg.shape[0]) - 1
+        o = out if out is not None else self.empty((max(F, 1), 8), torch.float64)
+        N = int(y.shape[0]) if n is None else min(int(n), int(y.shape[0]))
+        G = int(az_table.shape[0]) if az_table is not None else 0
+        if want_weight is True:
+            weight = self.empty((max(N, 1),), torch.float32)
+        else:
+            weight = None if want_weight is False or want_weight is None else want_weight
+        resid = self.empty((max(N, 1),), torch.float64) if want_resid else None
+        b4 = (c_double * 4)(*[float(x) for x in bounds])
+        self._bind()
+        self.check(self.lib.rsl_velocity_robust(self.h, _ptr(az), _ptr(gidx), _ptr(az_table), G, _ptr(y), _ptr(amask),
+                                                _ptr(seg), N, F, float(k), float(ridge), b4, loss, float(c),
+                                                0.0 if scale is None else float(scale), int(iters), float(tol),
+                                                _ptr(o), _ptr(weight), _ptr(resid)),
+                   'rsl_velocity_robust')
+        return o, weight, resid
+
 
 _ctx_lock = threading.Lock()
 _ctx: Dict[int, Context] = {}

@@ -125,6 +125,28 @@ class VelocitySolver:
         obs = self.compute_observed_phase_differences(rds_data, target_info)
         return self.two_step_optimization(pos, ang, obs, dt, initial_guess)
 
+    def solve_velocity_robust(self, rds_data: np.ndarray, target_info: List[Dict], dt: float = 0.1,
+                              loss: str = 'tukey', scale: Optional[float] = None, c: Optional[float] = None) -> Dict:
+        """Outlier-rejecting variant of solve_velocity (not in the reference): Huber / Tukey IRLS of the planar
+        two-unknown problem on the targets' azimuths and observed phases (``rsl_velocity_robust``, specified in
+        include/rsl.h).  ``scale`` is the residual scale sigma in radians; give the sensor's phase-noise sigma where it
+        is known (with 'tukey' the dependable configuration).  ``None`` estimates it from the residuals' median, which
+        starts from the LS fit and breaks down beyond roughly 30 % coherent outliers.  Returns the solve_velocity keys
+        it can fill plus ``weights``, ``num_inliers``, ``scale`` and ``iterations``."""
+        N = len(target_info)
+        if N < 3:
+            logger.warning("Insufficient targets for optimization")
+            return {'success': False, 'message': 'Insufficient targets'}
+        az = np.array([t['azimuth_rad'] for t in target_info], dtype=np.float64)
+        obs = self.compute_observed_phase_differences(rds_data, target_info)
+        r = ops.solve_velocity_robust(az, obs, k=self._k(dt), loss=loss, c=c, scale=scale,
+                                      bounds=(_TRANS_BOUNDS[0][0], _TRANS_BOUNDS[0][1], _TRANS_BOUNDS[1][0],
+                                              _TRANS_BOUNDS[1][1]))
+        return {'success': True, 'velocity': np.array([r['velocity'][0], r['velocity'][1], 0.0]),
+                'angular_velocity': np.zeros(3), 'cost': r['cost'], 'rmse': r['rmse_w'], 'residuals': r['residuals'],
+                'num_targets': N, 'weights': r['weights'], 'num_inliers': r['num_inliers'], 'scale': r['scale'],
+                'iterations': r['iterations']}
+
     def visualize_results(self, results: Dict, save_path: Optional[str] = None) -> None:
         if not results['success']:
             logger.warning("Cannot visualize failed optimization")
