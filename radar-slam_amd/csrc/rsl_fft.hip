@@ -128,9 +128,10 @@ RSL_DEV void st8(float2* p, float2 x) {
   }
 }
 
-// Packed `work` (K1 -> K2 at S = 512, C = 128).  Per K1 tile (frame, antenna, 8-chirp block cb)
-// a 24 KiB block of 6 planes x 256 bin pairs x 16 B: planes 0-2 hold the even bin 2p of pair p, planes 3-5 the odd
-// bin 2p + 1, each bin's 8 rows x (re, im) as 16 fields of 23 bits plus the bin's exponent (12 dwords, 3 x 16 B).
+// Packed `work` (K1 -> K2 at the work_packed_supported shapes).  Per K1 tile (frame, antenna, chirp
+// class cb) a block of 6 planes x S / 2 bin pairs x 16 B (24 KiB at S = 512; pk_plane_bytes, pk_tile_bytes): planes
+// 0-2 hold the even bin 2p of pair p, planes 3-5 the odd bin 2p + 1, each bin's 8 rows x (re, im) as 16 fields of 23
+// bits plus the bin's exponent (12 dwords, 3 x 16 B).
 // Every K1 store and every K2 load is a 16-B access: a K1 wave stores 1 KiB runs (lane = pair), a K2 lane loads the 3
 // chunks of one (bin, chirp block) and a wave's loads cover whole 128-B lines (16 bins = 8 pairs of one plane, or the
 // other plane).  Each bin of a tile has its own exponent e (int8); a field is n = rint(v 2^(22 - e)), |n| < 2^22, stored
@@ -141,8 +142,8 @@ RSL_DEV void st8(float2* p, float2 x) {
 // fields were 24-bit with the 24th bit always 0: the same values, bit for bit).
 // 6 B per value instead of 8: K1 + K2 move 14.0 instead of 16.8 MB per cfg2 frame.
 constexpr float kPkMagic = 12582912.0f;  // 1.5 * 2^23
-constexpr int kPkPlane = 4096;           // bytes per plane of one tile (256 pairs x 16 B)
-constexpr int kPkTile = 6 * kPkPlane;    // bytes per tile
+constexpr int pk_plane_bytes(int S) { return 8 * S; }                 // one plane of one tile: S / 2 pairs x 16 B
+constexpr int pk_tile_bytes(int S) { return 6 * pk_plane_bytes(S); }  // one tile
 constexpr int kR128Pitch = 128 + 7;      // k_doppler_detect_r128 tile row pitch (float2)
 constexpr int kR128Skew = 1;             // ... and the upper halo row's extra offset
 // frexp exponent of the largest |component| (abs bits), clamped so that both scale factors are normal floats
@@ -202,6 +203,78 @@ RSL_DEV void pk_unpack16(const uint4 (&w)[3], float (&f)[16]) {
     f[4 * g + 3] = b.y;
   }
 }
+
+// K1's packed epilogue (k_range_fft_r512 / _r1024 / _r256): the thread in slot `slot` holds bins 2 slot, 2 slot + 1 of
+// the tile's 8 rows (chirps cb + (C / 8) q), at obuf[q * pitch + pos] (one 16-B read per row; pos carries the kernel's
+// bank swizzle).  The Doppler transform's first step runs here in registers, Y[k1] = W_C^(cb k1) DFT8_q (K2 starts from
+// the step over the classes), and both bins are stored packed: six 16-B stores.  NTW: stored with the nt hint.
+template <int S, bool NTW>
+RSL_DEV void k1_packed_store(const float2* obuf, int pitch, int pos, int cb, const float2* __restrict__ tw,
+                             float2* __restrict__ work, size_t tile, int slot) {
+  float2 y0[8], y1[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const float4 ab = *reinterpret_cast<const float4*>(obuf + q * pitch + pos);
+    y0[q] = make_float2(ab.x, ab.y);
+    y1[q] = make_float2(ab.z, ab.w);
+  }
+  Dft<8>::run(y0);
+  Dft<8>::run(y1);
+  const int cbs = __builtin_amdgcn_readfirstlane(cb);  // the tile is workgroup-uniform
+#pragma unroll
+  for (int k = 1; k < 8; ++k) {
+    const float2 wk = tw[4 * cbs * k];  // W_C^(cb k) = W_S^(4 cb k), 4 cb k < 7 S / 8 (workgroup-uniform: scalar loads)
+    y0[k] = cmul(y0[k], wk);
+    y1[k] = cmul(y1[k], wk);
+  }
+  float f0[16], f1[16];
+  unsigned m0 = 0u, m1 = 0u;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    f0[2 * q] = y0[q].x;
+    f0[2 * q + 1] = y0[q].y;
+    f1[2 * q] = y1[q].x;
+    f1[2 * q + 1] = y1[q].y;
+    m0 = max(m0, max(__float_as_uint(y0[q].x) & 0x7FFFFFFFu, __float_as_uint(y0[q].y) & 0x7FFFFFFFu));
+    m1 = max(m1, max(__float_as_uint(y1[q].x) & 0x7FFFFFFFu, __float_as_uint(y1[q].y) & 0x7FFFFFFFu));
+  }
+  const int e0 = pk_exp(m0), e1 = pk_exp(m1);
+  uint4 w0[3], w1[3];
+  pk_pack16(f0, e0, w0);
+  pk_pack16(f1, e1, w1);
+  constexpr int PL = pk_plane_bytes(S) / 16;
+  uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(work) + tile * pk_tile_bytes(S)) + slot;
+#pragma unroll
+  for (int jj = 0; jj < 3; ++jj) {
+    st16<NTW>(reinterpret_cast<float4*>(dst + jj * PL), __builtin_bit_cast(float4, w0[jj]));
+    st16<NTW>(reinterpret_cast<float4*>(dst + (jj + 3) * PL), __builtin_bit_cast(float4, w1[jj]));
+  }
+}
+
+// K2's packed prologue (k_doppler_detect_r128 / _r256 / _r64): the unit (3 x 16 B) of range bin k in chirp class cls of
+// the (frame, antenna) whose first K1 tile is tile0.  DBG 6 (development builds): no work loads, a constant fill.
+template <int S, int DBG>
+RSL_DEV void pk_load_unit(const float2* __restrict__ work, size_t tile0, int k, int cls, uint4 (&w)[3]) {
+  constexpr int PL = pk_plane_bytes(S);
+  const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(work) +
+                                                    (tile0 + cls) * pk_tile_bytes(S) + (size_t)(3 * (k & 1)) * PL) +
+                     (k >> 1);
+#pragma unroll
+  for (int jj = 0; jj < 3; ++jj) {
+    if constexpr (DBG == 6)
+      w[jj] = make_uint4(0x4B4000u + threadIdx.x, 0x5Au * jj, 0x4B40u + k, 0x12345u);
+    else
+      w[jj] = src[jj * (PL / 16)];
+  }
+}
+// The halo range bin below (side 0) or above (side 1) the KB-bin tile at k0, periodic in S ('reflect' is applied in the
+// detect stage).
+RSL_DEV int dd_halo_bin(int k0, int KB, int side, int S) {
+  const int k = side ? k0 + KB : k0 - 1;
+  return k < 0 ? k + S : (k >= S ? k - S : k);
+}
+// The ablation values the packed K2 kernels forward to dd_tile_compute_reg (6 and 7 act in their own prologue).
+constexpr int dd_reg_dbg(int DBG) { return (DBG == 4 || DBG == 5 || DBG == 8 || DBG == 9) ? DBG : 0; }
 
 // Grid of a persistent kernel: resident workgroups only (occupancy x CUs), at most ntile.
 static long resident_grid(const void* kern, size_t lds, long ntile, int nt = kThreads) {
@@ -294,17 +367,71 @@ __global__ __launch_bounds__(kThreads) void k_range_fft(const float2* __restrict
   }
 }
 
+// The tile walk of the persistent K1 kernels.  DYN: workgroup b serves XCD x = b % 8 (dispatch order) and walks that
+// XCD's tile range [lo, hi) with its gx workgroups: the first two tiles are static (lo + b / 8, then + gx), every later
+// one comes from the XCD's dequeue head (rfq: kRfQueueBytes above), claimed one tile ahead (the atomic returns during a
+// whole tile), so workgroups that start late (CUs held by a concurrent kernel) take fewer tiles (tools/dyn.sh: K1 alone
+// 1.499 vs 1.667 ms per 1000 cfg2 frames for the static walk, outputs bit-identical).  A tile's body calls claim() at
+// its top and publish(claim) before its last barrier, which hands tile lo + 2 gx + claim over through the LDS word
+// *nn: written before that barrier, read after it, rewritten only after the next body's first barrier.  Every body
+// call claims once and every tile below hi is consumed once, so an XCD's claims are 0 .. hi - lo - 1 and the largest
+// index the walk forms is hi + 2 gx - 1 (k1_tiles_fit).  The XCD's last workgroup to leave (every dequeue of a leaver
+// has returned) resets the head and the exit counter for the stream's next launch.  Without DYN (grids of fewer than 8
+// workgroups) the walk is static over [0, ntile) with stride gridDim.x.
+// run() drives load(nx, t) (tile t's global loads into the registers nx) and body(nx, t, tn) (tile t from nx, refilling
+// nx with tile tn while it computes; a body narrows t / tn itself where it wants them scalar).
+template <bool DYN>
+struct TileWalk {
+  long lo, hi, gx;
+  unsigned* head;  // this XCD's dequeue head (the exit counter: + 256)
+  long* nn;        // the hand-off word (LDS, the kernel's)
+  RSL_DEV TileWalk(long ntile, unsigned* rfq, long* nn_) : nn(nn_) {
+    const int xcd = blockIdx.x & 7;
+    gx = ((long)gridDim.x - xcd + 7) / 8;
+    lo = DYN ? xcd * ntile / 8 : 0;
+    hi = DYN ? (xcd + 1) * ntile / 8 : ntile;
+    head = rfq + xcd * 32;
+  }
+  RSL_DEV unsigned claim() const {
+    unsigned c = 0;
+    if (DYN && threadIdx.x == 0) c = atomicAdd(head, 1u);
+    return c;
+  }
+  RSL_DEV void publish(unsigned c) const {
+    if (DYN && threadIdx.x == 0) *nn = lo + 2 * gx + (long)c;
+  }
+  template <class T, int N, class Load, class Body>
+  RSL_DEV void run(Load&& load, Body&& body) const {
+    T nx[N];
+    if constexpr (DYN) {
+      long t = lo + (blockIdx.x >> 3), tn = t + gx;
+      if (t < hi) load(nx, t);
+      while (t < hi) {
+        body(nx, t, tn);
+        t = tn;
+        tn = *nn;
+      }
+      if (threadIdx.x == 0 && atomicAdd(head + 8 * 32, 1u) == (unsigned)gx - 1u) {
+        atomicExch(head, 0u);
+        atomicExch(head + 8 * 32, 0u);
+      }
+    } else {
+      const long G = gridDim.x;
+      long t = blockIdx.x;
+      if (t < hi) load(nx, t);
+      for (; t < hi; t += G) body(nx, t, t + G);
+    }
+  }
+};
+
 // Persistent K1: the grid holds only resident workgroups; each loops over (frame, antenna, chirp-block) tiles
 // and issues the next tile's 16-B global loads into registers before running the current tile's LDS FFT, so
 // HBM latency overlaps the FFT instead of stalling every tile's load phase.  Requires even S with
 // CB * S / 2 a multiple of the block size (every power-of-two S >= 16).  Cube loads and `work` stores are
 // non-temporal (`nt`: both streamed once per batch; tools/cp_ab.py: 1.48-1.57 vs 1.57-1.64 ms per 1000 cfg2 frames).
-// DYN: workgroup b serves XCD x = b % 8 (dispatch order) and walks that XCD's tile range [lo, hi): its first two tiles
-// are static, every later one comes from the XCD's dequeue head, claimed one tile ahead (the atomic returns during a
-// whole tile), so workgroups that start late (CUs held by a concurrent kernel) take fewer tiles (tools/dyn.sh: K1 alone
-// 1.499 vs 1.667 ms per 1000 cfg2 frames for the static walk, outputs bit-identical).  Without DYN (grids of fewer
-// than 8 workgroups) the walk is static.  DBG (development builds only; ablations with wrong results): 1 no FFT,
-// 2 no cube loads (constant tiles), 3 loads and LDS staging only (no FFT, no stores).
+// The tiles come from a TileWalk: DYN on grids that span the 8 XCDs, static on grids of fewer than 8 workgroups.
+// DBG (development builds only; ablations with wrong results): 1 no FFT, 2 no cube loads (constant tiles), 3 loads and
+// LDS staging only (no FFT, no stores).
 template <int S, int CB, bool DYN, int DBG = 0>
 __global__ __launch_bounds__(kThreads) void k_range_fft_p(const float2* __restrict__ cube, int A, int Ct, int c0,
                                                            int C, long ntile, const float2* __restrict__ table,
@@ -321,7 +448,6 @@ __global__ __launch_bounds__(kThreads) void k_range_fft_p(const float2* __restri
   float2* buf = sm + lp_row(S);
   const int tid = threadIdx.x;
   const int ncb = (C + CB - 1) / CB;
-  const long G = gridDim.x;
   for (int k = tid; k < S; k += kThreads) tws[lp(k)] = tw[k];
   const float4* tab4 = reinterpret_cast<const float4*>(table);
   // the thread's table entries (one float4 when the block spans whole rows: every q hits the same samples)
@@ -347,14 +473,10 @@ __global__ __launch_bounds__(kThreads) void k_range_fft_p(const float2* __restri
     }
   };
   __shared__ long s_nn;
-  const int xcd = blockIdx.x & 7;
-  const long gx = (G - xcd + 7) / 8;
-  const long lo = DYN ? xcd * ntile / 8 : 0, hi = DYN ? (xcd + 1) * ntile / 8 : ntile;
-  unsigned* head = rfq + xcd * 32;  // this XCD's dequeue head (the exit counter: + 256)
+  const TileWalk<DYN> walk(ntile, rfq, &s_nn);
   // one tile: stage nx (x conj(ref) w) in LDS, refill nx with tile tn, FFT, DC bin, store
   auto body = [&](float4(&nx)[PF], long t, long tn) {
-    unsigned claim = 0;
-    if (DYN && tid == 0) claim = atomicAdd(head, 1u);
+    const unsigned claim = walk.claim();
     const int cb = (int)(t % ncb);
     const long fa = t / ncb;
     const int nrows = min(CB, C - cb * CB);
@@ -369,10 +491,10 @@ __global__ __launch_bounds__(kThreads) void k_range_fft_p(const float2* __restri
       buf[r * LD + lp(2 * s2 + 1)] = cmul(make_float2(x.z, x.w), make_float2(tb.z, tb.w));
     }
     __syncthreads();
-    if (tn < hi) load(nx, tn);  // in flight during the FFT below
+    if (tn < walk.hi) load(nx, tn);  // in flight during the FFT below
     if constexpr (DBG == 3) {  // loads only: keep the staged tile live, skip the FFT and the stores
       if (buf[tid * 2].x == 1.2345e30f) work[tid] = buf[tid * 2];
-      if (DYN && tid == 0) s_nn = lo + 2 * gx + (long)claim;
+      walk.publish(claim);
       __syncthreads();
       return;
     }
@@ -391,29 +513,10 @@ __global__ __launch_bounds__(kThreads) void k_range_fft_p(const float2* __restri
         st16<true>(dst4 + idx, make_float4(lo2.x, lo2.y, hi2.x, hi2.y));
       }
     }
-    if (DYN && tid == 0) s_nn = lo + 2 * gx + (long)claim;
+    walk.publish(claim);
     __syncthreads();  // buf is rewritten by the next tile
   };
-  if constexpr (DYN) {
-    long t = lo + (blockIdx.x >> 3), tn = t + gx;
-    float4 nx[PF];
-    if (t < hi) load(nx, t);
-    while (t < hi) {
-      body(nx, t, tn);
-      t = tn;
-      tn = s_nn;  // written before body's last barrier, rewritten only after the next body's first one
-    }
-    // every dequeue of this workgroup has returned: the XCD's last leaver resets the slot for its next launch
-    if (tid == 0 && atomicAdd(head + 8 * 32, 1u) == (unsigned)gx - 1u) {
-      atomicExch(head, 0u);
-      atomicExch(head + 8 * 32, 0u);
-    }
-    return;
-  }
-  long t = blockIdx.x;
-  float4 nx[PF];
-  if (t < ntile) load(nx, t);
-  for (; t < ntile; t += G) body(nx, t, t + G);
+  walk.template run<float4, PF>(load, body);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -445,7 +548,7 @@ RSL_DEV float2 w32(int k) {                // exp(-2 pi i k / 32), k < 16
   return make_float2(c[k], c[(k + 8) & 15] * (k < 8 ? 1.f : -1.f));  // -sin(2 pi k / 32)
 }
 
-template <bool DYN, int DBG = 0, bool NTW = true>
+template <int DBG = 0, bool NTW = true>
 __global__ __launch_bounds__(kThreads) void k_range_fft_r512(const float2* __restrict__ cube, int A, int Ct, int c0,
                                                               int C, long ntile, const float2* __restrict__ table,
                                                               const float2* __restrict__ tw, int dc,
@@ -463,14 +566,13 @@ __global__ __launch_bounds__(kThreads) void k_range_fft_r512(const float2* __res
   const int k1b = (tid >> 1) & 15, h = tid & 1;
   constexpr int ncb = 128 / CB;  // C = 128 wherever this kernel runs (work_packed_supported): tile index math by shifts
   (void)C;
-  const long G = gridDim.x;
   for (int k = tid; k < S; k += kThreads) ldtab[k] = table[k];
   for (int k = tid; k < 32 * 16; k += kThreads) {
     const int jj = k >> 4, kk = k & 15;
     ldtw[jj * kR512TwPitch + kk] = tw[jj * kk];  // W512^(j k1), j k1 <= 465
   }
   auto load = [&](float2(&nx)[16], long t) {
-    t = (long)__builtin_amdgcn_readfirstlane((int)t);  // the tile index is workgroup-uniform (ntile < 2^31)
+    t = (long)__builtin_amdgcn_readfirstlane((int)t);  // the tile index is workgroup-uniform (below 2^31: k1_tiles_fit)
     const int cb = (int)(t % ncb);
     const long fa = t / ncb;
     const float2* src = cube + ((size_t)fa * Ct + c0 + cb + 16 * row) * S + j;  // chirp class cb, row q = row
@@ -483,18 +585,14 @@ __global__ __launch_bounds__(kThreads) void k_range_fft_r512(const float2* __res
     }
   };
   __shared__ long s_nn;
-  const int xcd = blockIdx.x & 7;
-  const long gx = (G - xcd + 7) / 8;
-  const long lo = DYN ? xcd * ntile / 8 : 0, hi = DYN ? (xcd + 1) * ntile / 8 : ntile;
-  unsigned* head = rfq + xcd * 32;  // this XCD's dequeue head (the exit counter: + 256)
+  const TileWalk<true> walk(ntile, rfq, &s_nn);
   __syncthreads();
   auto body = [&](float2(&nx)[16], long t, long tn) {
-    // workgroup-uniform tile indices (read from LDS or derived from blockIdx; ntile < 2^31, checked by the launcher):
-    // scalar, so the tile's address arithmetic runs on the SALU
+    // workgroup-uniform tile indices (read from LDS or derived from blockIdx; below 2^31: k1_tiles_fit): scalar, so the
+    // tile's address arithmetic runs on the SALU
     t = (long)__builtin_amdgcn_readfirstlane((int)t);
     tn = (long)__builtin_amdgcn_readfirstlane((int)tn);
-    unsigned claim = 0;
-    if (DYN && tid == 0) claim = atomicAdd(head, 1u);
+    const unsigned claim = walk.claim();
     const int cb = (int)(t % ncb);
     const long fa = t / ncb;
     float2 v[16];
@@ -502,10 +600,10 @@ __global__ __launch_bounds__(kThreads) void k_range_fft_r512(const float2* __res
     for (int m = 0; m < 16; ++m) v[m] = cmul(nx[m], ldtab[j + 32 * m]);
     // in flight during this tile's transforms and stores; unconditional (past the range: this tile again, an L2 hit
     // once per workgroup), which spares a copy of the 32 loaded registers per tile
-    load(nx, tn < hi ? tn : t);
+    load(nx, tn < walk.hi ? tn : t);
     if constexpr (DBG == 3) {
       if (v[0].x == 1.2345e30f) work[tid] = v[1];
-      if (DYN && tid == 0) s_nn = lo + 2 * gx + (long)claim;
+      walk.publish(claim);
       __syncthreads();
       return;
     }
@@ -541,70 +639,12 @@ __global__ __launch_bounds__(kThreads) void k_range_fft_r512(const float2* __res
 #pragma unroll
     for (int k = 0; k < 16; ++k) ow[16 * k] = xo[k];
     __syncthreads();
-    // thread tid holds bins 2 tid, 2 tid + 1 of the 8 rows (chirps cb + 16 q): the Doppler transform's first step,
-    // Y[k1] = W128^(cb k1) DFT8_q, here in registers (K2 starts from the 16-point step)
-    float2 y0[8], y1[8];
-    const int pos = 2 * tid + (tid >= 128 ? 8 : 0);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float4 ab = *reinterpret_cast<const float4*>(obuf + q * kR512Obuf + pos);
-      y0[q] = make_float2(ab.x, ab.y);
-      y1[q] = make_float2(ab.z, ab.w);
-    }
-    Dft<8>::run(y0);
-    Dft<8>::run(y1);
-    const int cbs = __builtin_amdgcn_readfirstlane(cb);  // the tile is workgroup-uniform
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-      const float2 wk = tw[4 * cbs * k];  // W128^(cb k) = W512^(4 cb k), 4 cb k <= 420 (workgroup-uniform: scalar loads)
-      y0[k] = cmul(y0[k], wk);
-      y1[k] = cmul(y1[k], wk);
-    }
-    // packed store
-    float f0[16], f1[16];
-    unsigned m0 = 0u, m1 = 0u;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      f0[2 * q] = y0[q].x;
-      f0[2 * q + 1] = y0[q].y;
-      f1[2 * q] = y1[q].x;
-      f1[2 * q + 1] = y1[q].y;
-      m0 = max(m0, max(__float_as_uint(y0[q].x) & 0x7FFFFFFFu, __float_as_uint(y0[q].y) & 0x7FFFFFFFu));
-      m1 = max(m1, max(__float_as_uint(y1[q].x) & 0x7FFFFFFFu, __float_as_uint(y1[q].y) & 0x7FFFFFFFu));
-    }
-    const int e0 = pk_exp(m0), e1 = pk_exp(m1);
-    uint4 w0[3], w1[3];
-    pk_pack16(f0, e0, w0);
-    pk_pack16(f1, e1, w1);
-    const size_t tile = (size_t)fa * ncb + cb;
-    uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(work) + tile * kPkTile) + tid;
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj) {
-      st16<NTW>(reinterpret_cast<float4*>(dst + jj * (kPkPlane / 16)), __builtin_bit_cast(float4, w0[jj]));
-      st16<NTW>(reinterpret_cast<float4*>(dst + (jj + 3) * (kPkPlane / 16)), __builtin_bit_cast(float4, w1[jj]));
-    }
-    if (DYN && tid == 0) s_nn = lo + 2 * gx + (long)claim;
+    // thread tid holds bins 2 tid, 2 tid + 1 of the 8 rows (chirps cb + 16 q); the b >= 256 half sits 8 later
+    k1_packed_store<S, NTW>(obuf, kR512Obuf, 2 * tid + (tid >= 128 ? 8 : 0), cb, tw, work, (size_t)fa * ncb + cb, tid);
+    walk.publish(claim);
     __syncthreads();  // obuf is read above; the next tile's exchange writes overwrite it
   };
-  if constexpr (DYN) {
-    long t = lo + (blockIdx.x >> 3), tn = t + gx;
-    float2 nx[16];
-    if (t < hi) load(nx, t);
-    while (t < hi) {
-      body(nx, t, tn);
-      t = tn;
-      tn = s_nn;
-    }
-    if (tid == 0 && atomicAdd(head + 8 * 32, 1u) == (unsigned)gx - 1u) {
-      atomicExch(head, 0u);
-      atomicExch(head + 8 * 32, 0u);
-    }
-    return;
-  }
-  long t = blockIdx.x;
-  float2 nx[16];
-  if (t < ntile) load(nx, t);
-  for (; t < ntile; t += G) body(nx, t, t + G);
+  walk.template run<float2, 16>(load, body);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -623,15 +663,13 @@ __global__ __launch_bounds__(kThreads) void k_range_fft_r512(const float2* __res
 //   (16-B reads), takes W256^(c k1) DFT8_q and stores both bins packed (pk_pack16; planes of 512 pairs x 16 B).
 // LDS: xbuf 64 KiB (aliased by obuf) + twiddles 8 KiB: two workgroups (16 waves) per CU.
 constexpr int kR1kThreads = 512;
-constexpr int kPkPlane1k = 8 * 1024;        // bytes per plane of one S = 1024 tile (512 pairs x 16 B)
-constexpr int kPkTile1k = 6 * kPkPlane1k;   // bytes per tile
 // W1024^(j k) in ldtw.  Swizzle (j / 2) ^ (j / 32): the stage-1 reads (lane j, one k) hit 64 distinct banks per 32-lane
 // group, and the stage-2 reads of rows j = 16 h (h = lane % 4: swizzles 0, 8, 1, 9) do too; with (j / 2) alone rows
 // 0 / 32 and 16 / 48 shared banks (2-way on 15 reads per tile and wave: most of the 17.2 M conflict cycles per 100
 // configs[4] frames, gpurun_out/r5aa_ddctr5)
 RSL_DEV int r1k_tw(int j, int k) { return j * 16 + (k ^ (((j >> 1) ^ (j >> 5)) & 15)); }
 
-template <bool DYN, int DBG = 0>
+template <int DBG = 0>
 __global__ __launch_bounds__(kR1kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_range_fft_r1024(const float2* __restrict__ cube, int A, int Ct,
                                                                   int c0, int C, long ntile,
                                                                   const float2* __restrict__ table,
@@ -649,14 +687,13 @@ __global__ __launch_bounds__(kR1kThreads) __attribute__((amdgpu_waves_per_eu(4))
   long* s_nn = reinterpret_cast<long*>(&ldtw[r1k_tw(0, 0)]);
   float2* obuf = xbuf;
   const int tid = threadIdx.x;
-  const long G = gridDim.x;
   for (int k = tid; k < S; k += NT) ldtab[k] = table[k];
   for (int k = tid; k < 64 * 16; k += NT) {
     const int jj = k >> 4, kk = k & 15;
     if (kk) ldtw[r1k_tw(jj, kk)] = tw[jj * kk];  // W1024^(j k1), j k1 <= 945 (k1 = 0: never read)
   }
   auto load = [&](float2(&nx)[16], long t) {
-    t = (long)__builtin_amdgcn_readfirstlane((int)t);  // the tile index is workgroup-uniform (ntile < 2^31)
+    t = (long)__builtin_amdgcn_readfirstlane((int)t);  // the tile index is workgroup-uniform (below 2^31: k1_tiles_fit)
     int lt = tid;
     asm volatile("" : "+v"(lt));
     const int row = __builtin_amdgcn_readfirstlane(lt >> 6), j = lt & 63;  // one wave per chirp row: row is scalar
@@ -671,18 +708,14 @@ __global__ __launch_bounds__(kR1kThreads) __attribute__((amdgpu_waves_per_eu(4))
         nx[m] = ld8<true>(src + 64 * m);
     }
   };
-  const int xcd = blockIdx.x & 7;
-  const long gx = (G - xcd + 7) / 8;
-  const long lo = DYN ? xcd * ntile / 8 : 0, hi = DYN ? (xcd + 1) * ntile / 8 : ntile;
-  unsigned* head = rfq + xcd * 32;  // this XCD's dequeue head (the exit counter: + 256)
+  const TileWalk<true> walk(ntile, rfq, s_nn);
   __syncthreads();
   auto body = [&](float2(&nx)[16], long t, long tn) {
-    // workgroup-uniform tile indices (read from LDS or derived from blockIdx; ntile < 2^31, checked by the launcher):
-    // scalar, so the tile's address arithmetic runs on the SALU
+    // workgroup-uniform tile indices (read from LDS or derived from blockIdx; below 2^31: k1_tiles_fit): scalar, so the
+    // tile's address arithmetic runs on the SALU
     t = (long)__builtin_amdgcn_readfirstlane((int)t);
     tn = (long)__builtin_amdgcn_readfirstlane((int)tn);
-    unsigned claim = 0;
-    if (DYN && tid == 0) claim = atomicAdd(head, 1u);
+    const unsigned claim = walk.claim();
     const int cb = (int)(t % ncb);
     const long fa = t / ncb;
     // the thread index laundered per tile: otherwise the compiler hoists the tile-invariant table and twiddle reads
@@ -695,10 +728,10 @@ __global__ __launch_bounds__(kR1kThreads) __attribute__((amdgpu_waves_per_eu(4))
     float2 v[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) v[m] = cmul(nx[m], ldtab[j + 64 * m]);
-    load(nx, tn < hi ? tn : t);  // in flight during this tile's transforms and stores
+    load(nx, tn < walk.hi ? tn : t);  // in flight during this tile's transforms and stores
     if constexpr (DBG == 3) {
       if (v[0].x == 1.2345e30f) work[tid] = v[1];
-      if (DYN && tid == 0) *s_nn = lo + 2 * gx + (long)claim;
+      walk.publish(claim);
       __syncthreads();
       return;
     }
@@ -738,69 +771,12 @@ __global__ __launch_bounds__(kR1kThreads) __attribute__((amdgpu_waves_per_eu(4))
       ow[16 * k] = xo;
     }
     __syncthreads();
-    // thread tid holds bins 2 tid, 2 tid + 1 of the 8 rows (chirps cb + 32 q): the Doppler transform's first step,
-    // Y[k1] = W256^(cb k1) DFT8_q, here in registers (K2 starts from the 32-point step)
-    float2 y0[8], y1[8];
-    const int pos = (2 * lt) ^ (4 * ((lt >> 7) & 3));
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float4 ab = *reinterpret_cast<const float4*>(obuf + q * S + pos);
-      y0[q] = make_float2(ab.x, ab.y);
-      y1[q] = make_float2(ab.z, ab.w);
-    }
-    Dft<8>::run(y0);
-    Dft<8>::run(y1);
-    const int cbs = __builtin_amdgcn_readfirstlane(cb);  // the tile is workgroup-uniform
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-      const float2 wk = tw[4 * cbs * k];  // W256^(cb k) = W1024^(4 cb k), 4 cb k <= 868 (workgroup-uniform: scalar loads)
-      y0[k] = cmul(y0[k], wk);
-      y1[k] = cmul(y1[k], wk);
-    }
-    float f0[16], f1[16];
-    unsigned m0 = 0u, m1 = 0u;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      f0[2 * q] = y0[q].x;
-      f0[2 * q + 1] = y0[q].y;
-      f1[2 * q] = y1[q].x;
-      f1[2 * q + 1] = y1[q].y;
-      m0 = max(m0, max(__float_as_uint(y0[q].x) & 0x7FFFFFFFu, __float_as_uint(y0[q].y) & 0x7FFFFFFFu));
-      m1 = max(m1, max(__float_as_uint(y1[q].x) & 0x7FFFFFFFu, __float_as_uint(y1[q].y) & 0x7FFFFFFFu));
-    }
-    const int e0 = pk_exp(m0), e1 = pk_exp(m1);
-    uint4 w0[3], w1[3];
-    pk_pack16(f0, e0, w0);
-    pk_pack16(f1, e1, w1);
-    const size_t tile = (size_t)fa * ncb + cb;
-    uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(work) + tile * kPkTile1k) + lt;
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj) {
-      st16<true>(reinterpret_cast<float4*>(dst + jj * (kPkPlane1k / 16)), __builtin_bit_cast(float4, w0[jj]));
-      st16<true>(reinterpret_cast<float4*>(dst + (jj + 3) * (kPkPlane1k / 16)), __builtin_bit_cast(float4, w1[jj]));
-    }
-    if (DYN && tid == 0) *s_nn = lo + 2 * gx + (long)claim;
+    // thread lt holds bins 2 lt, 2 lt + 1 of the 8 rows (chirps cb + 32 q), at the output swizzle's position
+    k1_packed_store<S, true>(obuf, S, (2 * lt) ^ (4 * ((lt >> 7) & 3)), cb, tw, work, (size_t)fa * ncb + cb, lt);
+    walk.publish(claim);
     __syncthreads();  // obuf is read above; the next tile's exchange writes overwrite it
   };
-  if constexpr (DYN) {
-    long t = lo + (blockIdx.x >> 3), tn = t + gx;
-    float2 nx[16];
-    if (t < hi) load(nx, t);
-    while (t < hi) {
-      body(nx, t, tn);
-      t = tn;
-      tn = *s_nn;
-    }
-    if (tid == 0 && atomicAdd(head + 8 * 32, 1u) == (unsigned)gx - 1u) {
-      atomicExch(head, 0u);
-      atomicExch(head + 8 * 32, 0u);
-    }
-    return;
-  }
-  long t = blockIdx.x;
-  float2 nx[16];
-  if (t < ntile) load(nx, t);
-  for (; t < ntile; t += G) body(nx, t, t + G);
+  walk.template run<float2, 16>(load, body);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -815,8 +791,6 @@ __global__ __launch_bounds__(kR1kThreads) __attribute__((amdgpu_waves_per_eu(4))
 //   W64^(c k1) DFT8_q and stores both bins packed (planes of 128 pairs x 16 B).
 // LDS 20 KiB: 8 workgroups (16 waves) per CU.
 constexpr int kR256Threads = 128;
-constexpr int kPkPlane256 = 8 * 256;        // bytes per plane of one S = 256 tile (128 pairs x 16 B)
-constexpr int kPkTile256 = 6 * kPkPlane256;
 RSL_DEV int r256_tw(int j, int k) { return j * 16 + (k ^ j); }  // W256^(j k) in ldtw
 
 template <int DBG = 0>
@@ -835,14 +809,13 @@ __global__ __launch_bounds__(kR256Threads) void k_range_fft_r256(const float2* _
   __shared__ long s_nn;
   float2* obuf = xbuf;
   const int tid = threadIdx.x;
-  const long G = gridDim.x;
   for (int k = tid; k < S; k += NT) ldtab[k] = table[k];
   for (int k = tid; k < 16 * 16; k += NT) {
     const int jj = k >> 4, kk = k & 15;
     ldtw[r256_tw(jj, kk)] = tw[jj * kk];  // W256^(j k1), j k1 <= 225
   }
   auto load = [&](float2(&nx)[16], long t) {
-    t = (long)__builtin_amdgcn_readfirstlane((int)t);  // the tile index is workgroup-uniform (ntile < 2^31)
+    t = (long)__builtin_amdgcn_readfirstlane((int)t);  // the tile index is workgroup-uniform (below 2^31: k1_tiles_fit)
     int lt = tid;
     asm volatile("" : "+v"(lt));
     const int row = lt >> 4, j = lt & 15;
@@ -857,18 +830,14 @@ __global__ __launch_bounds__(kR256Threads) void k_range_fft_r256(const float2* _
         nx[m] = ld8<true>(src + 16 * m);
     }
   };
-  const int xcd = blockIdx.x & 7;
-  const long gx = (G - xcd + 7) / 8;
-  const long lo = xcd * ntile / 8, hi = (xcd + 1) * ntile / 8;
-  unsigned* head = rfq + xcd * 32;  // this XCD's dequeue head (the exit counter: + 256)
+  const TileWalk<true> walk(ntile, rfq, &s_nn);
   __syncthreads();
   auto body = [&](float2(&nx)[16], long t, long tn) {
-    // workgroup-uniform tile indices (read from LDS or derived from blockIdx; ntile < 2^31, checked by the launcher):
-    // scalar, so the tile's address arithmetic runs on the SALU
+    // workgroup-uniform tile indices (read from LDS or derived from blockIdx; below 2^31: k1_tiles_fit): scalar, so the
+    // tile's address arithmetic runs on the SALU
     t = (long)__builtin_amdgcn_readfirstlane((int)t);
     tn = (long)__builtin_amdgcn_readfirstlane((int)tn);
-    unsigned claim = 0;
-    if (tid == 0) claim = atomicAdd(head, 1u);
+    const unsigned claim = walk.claim();
     const int cb = (int)(t % ncb);
     const long fa = t / ncb;
     int lt = tid;  // laundered per tile: keeps the tile-invariant table reads inside the tile loop
@@ -877,7 +846,7 @@ __global__ __launch_bounds__(kR256Threads) void k_range_fft_r256(const float2* _
     float2 v[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) v[m] = cmul(nx[m], ldtab[j + 16 * m]);
-    load(nx, tn < hi ? tn : t);  // in flight during this tile's transforms and stores
+    load(nx, tn < walk.hi ? tn : t);  // in flight during this tile's transforms and stores
     Dft<16>::run(v);
 #pragma unroll
     for (int k = 1; k < 16; ++k) v[k] = cmul(v[k], ldtw[r256_tw(j, k)]);
@@ -897,60 +866,12 @@ __global__ __launch_bounds__(kR256Threads) void k_range_fft_r256(const float2* _
 #pragma unroll
     for (int k = 0; k < 16; ++k) ow[16 * k] = v[k];
     __syncthreads();
-    // thread lt holds bins 2 lt, 2 lt + 1 of the 8 rows (chirps cb + 8 q): Y[k1] = W64^(cb k1) DFT8_q
-    float2 y0[8], y1[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float4 ab = *reinterpret_cast<const float4*>(obuf + q * S + 2 * lt);
-      y0[q] = make_float2(ab.x, ab.y);
-      y1[q] = make_float2(ab.z, ab.w);
-    }
-    Dft<8>::run(y0);
-    Dft<8>::run(y1);
-    const int cbs = __builtin_amdgcn_readfirstlane(cb);  // the tile is workgroup-uniform
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-      const float2 wk = tw[4 * cbs * k];  // W64^(cb k) = W256^(4 cb k), 4 cb k <= 196 (workgroup-uniform: scalar loads)
-      y0[k] = cmul(y0[k], wk);
-      y1[k] = cmul(y1[k], wk);
-    }
-    float f0[16], f1[16];
-    unsigned m0 = 0u, m1 = 0u;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      f0[2 * q] = y0[q].x;
-      f0[2 * q + 1] = y0[q].y;
-      f1[2 * q] = y1[q].x;
-      f1[2 * q + 1] = y1[q].y;
-      m0 = max(m0, max(__float_as_uint(y0[q].x) & 0x7FFFFFFFu, __float_as_uint(y0[q].y) & 0x7FFFFFFFu));
-      m1 = max(m1, max(__float_as_uint(y1[q].x) & 0x7FFFFFFFu, __float_as_uint(y1[q].y) & 0x7FFFFFFFu));
-    }
-    const int e0 = pk_exp(m0), e1 = pk_exp(m1);
-    uint4 w0[3], w1[3];
-    pk_pack16(f0, e0, w0);
-    pk_pack16(f1, e1, w1);
-    const size_t tile = (size_t)fa * ncb + cb;
-    uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(work) + tile * kPkTile256) + lt;
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj) {
-      st16<true>(reinterpret_cast<float4*>(dst + jj * (kPkPlane256 / 16)), __builtin_bit_cast(float4, w0[jj]));
-      st16<true>(reinterpret_cast<float4*>(dst + (jj + 3) * (kPkPlane256 / 16)), __builtin_bit_cast(float4, w1[jj]));
-    }
-    if (tid == 0) s_nn = lo + 2 * gx + (long)claim;
+    // thread lt holds bins 2 lt, 2 lt + 1 of the 8 rows (chirps cb + 8 q)
+    k1_packed_store<S, true>(obuf, S, 2 * lt, cb, tw, work, (size_t)fa * ncb + cb, lt);
+    walk.publish(claim);
     __syncthreads();  // obuf is read above; the next tile's exchange writes overwrite it
   };
-  long t = lo + (blockIdx.x >> 3), tn = t + gx;
-  float2 nx[16];
-  if (t < hi) load(nx, t);
-  while (t < hi) {
-    body(nx, t, tn);
-    t = tn;
-    tn = s_nn;
-  }
-  if (tid == 0 && atomicAdd(head + 8 * 32, 1u) == (unsigned)gx - 1u) {
-    atomicExch(head, 0u);
-    atomicExch(head + 8 * 32, 0u);
-  }
+  walk.template run<float2, 16>(load, body);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1359,18 +1280,6 @@ __global__ __launch_bounds__(256) void k_doppler_detect_r128(const float2* __res
   const int tid = threadIdx.x;
   constexpr unsigned nkb = (unsigned)(S / KB);
   const unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)xcd_tile(blockIdx.x, gridDim.x));
-  const unsigned char* wb = reinterpret_cast<const unsigned char*>(work);
-  auto unit = [&](size_t tile0, int k, int cls, uint4(&w)[3]) {
-    const uint4* src =
-        reinterpret_cast<const uint4*>(wb + (tile0 + cls) * kPkTile + (size_t)(3 * (k & 1)) * kPkPlane) + (k >> 1);
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj) {
-      if constexpr (DBG == 6)
-        w[jj] = make_uint4(0x4B4000u + tid, 0x5Au * jj, 0x4B40u + k, 0x12345u);
-      else
-        w[jj] = src[jj * (kPkPlane / 16)];
-    }
-  };
   const int b = tid % KB, cls = tid / KB;
   const bool halo = tid < 2 * NCB;  // threads 0-31: (side, class) = (tid / 16, tid % 16)
   const int hside = tid >> 4, hcls = tid & 15;
@@ -1379,12 +1288,8 @@ __global__ __launch_bounds__(256) void k_doppler_detect_r128(const float2* __res
   const size_t tile0 = (size_t)fa * NCB;
   // every load issued before the first LDS write
   uint4 wi[3], wh[3];
-  unit(tile0, k0 + b, cls, wi);
-  if (halo) {
-    int kk = hside ? k0 + KB : k0 - 1;  // periodic: 'reflect' is applied in the detect stage
-    kk = kk < 0 ? kk + S : (kk >= S ? kk - S : kk);
-    unit(tile0, kk, hcls, wh);
-  }
+  pk_load_unit<S, DBG>(work, tile0, k0 + b, cls, wi);
+  if (halo) pk_load_unit<S, DBG>(work, tile0, dd_halo_bin(k0, KB, hside, S), hcls, wh);
   if constexpr (DBG == 7) {
     if (__uint_as_float(wi[0].x ^ wh[1].y) == 1.2345e30f) rds[tid] = make_float2((float)wi[1].z, 0.f);
     return;
@@ -1419,7 +1324,7 @@ __global__ __launch_bounds__(256) void k_doppler_detect_r128(const float2* __res
     for (int k2 = 0; k2 < 16; ++k2) row[k1 + 8 * k2] = x[k2];
   }
   __syncthreads();
-  dd_tile_compute_reg<C, KB, NT, (DBG == 4 || DBG == 5 || DBG == 8 || DBG == 9) ? DBG : 0, LD, false, SKL, 0, true>(
+  dd_tile_compute_reg<C, KB, NT, dd_reg_dbg(DBG), LD, false, SKL, 0, true>(
       buf, reinterpret_cast<float*>(buf + NR * LD), S, k0, fa, rds, thr_f, i_lo, i_hi, mask, row_count, dbmap, pk_pow);
 }
 
@@ -1464,18 +1369,6 @@ __global__ __launch_bounds__(512) void k_doppler_detect_r256(const float2* __res
   const int tid = threadIdx.x;
   constexpr unsigned nkb = (unsigned)(S / KB);
   const unsigned tile = (unsigned)xcd_tile(blockIdx.x, gridDim.x);
-  const unsigned char* wb = reinterpret_cast<const unsigned char*>(work);
-  auto unit = [&](size_t tile0, int k, int cls, uint4(&w)[3]) {
-    const uint4* src = reinterpret_cast<const uint4*>(wb + (tile0 + cls) * kPkTile1k +
-                                                      (size_t)(3 * (k & 1)) * kPkPlane1k) + (k >> 1);
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj) {
-      if constexpr (DBG == 6)
-        w[jj] = make_uint4(0x4B4000u + tid, 0x5Au * jj, 0x4B40u + k, 0x12345u);
-      else
-        w[jj] = src[jj * (kPkPlane1k / 16)];
-    }
-  };
   const int b = tid % KB, cls = tid / KB;
   const bool halo = tid < 2 * NCB;  // threads 0-63: (side, class) = (tid / 32, tid % 32)
   const int hside = tid >> 5, hcls = tid & 31;
@@ -1483,12 +1376,8 @@ __global__ __launch_bounds__(512) void k_doppler_detect_r256(const float2* __res
   const unsigned fa = tile / nkb;
   const size_t tile0 = (size_t)fa * NCB;
   uint4 wi[3], wh[3] = {};
-  unit(tile0, k0 + b, cls, wi);
-  if (halo) {
-    int kk = hside ? k0 + KB : k0 - 1;  // periodic: 'reflect' is applied in the detect stage
-    kk = kk < 0 ? kk + S : (kk >= S ? kk - S : kk);
-    unit(tile0, kk, hcls, wh);
-  }
+  pk_load_unit<S, DBG>(work, tile0, k0 + b, cls, wi);
+  if (halo) pk_load_unit<S, DBG>(work, tile0, dd_halo_bin(k0, KB, hside, S), hcls, wh);
   if constexpr (DBG == 7) {
     if (__uint_as_float(wi[0].x ^ wh[1].y) == 1.2345e30f) rds[tid] = make_float2((float)wi[1].z, 0.f);
     return;
@@ -1552,7 +1441,7 @@ __global__ __launch_bounds__(512) void k_doppler_detect_r256(const float2* __res
     }
   }
   __syncthreads();
-  dd_tile_compute_reg<C, KB, NT, (DBG == 4 || DBG == 5 || DBG == 8 || DBG == 9) ? DBG : 0, LD, false, SKL, HSH>(
+  dd_tile_compute_reg<C, KB, NT, dd_reg_dbg(DBG), LD, false, SKL, HSH>(
       buf, reinterpret_cast<float*>(buf + NR * LD + kR256Gap), S, k0, fa, rds, thr_f, i_lo, i_hi, mask, row_count, dbmap, pk_pow);
 }
 
@@ -1584,18 +1473,6 @@ __global__ __launch_bounds__(256) void k_doppler_detect_r64(const float2* __rest
   const int tid = threadIdx.x;
   constexpr unsigned nkb = (unsigned)(S / KB);
   const unsigned tile = (unsigned)xcd_tile(blockIdx.x, gridDim.x);
-  const unsigned char* wb = reinterpret_cast<const unsigned char*>(work);
-  auto unit = [&](size_t tile0, int k, int cls, uint4(&w)[3]) {
-    const uint4* src = reinterpret_cast<const uint4*>(wb + (tile0 + cls) * kPkTile256 +
-                                                      (size_t)(3 * (k & 1)) * kPkPlane256) + (k >> 1);
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj) {
-      if constexpr (DBG == 6)
-        w[jj] = make_uint4(0x4B4000u + tid, 0x5Au * jj, 0x4B40u + k, 0x12345u);
-      else
-        w[jj] = src[jj * (kPkPlane256 / 16)];
-    }
-  };
   const int b = tid % KB, cls = tid / KB;
   const bool halo = (tid & 15) == 0;  // 16 halo units, one per 16 threads: (side, class) = (h / 8, h % 8), h = tid / 16
   const int hside = tid >> 7, hcls = (tid >> 4) & 7;
@@ -1603,12 +1480,8 @@ __global__ __launch_bounds__(256) void k_doppler_detect_r64(const float2* __rest
   const unsigned fa = tile / nkb;
   const size_t tile0 = (size_t)fa * NCB;
   uint4 wi[3], wh[3] = {};
-  unit(tile0, k0 + b, cls, wi);
-  if (halo) {
-    int kk = hside ? k0 + KB : k0 - 1;  // periodic: 'reflect' is applied in the detect stage
-    kk = kk < 0 ? kk + S : (kk >= S ? kk - S : kk);
-    unit(tile0, kk, hcls, wh);
-  }
+  pk_load_unit<S, DBG>(work, tile0, k0 + b, cls, wi);
+  if (halo) pk_load_unit<S, DBG>(work, tile0, dd_halo_bin(k0, KB, hside, S), hcls, wh);
   {
     float f[16];
     pk_unpack16(wi, f);
@@ -1650,52 +1523,123 @@ __global__ __launch_bounds__(256) void k_doppler_detect_r64(const float2* __rest
     for (int k2 = 0; k2 < 8; ++k2) rw[8 * k2] = y[k2];
   }
   __syncthreads();
-  dd_tile_compute_reg<C, KB, NT, (DBG == 4 || DBG == 5 || DBG == 8 || DBG == 9) ? DBG : 0, LD, false>(
+  dd_tile_compute_reg<C, KB, NT, dd_reg_dbg(DBG), LD, false>(
       buf, reinterpret_cast<float*>(buf + NR * LD), S, k0, fa, rds, thr_f, i_lo, i_hi, mask, row_count, dbmap, pk_pow);
 }
 
-static hipError_t launch_k2d_r64(hipStream_t st, const float2* work, int F, int A, int S, float2* rds, double thr_p,
-                                 int i_lo, int i_hi, unsigned long long* mask, int* row_count, float* dbmap,
-                                 float* pk_pow, int* pk_group, const unsigned char* wexp) {
-  constexpr int C = 64, KB = 32, NT = 256;
-  static_assert(dd_reg_ok<C, KB, NT>(), "register tile body shape");
-  if (S != 256) return hipErrorInvalidValue;  // the kernel's tile math is compiled for S = 256
-  const long ntile = (long)F * A * (S / KB);
-  const size_t lds = sizeof(float2) * (size_t)(KB + 2) * (C + 1) + (size_t)KB * (C / 64) * 16;
-  auto kern = k_doppler_detect_r64<>;
+// An integer knob of the development build (make dev): 0 when unset, and always 0 in the product build.
+static int dev_knob(const char* name) {
 #ifdef RSL_DEV_KNOBS
-  if (const char* e = getenv("RSL_DD_DBG")) {  // ablation variants (development builds only; results are wrong)
-    const int v = atoi(e);
-    if (v == 6) kern = k_doppler_detect_r64<6>;
-    if (v == 8) kern = k_doppler_detect_r64<8>;
-  }
+  if (const char* e = getenv(name)) return atoi(e);
 #endif
-  *pk_group = KB;
-  hipLaunchKernelGGL(kern, dim3((unsigned)ntile), dim3(NT), lds, st, work, S, nullptr, rds, threshold_as_float(thr_p),
-                     i_lo, i_hi, mask, row_count, dbmap, pk_pow, wexp);
-  return hipGetLastError();
+  (void)name;
+  return 0;
 }
 
-static hipError_t launch_k2d_r256(hipStream_t st, const float2* work, int F, int A, int S, float2* rds, double thr_p,
-                                  int i_lo, int i_hi, unsigned long long* mask, int* row_count, float* dbmap,
-                                  float* pk_pow, int* pk_group, const unsigned char* wexp) {
-  constexpr int C = 256, KB = 16, NT = 512;
-  static_assert(dd_reg_ok<C, KB, NT>(), "register tile body shape");
-  if (S != 1024) return hipErrorInvalidValue;  // the kernel's tile math is compiled for S = 1024
-  const long ntile = (long)F * A * (S / KB);
-  const size_t lds = sizeof(float2) * ((size_t)(KB + 2) * kR256Pitch + kR256Gap) + (size_t)KB * (C / 64) * 16;
-  auto kern = k_doppler_detect_r256<>;
+// The packed shapes (work_packed_supported), by C: S = 4 C samples; K1 tiles of one chirp class (8 chirps, C / 8 classes
+// per (frame, antenna)) on NT1 threads with static LDS only; K2 tiles of KB range bins on NT2 threads, their rows in
+// kRows2 bytes of dynamic LDS.  k1() / k2() give the kernel: the product one or, in development builds, the ablation
+// variant that RSL_RF_DBG / RSL_DD_DBG names (results are wrong) and, at C = 128, the `work` stores without the nt hint
+// of RSL_WORK_TEMPORAL=1 (MALL study).
+using K1Fn = void (*)(const float2*, int, int, int, int, long, const float2*, const float2*, int, float2*, unsigned*,
+                      unsigned char*);
+using K2Fn = void (*)(const float2*, int, const float2*, float2*, float, int, int, unsigned long long*, int*, float*,
+                      float*, const unsigned char*);
+template <int C>
+struct PackedShape;
+// cfg2.  K2: 16 range bins per tile (2.59 ms per 2000 cfg2 frames against 2.67 for 32 on 512 threads, and 3.10 for two
+// tiles per workgroup; round 3); the upper halo row is skewed inside its pitch: with the detection exchange area
+// 19,952 B of LDS, 8 workgroups per CU
+template <>
+struct PackedShape<128> {
+  static constexpr int NT1 = kThreads, KB = 16, NT2 = 256;
+  static constexpr size_t kRows2 = sizeof(float2) * (KB + 2) * kR128Pitch;
+  static K1Fn k1() {
 #ifdef RSL_DEV_KNOBS
-  if (const char* e = getenv("RSL_DD_DBG")) {  // ablation variants (development builds only; results are wrong)
-    const int v = atoi(e);
-    if (v == 6) kern = k_doppler_detect_r256<6>;
-    if (v == 7) kern = k_doppler_detect_r256<7>;
-    if (v == 8) kern = k_doppler_detect_r256<8>;
-  }
+    switch (dev_knob("RSL_RF_DBG")) {
+      case 2: return k_range_fft_r512<2>;
+      case 3: return k_range_fft_r512<3>;
+    }
+    if (dev_knob("RSL_WORK_TEMPORAL") == 1) return k_range_fft_r512<0, false>;
 #endif
-  *pk_group = KB;
-  hipLaunchKernelGGL(kern, dim3((unsigned)ntile), dim3(NT), lds, st, work, S, nullptr, rds, threshold_as_float(thr_p),
-                     i_lo, i_hi, mask, row_count, dbmap, pk_pow, wexp);
+    return k_range_fft_r512<>;
+  }
+  static K2Fn k2() {
+#ifdef RSL_DEV_KNOBS
+    switch (dev_knob("RSL_DD_DBG")) {
+      case 4: return k_doppler_detect_r128<4>;
+      case 5: return k_doppler_detect_r128<5>;
+      case 6: return k_doppler_detect_r128<6>;
+      case 7: return k_doppler_detect_r128<7>;
+      case 8: return k_doppler_detect_r128<8>;
+      case 9: return k_doppler_detect_r128<9>;
+    }
+#endif
+    return k_doppler_detect_r128<>;
+  }
+};
+// configs[4]
+template <>
+struct PackedShape<256> {
+  static constexpr int NT1 = kR1kThreads, KB = 16, NT2 = 512;
+  static constexpr size_t kRows2 = sizeof(float2) * ((KB + 2) * kR256Pitch + kR256Gap);
+  static K1Fn k1() {
+#ifdef RSL_DEV_KNOBS
+    switch (dev_knob("RSL_RF_DBG")) {
+      case 2: return k_range_fft_r1024<2>;
+      case 3: return k_range_fft_r1024<3>;
+    }
+#endif
+    return k_range_fft_r1024<>;
+  }
+  static K2Fn k2() {
+#ifdef RSL_DEV_KNOBS
+    switch (dev_knob("RSL_DD_DBG")) {
+      case 6: return k_doppler_detect_r256<6>;
+      case 7: return k_doppler_detect_r256<7>;
+      case 8: return k_doppler_detect_r256<8>;
+    }
+#endif
+    return k_doppler_detect_r256<>;
+  }
+};
+// cfg1
+template <>
+struct PackedShape<64> {
+  static constexpr int NT1 = kR256Threads, KB = 32, NT2 = 256;
+  static constexpr size_t kRows2 = sizeof(float2) * (KB + 2) * (64 + 1);
+  static K1Fn k1() {
+#ifdef RSL_DEV_KNOBS
+    if (dev_knob("RSL_RF_DBG") == 2) return k_range_fft_r256<2>;
+#endif
+    return k_range_fft_r256<>;
+  }
+  static K2Fn k2() {
+#ifdef RSL_DEV_KNOBS
+    switch (dev_knob("RSL_DD_DBG")) {
+      case 6: return k_doppler_detect_r64<6>;
+      case 8: return k_doppler_detect_r64<8>;
+    }
+#endif
+    return k_doppler_detect_r64<>;
+  }
+};
+
+// K2 + K3 on packed work: one workgroup per tile of KB range bins.
+template <int C>
+static hipError_t launch_k2d_packed(hipStream_t st, const float2* work, int F, int A, int S, float2* rds, double thr_p,
+                                    int i_lo, int i_hi, unsigned long long* mask, int* row_count, float* dbmap,
+                                    float* pk_pow, int* pk_group, const unsigned char* wexp) {
+  using P = PackedShape<C>;
+  static_assert(dd_reg_ok<C, P::KB, P::NT2>(), "register tile body shape");
+  if (S != 4 * C) return hipErrorInvalidValue;  // the kernel's tile math is compiled for its S
+  const long ntile = (long)F * A * (S / P::KB);
+  // the tile rows + the register body's exchange area (edge columns and ballots: 16 B per row per 64 columns)
+  const size_t lds = P::kRows2 + (size_t)P::KB * (C / 64) * 16;
+  const K2Fn kern = P::k2();
+  *pk_group = P::KB;  // tile-compact peak powers (dd_tile_compute_reg)
+  hipLaunchKernelGGL(kern, dim3((unsigned)ntile), dim3(P::NT2), lds, st, work, S, nullptr, rds,
+                     threshold_as_float(thr_p), i_lo, i_hi, mask, row_count, dbmap, pk_pow, wexp);
   return hipGetLastError();
 }
 
@@ -1741,53 +1685,14 @@ static int dd_kb(int C, int S) {
   return kb;
 }
 
-// K2 + K3 on packed work (work_packed_supported: C = 128, S = 512), k_doppler_detect_r128 (16 range bins per tile:
-// 2.59 ms per 2000 cfg2 frames against 2.67 for 32 on 512 threads, and 3.10 for two tiles per workgroup; round 3).
-static hipError_t launch_k2d_r128(hipStream_t st, const float2* work, int F, int A, int S, float2* rds, double thr_p,
-                                  int i_lo, int i_hi, unsigned long long* mask, int* row_count, float* dbmap,
-                                  float* pk_pow, int* pk_group, const unsigned char* wexp) {
-  constexpr int C = 128, KR = 16, NT = 16 * KR;
-  static_assert(dd_reg_ok<C, KR, NT>(), "register tile body shape");
-  if (S != 512) return hipErrorInvalidValue;  // the kernel's tile math is compiled for S = 512 (work_packed_supported)
-  const long ntile = (long)F * A * (S / KR);
-  // the tile rows (the upper halo row skewed inside its pitch) + the register body's exchange area (edge columns and
-  // ballots: 16 B per row per 64 columns): 19,952 B, 8 workgroups per CU
-  const size_t lds = sizeof(float2) * (size_t)(KR + 2) * kR128Pitch + (size_t)KR * (C / 64) * 16;
-  const float thr_f = threshold_as_float(thr_p);
-  auto kern = k_doppler_detect_r128<>;
-#ifdef RSL_DEV_KNOBS
-  if (const char* e = getenv("RSL_DD_DBG")) {  // ablation variants (development builds only; results are wrong)
-    const int v = atoi(e);
-    if (v == 4) kern = k_doppler_detect_r128<4>;
-    if (v == 5) kern = k_doppler_detect_r128<5>;
-    if (v == 6) kern = k_doppler_detect_r128<6>;
-    if (v == 7) kern = k_doppler_detect_r128<7>;
-    if (v == 8) kern = k_doppler_detect_r128<8>;
-    if (v == 9) kern = k_doppler_detect_r128<9>;
-  }
-#endif
-  *pk_group = KR;  // tile-compact peak powers (dd_tile_compute_reg)
-  hipLaunchKernelGGL(kern, dim3((unsigned)ntile), dim3(NT), lds, st, work, S, nullptr, rds, thr_f, i_lo, i_hi, mask,
-                     row_count, dbmap, pk_pow, wexp);
-  return hipGetLastError();
-}
-
-
 template <int C>
 static hipError_t launch_k2d(hipStream_t st, const float2* work, int F, int A, int S, const float2* tw, float2* rds,
                              double thr_p, int i_lo, int i_hi, unsigned long long* mask, int* row_count, float* dbmap,
                              float* pk_pow, int* pk_group, const unsigned char* wexp) {
-  if constexpr (C == 128) {
+  if constexpr (C == 64 || C == 128 || C == 256) {
     if (wexp)
-      return launch_k2d_r128(st, work, F, A, S, rds, thr_p, i_lo, i_hi, mask, row_count, dbmap, pk_pow, pk_group, wexp);
-  }
-  if constexpr (C == 256) {
-    if (wexp)
-      return launch_k2d_r256(st, work, F, A, S, rds, thr_p, i_lo, i_hi, mask, row_count, dbmap, pk_pow, pk_group, wexp);
-  }
-  if constexpr (C == 64) {
-    if (wexp)
-      return launch_k2d_r64(st, work, F, A, S, rds, thr_p, i_lo, i_hi, mask, row_count, dbmap, pk_pow, pk_group, wexp);
+      return launch_k2d_packed<C>(st, work, F, A, S, rds, thr_p, i_lo, i_hi, mask, row_count, dbmap, pk_pow, pk_group,
+                                  wexp);
   }
   constexpr int K0 = rows_for(C);
   constexpr int K1 = (2048 / C) < 1 ? 1 : (2048 / C) > K0 ? K0 : (2048 / C);
@@ -1798,51 +1703,46 @@ static hipError_t launch_k2d(hipStream_t st, const float2* work, int F, int A, i
                               wexp);
 }
 
-// K1 at S = 1024 on packed work (work_packed_supported): k_range_fft_r1024, one tile per (frame, antenna, class).
-static hipError_t launch_k1_r1024(hipStream_t st, const float2* cube, int F, int A, int Ct, int c0, int C,
-                                  const float2* table, const float2* tw, int dc, float2* work, unsigned char* wexp,
-                                  RfQueues* qs) {
-  if (C != 256) return hipErrorInvalidValue;  // its chirp-class tiles are compiled for C = 256
-  const long ntile = (long)F * A * 32;
-  if (ntile >= (1L << 31)) return hipErrorInvalidValue;  // the kernel's tile indices are 32-bit (readfirstlane)
-  auto kern = k_range_fft_r1024<true>;
-#ifdef RSL_DEV_KNOBS
-  if (const char* e = getenv("RSL_RF_DBG")) {  // ablation (development builds only; results are wrong)
-    const int v = atoi(e);
-    if (v == 2) kern = k_range_fft_r1024<true, 2>;
-    if (v == 3) kern = k_range_fft_r1024<true, 3>;
+// K1's grid: the resident workgroups; RSL_K1_WG_PER_CU (development builds) caps them per CU (room for the other
+// stream).
+static long k1_grid(const void* kern, size_t lds, long ntile, int nt) {
+  long nblk = resident_grid(kern, lds, ntile, nt);
+  if (const int per_cu = dev_knob("RSL_K1_WG_PER_CU")) {
+    int dev = 0, ncu = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const long cap = (long)per_cu * ncu;
+    if (cap >= 8 && cap < nblk) nblk = cap;
   }
-#endif
-  // ntile >= 32 (A >= 1, 32 classes) and every CU holds two workgroups: the grid always spans the 8 XCDs, so the
-  // per-XCD dequeue always applies (no static-walk instance)
-  const long nblk = resident_grid(reinterpret_cast<const void*>(kern), 0, ntile, kR1kThreads);
-  if (nblk < 8) return hipErrorInvalidValue;
-  unsigned* rfq = nullptr;
-  if (hipError_t qe = rf_queue(qs, st, &rfq)) return qe;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kR1kThreads), 0, st, cube, A, Ct, c0, C, ntile, table, tw, dc,
-                     work, rfq, wexp);
-  return hipGetLastError();
+  return nblk;
 }
 
-// K1 at S = 256 on packed work (work_packed_supported): k_range_fft_r256, one tile per (frame, antenna, class).
-static hipError_t launch_k1_r256(hipStream_t st, const float2* cube, int F, int A, int Ct, int c0, int C,
-                                 const float2* table, const float2* tw, int dc, float2* work, unsigned char* wexp,
-                                 RfQueues* qs) {
-  if (C != 64) return hipErrorInvalidValue;  // its chirp-class tiles are compiled for C = 64
-  const long ntile = (long)F * A * 8;
-  if (ntile >= (1L << 31)) return hipErrorInvalidValue;  // the kernel's tile indices are 32-bit (readfirstlane)
-  auto kern = k_range_fft_r256<>;
-#ifdef RSL_DEV_KNOBS
-  if (const char* e = getenv("RSL_RF_DBG"))  // ablation (development builds only; results are wrong)
-    if (atoi(e) == 2) kern = k_range_fft_r256<2>;
-#endif
-  // the per-XCD dequeue needs a workgroup on every XCD: tiny batches (F A < 1) do not occur (ntile >= 8)
-  const long nblk = resident_grid(reinterpret_cast<const void*>(kern), 0, ntile, kR256Threads);
-  if (nblk < 8) return hipErrorInvalidValue;
+// The register-form K1 bodies narrow the walk's tile indices to 32 bits (readfirstlane), the hand-off they read back
+// included.  The largest index a TileWalk forms is a published hand-off, lo + 2 gx + claim <= hi + 2 gx - 1 (an XCD's
+// claims stay below hi - lo), where hi <= ntile and gx <= ceil(nblk / 8): ntile + 2 ceil(nblk / 8) - 1 must be below
+// 2^31.  (ntile < 2^31 alone let a hand-off past the range wrap negative, pass `tn < hi` and be walked.)  Every K1
+// launcher holds to it, k_range_fft_p's 64-bit walk too.
+static bool k1_tiles_fit(long ntile, long nblk) { return ntile + 2 * ((nblk + 7) / 8) - 1 < (1L << 31); }
+
+// K1 on packed work: one tile per (frame, antenna, chirp class).  ntile >= 8 and every CU holds a workgroup, so the
+// grid always spans the 8 XCDs that the per-XCD dequeue needs (no static-walk instance); a grid that does not is an
+// error.
+template <int S>
+static hipError_t launch_k1_packed(hipStream_t st, const float2* cube, int F, int A, int Ct, int c0, int C,
+                                   const float2* table, const float2* tw, int dc, float2* work, unsigned char* wexp,
+                                   RfQueues* qs) {
+  using P = PackedShape<S / 4>;
+  if (C != S / 4) return hipErrorInvalidValue;  // its chirp-class tiles are compiled for this C
+  const long ntile = (long)F * A * (C / 8);
+  const K1Fn kern = P::k1();
+  // RSL_K1_WG_PER_CU (k1_grid) acts on the S = 512 kernel only, as before the launchers were merged
+  const long nblk = S == 512 ? k1_grid(reinterpret_cast<const void*>(kern), 0, ntile, P::NT1)
+                             : resident_grid(reinterpret_cast<const void*>(kern), 0, ntile, P::NT1);
+  if (nblk < 8 || !k1_tiles_fit(ntile, nblk)) return hipErrorInvalidValue;
   unsigned* rfq = nullptr;
   if (hipError_t qe = rf_queue(qs, st, &rfq)) return qe;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kR256Threads), 0, st, cube, A, Ct, c0, C, ntile, table, tw, dc,
-                     work, rfq, wexp);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(P::NT1), 0, st, cube, A, Ct, c0, C, ntile, table, tw, dc, work,
+                     rfq, wexp);
   return hipGetLastError();
 }
 
@@ -1850,65 +1750,33 @@ template <int S>
 static hipError_t launch_k1(hipStream_t st, const float2* cube, int F, int A, int Ct, int c0, int C,
                             const float2* table, const float2* tw, int dc, float2* work, unsigned char* wexp,
                             RfQueues* qs) {
-  if constexpr (S == 1024) {
-    if (wexp) return launch_k1_r1024(st, cube, F, A, Ct, c0, C, table, tw, dc, work, wexp, qs);
-  }
-  if constexpr (S == 256) {
-    if (wexp) return launch_k1_r256(st, cube, F, A, Ct, c0, C, table, tw, dc, work, wexp, qs);
+  if constexpr (S == 256 || S == 512 || S == 1024) {
+    if (wexp) return launch_k1_packed<S>(st, cube, F, A, Ct, c0, C, table, tw, dc, work, wexp, qs);
   }
   constexpr int CB = rows_for(S);
   if constexpr (S % 2 == 0 && (CB * (S / 2)) % kThreads == 0) {
     // 8 chirp rows per tile at S = 512: 16 rows (78 KiB LDS) is faster alone (1.53 vs 1.63 ms per 1000 cfg2 frames)
     // but leaves no LDS for the previous batch's DoA blocks in the pipelined chain (153 k vs 171 k frames/s)
     const long ntile = (long)F * A * ((C + CB - 1) / CB);
-    if (ntile >= (1L << 31)) return hipErrorInvalidValue;  // 32-bit tile indices in the tile kernels (readfirstlane)
     const size_t lds = sizeof(float2) * (lp_row(S) + (size_t)CB * lp_row(S));
     auto kern = k_range_fft_p<S, CB, true>;
-    size_t lds_k = lds;
-    if constexpr (S == 512 && CB == 8) {
-      if (wexp) {  // packed work (work_packed_supported): the register-form 16 x 32 transform
-        if (C != 128) return hipErrorInvalidValue;  // its chirp-class tiles are compiled for C = 128
-        kern = k_range_fft_r512<true>;
-        lds_k = 0;  // static LDS only
-      }
-    }
 #ifdef RSL_DEV_KNOBS
-    if constexpr (S == 512 && CB == 8) {  // RSL_WORK_TEMPORAL=1: the packed `work` stored without the nt hint (MALL study)
-      if (const char* e = getenv("RSL_WORK_TEMPORAL"))
-        if (wexp && atoi(e) == 1) kern = k_range_fft_r512<true, 0, false>;
-    }
-    if (const char* e = getenv("RSL_RF_DBG")) {  // ablation (development builds only; results are wrong)
-      const int v = atoi(e);
-      if constexpr (S == 512 && CB == 8) {
-        if (wexp && v == 2) kern = k_range_fft_r512<true, 2>;
-        if (wexp && v == 3) kern = k_range_fft_r512<true, 3>;
-      }
-      if (!wexp && v == 1) kern = k_range_fft_p<S, CB, true, 1>;
-      if (!wexp && v == 2) kern = k_range_fft_p<S, CB, true, 2>;
-      if (!wexp && v == 3) kern = k_range_fft_p<S, CB, true, 3>;
+    switch (dev_knob("RSL_RF_DBG")) {  // ablation (development builds only; results are wrong)
+      case 1: kern = k_range_fft_p<S, CB, true, 1>; break;
+      case 2: kern = k_range_fft_p<S, CB, true, 2>; break;
+      case 3: kern = k_range_fft_p<S, CB, true, 3>; break;
     }
 #endif
-    long nblk = resident_grid(reinterpret_cast<const void*>(kern), lds_k, ntile);
-#ifdef RSL_DEV_KNOBS
-    if (const char* e = getenv("RSL_K1_WG_PER_CU")) {  // fewer resident K1 workgroups (room for the other stream)
-      int dev = 0, ncu = 256;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-      const long cap = (long)atoi(e) * ncu;
-      if (cap >= 8 && cap < nblk) nblk = cap;
-    }
-#endif
+    const long nblk = k1_grid(reinterpret_cast<const void*>(kern), lds, ntile, kThreads);
+    if (!k1_tiles_fit(ntile, nblk)) return hipErrorInvalidValue;
     unsigned* rfq = nullptr;
     if (nblk >= 8) {  // the per-XCD dequeue needs a workgroup on every XCD
       if (hipError_t qe = rf_queue(qs, st, &rfq)) return qe;
     } else {
-      kern = k_range_fft_p<S, CB, false>;
-      if constexpr (S == 512 && CB == 8) {
-        if (wexp) kern = k_range_fft_r512<false, 0, false>;  // fewer than 8 workgroups: a tiny batch
-      }
+      kern = k_range_fft_p<S, CB, false>;  // fewer than 8 workgroups: a tiny batch
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kThreads), lds_k, st, cube, A, Ct, c0, C, ntile, table, tw,
-                       dc, work, rfq, wexp);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kThreads), lds, st, cube, A, Ct, c0, C, ntile, table, tw, dc,
+                       work, rfq, wexp);
     return hipGetLastError();
   }
   const long nblk = (long)F * A * ((C + CB - 1) / CB);
@@ -2017,10 +1885,7 @@ hipError_t launch_doppler_dft(hipStream_t st, const float2* work, int F, int A, 
 // (k_range_fft_r256, k_doppler_detect_r64).  Development builds:
 // RSL_WORK_C64=1 keeps c64 rows (A/B).
 bool work_packed_supported(int C, int S) {
-#ifdef RSL_DEV_KNOBS
-  if (const char* e = getenv("RSL_WORK_C64"))
-    if (atoi(e) != 0) return false;
-#endif
+  if (dev_knob("RSL_WORK_C64") != 0) return false;
   return ((S == 512 && C == 128) || (S == 1024 && C == 256) || (S == 256 && C == 64)) &&
          doppler_detect_supported(C, S);
 }

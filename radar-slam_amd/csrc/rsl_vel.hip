@@ -10,21 +10,9 @@
 // antenna mask of a deduplicated cell) so duplicate per-antenna detections count as in the reference.
 #include "rsl_common.h"
 #include "rsl_internal.h"
+#include "rsl_vel_common.h"
 
 namespace rsl {
-
-__device__ double block_sum(double v, double* sh) {
-  const int t = threadIdx.x;
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  __syncthreads();
-  if ((t & 63) == 0) sh[t >> 6] = v;
-  __syncthreads();
-  double r = 0.0;
-  if (t == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += sh[w];
-  __syncthreads();
-  return r;  // valid on thread 0
-}
 
 __device__ double block_max(double v, double* sh) {
   const int t = threadIdx.x;
@@ -37,35 +25,6 @@ __device__ double block_max(double v, double* sh) {
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r = fmax(r, sh[w]);
   __syncthreads();
   return r;
-}
-
-__device__ double qcost(double vx, double vy, double k, double ridge, const double* m) {
-  // m: [n, cc, cs, ss, cy, sy, yy]
-  const double kx = k * vx, ky = k * vy;
-  return m[6] - 2.0 * (kx * m[4] + ky * m[5]) + kx * kx * m[1] + 2.0 * kx * ky * m[2] + ky * ky * m[3] +
-         ridge * (vx * vx + vy * vy);
-}
-
-constexpr int kVelU = 8;
-
-// kVelU cells i0 + u * blockDim.x (u < kVelU) of one thread; cells at or past e read as weight 0, grid index 0
-RSL_DEV void vel_load(long long i0, long long e, const int* __restrict__ gidx, const double* __restrict__ y,
-                      const unsigned* __restrict__ amask, int (&gv)[kVelU], double (&yv)[kVelU],
-                      unsigned (&mv)[kVelU]) {
-#pragma unroll
-  for (int u = 0; u < kVelU; ++u) {
-    const long long i = i0 + (long long)u * blockDim.x;
-    const bool ok = i < e;
-    const long long ii = ok ? i : i0;  // i0 < e: always a valid address
-    gv[u] = gidx[ii];
-    yv[u] = y[ii];
-    mv[u] = amask ? amask[ii] : 1u;
-    if (!ok) {
-      gv[u] = 0;
-      yv[u] = 0.0;
-      mv[u] = 0u;
-    }
-  }
 }
 
 // Order-preserving key of a finite or infinite double (NaN never enters): min / max of keys = min / max of values.
@@ -130,7 +89,7 @@ __global__ __launch_bounds__(512) void k_velocity(const double* __restrict__ az,
       int gv[kVelU];
       double yv[kVelU];
       unsigned mv[kVelU];
-      vel_load(i0, e, gidx, y, amask, gv, yv, mv);
+      vel_load(i0, e, blockDim.x, gidx, y, amask, gv, yv, mv);
 #pragma unroll
       for (int u = 0; u < kVelU; ++u) {
         acc1((double)__popc(mv[u]), cs_tab[gv[u]], cs_tab[G + gv[u]], yv[u]);
@@ -149,47 +108,15 @@ __global__ __launch_bounds__(512) void k_velocity(const double* __restrict__ az,
     }
   }
   const double vals[7] = {n, cc, cs, ss, cy, sy, yy};
-  for (int v = 0; v < 7; ++v) {
-    const double r = block_sum(vals[v], sh);
-    if (threadIdx.x == 0) mom[v] = r;
-  }
+  block_sum7(vals, sh, mom);
   if (threadIdx.x == 0) {
-    const double* m = mom;
-    const double H00 = k * k * m[1] + ridge, H01 = k * k * m[2], H11 = k * k * m[3] + ridge;
-    const double b0 = k * m[4], b1 = k * m[5];
-    const double det = H00 * H11 - H01 * H01;
-    double bx = 0.0, by = 0.0;
-    bool done = false;
-    if (det > 1e-300) {
-      const double vx = (H11 * b0 - H01 * b1) / det, vy = (H00 * b1 - H01 * b0) / det;
-      if (vx >= lx && vx <= hx && vy >= ly && vy <= hy) {
-        bx = vx;
-        by = vy;
-        done = true;
-      }
-    }
-    if (!done) {
-      double bc = INFINITY;
-      for (int edge = 0; edge < 4; ++edge) {
-        const int fix = edge >> 1;  // 0: vx fixed, 1: vy fixed
-        const double val = (fix == 0) ? ((edge & 1) ? hx : lx) : ((edge & 1) ? hy : ly);
-        double x;
-        if (fix == 0) {
-          x = H11 > 0 ? (b1 - H01 * val) / H11 : 0.0;
-          x = fmin(fmax(x, ly), hy);
-        } else {
-          x = H00 > 0 ? (b0 - H01 * val) / H00 : 0.0;
-          x = fmin(fmax(x, lx), hx);
-        }
-        const double vx = fix == 0 ? val : x, vy = fix == 0 ? x : val;
-        const double cst = qcost(vx, vy, k, ridge, m);
-        if (cst < bc) {
-          bc = cst;
-          bx = vx;
-          by = vy;
-        }
-      }
-    }
+    // the moments in registers, read once for the solve and the residual form below: which product the compiler fuses
+    // into each fma of that form (the last bit of the cost) follows the order of these reads
+    double m[7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) m[q] = mom[q];
+    const double2 bv = box_solve(m, k, ridge, lx, hx, ly, hy);
+    const double bx = bv.x, by = bv.y;
     sol[0] = bx;
     sol[1] = by;
     // residual sum of squares from the moments, kept when its terms do not cancel (gidx path only)
@@ -216,7 +143,7 @@ __global__ __launch_bounds__(512) void k_velocity(const double* __restrict__ az,
         int gv[kVelU];
         double yv[kVelU];
         unsigned mv[kVelU];
-        vel_load(i0, e, gidx, y, amask, gv, yv, mv);
+        vel_load(i0, e, blockDim.x, gidx, y, amask, gv, yv, mv);
 #pragma unroll
         for (int u = 0; u < kVelU; ++u)
           if (i0 + (long long)u * blockDim.x < e)
@@ -237,7 +164,7 @@ __global__ __launch_bounds__(512) void k_velocity(const double* __restrict__ az,
       acc2(i, amask ? (double)__popc(amask[i]) : 1.0, c, s, y[i]);
     }
   }
-  const double R2s = block_sum(r2, sh);
+  const double R2s = block_sum(r2, sh, (int)(blockDim.x >> 6));
   const double R2 = r2m >= 0.0 ? r2m : R2s;
   const double RM = block_max(rmax, sh);
   if (threadIdx.x == 0) {

@@ -1,0 +1,105 @@
+// rsl_vel_common.h — what the velocity solvers share (k_velocity in rsl_vel.hip, k_velocity_robust in
+// rsl_vel_robust.hip): the cell loader, the workgroup sums, the quadratic cost and the 2x2 box solve.  The robust
+// solver starts from k_velocity's solution; both take it from these functions, in the same order of operations.
+#pragma once
+#include "rsl_common.h"
+
+namespace rsl {
+
+// Sum of v over the workgroup's nw waves: wave shuffle tree, then the waves in order on thread 0.  sh: 8 doubles of LDS.
+RSL_DEV double block_sum(double v, double* sh, int nw) {
+  const int t = threadIdx.x;
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+  __syncthreads();
+  if ((t & 63) == 0) sh[t >> 6] = v;
+  __syncthreads();
+  double r = 0.0;
+  if (t == 0)
+    for (int w = 0; w < nw; ++w) r += sh[w];
+  __syncthreads();
+  return r;  // valid on thread 0
+}
+
+// The 7 moment sums [n, cc, cs, ss, cy, sy, yy] of a pass into mom, each a block_sum.  mom is written by thread 0:
+// a barrier comes before any other thread reads it.  (k_velocity_robust adds in the same order in one pass over 56
+// doubles of LDS: rv_reduce7.)
+RSL_DEV void block_sum7(const double (&v)[7], double* sh, double* mom) {
+  const int nw = (int)(blockDim.x >> 6);  // read once: not again between each sum's barriers
+  for (int q = 0; q < 7; ++q) {
+    const double r = block_sum(v[q], sh, nw);
+    if (threadIdx.x == 0) mom[q] = r;
+  }
+}
+
+constexpr int kVelU = 8;
+
+// kVelU cells i0 + u * stride (u < kVelU; stride = the block size) of one thread, all loads issued first (the loop is
+// HBM-latency bound otherwise); cells at or past e read as weight 0, grid index 0
+RSL_DEV void vel_load(long long i0, long long e, unsigned stride, const int* __restrict__ gidx,
+                      const double* __restrict__ y, const unsigned* __restrict__ amask, int (&gv)[kVelU],
+                      double (&yv)[kVelU], unsigned (&mv)[kVelU]) {
+#pragma unroll
+  for (int u = 0; u < kVelU; ++u) {
+    const long long i = i0 + (long long)u * stride;
+    const bool ok = i < e;
+    const long long ii = ok ? i : i0;  // i0 < e: always a valid address
+    gv[u] = gidx[ii];
+    yv[u] = y[ii];
+    mv[u] = amask ? amask[ii] : 1u;
+    if (!ok) {
+      gv[u] = 0;
+      yv[u] = 0.0;
+      mv[u] = 0u;
+    }
+  }
+}
+
+RSL_DEV double qcost(double vx, double vy, double k, double ridge, const double* m) {
+  // m: [n, cc, cs, ss, cy, sy, yy]
+  const double kx = k * vx, ky = k * vy;
+  return m[6] - 2.0 * (kx * m[4] + ky * m[5]) + kx * kx * m[1] + 2.0 * kx * ky * m[2] + ky * ky * m[3] +
+         ridge * (vx * vx + vy * vy);
+}
+
+// The minimiser of the convex quadratic of the moments m over the box [lx, hx] x [ly, hy]: the interior
+// normal-equation solution when feasible, else the best of the four edge minimisers (1-D clamp).
+RSL_DEV double2 box_solve(const double* m, double k, double ridge, double lx, double hx, double ly, double hy) {
+  const double H00 = k * k * m[1] + ridge, H01 = k * k * m[2], H11 = k * k * m[3] + ridge;
+  const double b0 = k * m[4], b1 = k * m[5];
+  const double det = H00 * H11 - H01 * H01;
+  double bx = 0.0, by = 0.0;
+  bool done = false;
+  if (det > 1e-300) {
+    const double vx = (H11 * b0 - H01 * b1) / det, vy = (H00 * b1 - H01 * b0) / det;
+    if (vx >= lx && vx <= hx && vy >= ly && vy <= hy) {
+      bx = vx;
+      by = vy;
+      done = true;
+    }
+  }
+  if (!done) {
+    double bc = INFINITY;
+    for (int edge = 0; edge < 4; ++edge) {
+      const int fix = edge >> 1;  // 0: vx fixed, 1: vy fixed
+      const double val = (fix == 0) ? ((edge & 1) ? hx : lx) : ((edge & 1) ? hy : ly);
+      double x;
+      if (fix == 0) {
+        x = H11 > 0 ? (b1 - H01 * val) / H11 : 0.0;
+        x = fmin(fmax(x, ly), hy);
+      } else {
+        x = H00 > 0 ? (b0 - H01 * val) / H00 : 0.0;
+        x = fmin(fmax(x, lx), hx);
+      }
+      const double vx = fix == 0 ? val : x, vy = fix == 0 ? x : val;
+      const double cst = qcost(vx, vy, k, ridge, m);
+      if (cst < bc) {
+        bc = cst;
+        bx = vx;
+        by = vy;
+      }
+    }
+  }
+  return make_double2(bx, by);
+}
+
+}  // namespace rsl

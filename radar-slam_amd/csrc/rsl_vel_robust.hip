@@ -12,10 +12,13 @@
 // scale costs 1 pass per iteration, the estimated scale 4; the LS start and the output pass add 2.  The workgroup
 // re-reads its own lines, so all passes after the first are served by L2 / Infinity Cache.
 //
-// k_velocity's arithmetic is not shared but duplicated here (block reduction order, the 2x2 box rule), so that file
-// compiles exactly as before.
+// The start comes from k_velocity's own source: the cell loader and the 2x2 box solve are the functions k_velocity
+// calls (rsl_vel_common.h), and rv_reduce7 below adds in block_sum's order.  Same source, not guaranteed the same bits:
+// under fp-contract the compiler chooses per kernel which products it fuses into an fma, so the two starts may differ
+// in the last place (tests/test_gpu_vel_robust.py::test_ls_equivalence holds them within 1e-13).
 #include "rsl_common.h"
 #include "rsl_internal.h"
+#include "rsl_vel_common.h"
 #include "../../include/rsl.h"
 
 namespace rsl {
@@ -23,7 +26,6 @@ namespace {
 
 constexpr int kRvThreads = 512;
 constexpr int kRvWaves = kRvThreads / 64;
-constexpr int kRvU = 8;        // cells per thread per trip (gidx path), all loads issued first
 constexpr int kRvBins = 2048;  // histogram bins of one radix-select pass (11-bit digit), 4 per thread
 constexpr int kRvPer = kRvBins / kRvThreads;
 typedef unsigned long long u64;
@@ -44,27 +46,14 @@ RSL_DEV void rv_cells(const double* __restrict__ az, const int* __restrict__ gid
                       const unsigned* __restrict__ amask, const double* cs_tab, int G, long long b, long long e,
                       Fn&& fn) {
   if (gidx) {
-    const long long step = (long long)kRvThreads * kRvU;
+    const long long step = (long long)kRvThreads * kVelU;
     for (long long i0 = b + threadIdx.x; i0 < e; i0 += step) {
-      int gv[kRvU];
-      double yv[kRvU];
-      unsigned mv[kRvU];
+      int gv[kVelU];
+      double yv[kVelU];
+      unsigned mv[kVelU];
+      vel_load(i0, e, kRvThreads, gidx, y, amask, gv, yv, mv);
 #pragma unroll
-      for (int u = 0; u < kRvU; ++u) {
-        const long long i = i0 + (long long)u * kRvThreads;
-        const bool ok = i < e;
-        const long long ii = ok ? i : i0;  // i0 < e: always a valid address
-        gv[u] = gidx[ii];
-        yv[u] = y[ii];
-        mv[u] = amask ? amask[ii] : 1u;
-        if (!ok) {
-          gv[u] = 0;
-          yv[u] = 0.0;
-          mv[u] = 0u;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kRvU; ++u) {
+      for (int u = 0; u < kVelU; ++u) {
         const long long i = i0 + (long long)u * kRvThreads;
         fn(i, i < e, __popc(mv[u]), cs_tab[gv[u]], cs_tab[G + gv[u]], yv[u]);
       }
@@ -102,8 +91,10 @@ RSL_DEV double rv_rho(int loss, double a, double t) {
   return t * t / 3.0;
 }
 
-// Sums of 7 values over the workgroup into mom[0..6], in k_velocity's order (wave shuffle tree, then the waves in
-// order on thread 0).  Valid for every thread on return.
+// Sums of 7 values over the workgroup into mom[0..6], in block_sum's order (wave shuffle tree, then the waves in order
+// on thread 0) with all 7 in one pass: 2 barriers instead of 21.  Valid for every thread on return.  Kept beside
+// block_sum7 (8 doubles of LDS, k_velocity's): with 7 x block_sum here the Huber solve at a fixed scale took 2.376
+// instead of 2.210 ms per 2000 cfg2 frames.
 RSL_DEV void rv_reduce7(double (&v)[7], double* red, double* mom) {
   const int t = threadIdx.x;
 #pragma unroll
@@ -120,55 +111,6 @@ RSL_DEV void rv_reduce7(double (&v)[7], double* red, double* mom) {
       mom[q] = r;
     }
   __syncthreads();
-}
-
-RSL_DEV double rv_qcost(double vx, double vy, double k, double ridge, const double* m) {
-  // m: [n, cc, cs, ss, cy, sy, yy]
-  const double kx = k * vx, ky = k * vy;
-  return m[6] - 2.0 * (kx * m[4] + ky * m[5]) + kx * kx * m[1] + 2.0 * kx * ky * m[2] + ky * ky * m[3] +
-         ridge * (vx * vx + vy * vy);
-}
-
-// k_velocity's 2x2 rule on the moments m: the interior normal-equation solution when feasible, else the best edge.
-RSL_DEV void rv_box_solve(const double* m, double k, double ridge, double lx, double hx, double ly, double hy,
-                          double* sol) {
-  const double H00 = k * k * m[1] + ridge, H01 = k * k * m[2], H11 = k * k * m[3] + ridge;
-  const double b0 = k * m[4], b1 = k * m[5];
-  const double det = H00 * H11 - H01 * H01;
-  double bx = 0.0, by = 0.0;
-  bool done = false;
-  if (det > 1e-300) {
-    const double vx = (H11 * b0 - H01 * b1) / det, vy = (H00 * b1 - H01 * b0) / det;
-    if (vx >= lx && vx <= hx && vy >= ly && vy <= hy) {
-      bx = vx;
-      by = vy;
-      done = true;
-    }
-  }
-  if (!done) {
-    double bc = INFINITY;
-    for (int edge = 0; edge < 4; ++edge) {
-      const int fix = edge >> 1;  // 0: vx fixed, 1: vy fixed
-      const double val = (fix == 0) ? ((edge & 1) ? hx : lx) : ((edge & 1) ? hy : ly);
-      double x;
-      if (fix == 0) {
-        x = H11 > 0 ? (b1 - H01 * val) / H11 : 0.0;
-        x = fmin(fmax(x, ly), hy);
-      } else {
-        x = H00 > 0 ? (b0 - H01 * val) / H00 : 0.0;
-        x = fmin(fmax(x, lx), hx);
-      }
-      const double vx = fix == 0 ? val : x, vy = fix == 0 ? x : val;
-      const double cst = rv_qcost(vx, vy, k, ridge, m);
-      if (cst < bc) {
-        bc = cst;
-        bx = vx;
-        by = vy;
-      }
-    }
-  }
-  sol[0] = bx;
-  sol[1] = by;
 }
 
 }  // namespace
@@ -212,7 +154,12 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
     rv_reduce7(v, red, mom);
   }
   const double W = mom[0];  // sum of the multiplicities: an exact integer
-  if (t == 0) rv_box_solve(mom, k, ridge, lx, hx, ly, hy, bc);
+  auto solve = [&]() {  // thread 0: the box solve on the moments, broadcast through bc
+    const double2 x = box_solve(mom, k, ridge, lx, hx, ly, hy);
+    bc[0] = x.x;
+    bc[1] = x.y;
+  };
+  if (t == 0) solve();
   __syncthreads();
   double vx = bc[0], vy = bc[1];
 
@@ -300,7 +247,7 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
       conv = true;
       break;
     }
-    if (t == 0) rv_box_solve(mom, k, ridge, lx, hx, ly, hy, bc);
+    if (t == 0) solve();
     __syncthreads();
     const double nx = bc[0], ny = bc[1];
     const double dx = fmax(fabs(nx - vx), fabs(ny - vy));

@@ -17,6 +17,11 @@ SHAPES = {  # name: (F, A, C, T_c)  -> K1 tiles = F * A * ceil(C / 8) at S = 512
     'cfg1': (5, 8, 64, 25.6e-6),         # S = 256, packed: k_range_fft_r256, 8 class tiles per (frame, antenna)
     'cfg2': (40, 8, 128, 51.2e-6),       # 5120 tiles: 6.7 per resident workgroup
     'cfg5': (6, 16, 256, 102.4e-6),      # S = 1024, packed: k_range_fft_r1024, 32 class tiles per (frame, antenna)
+    # k_range_fft_r256 past its static tiles: 4608 tiles, more than twice any resident grid (at most 8 workgroups x 256
+    # CUs = 2048), so tiles are really dequeued ('cfg1' has 320, fewer than the grid: every workgroup's first tile)
+    'cfg1_deep': (72, 8, 64, 25.6e-6),
+    # ... and at its smallest grid: the per-frame launches have 8 tiles = 8 workgroups, one tile per XCD
+    'cfg1_min': (2, 1, 64, 25.6e-6),
 }
 
 
