@@ -204,6 +204,39 @@ int rsl_doa_extras(rsl_handle h, const void* rds, int A, int S, int C, const voi
                    const void* ncell_dev, long long ncell, const void* steer_tab, const void* steer_c128, int G,
                    int method, double esprit_scale, void* out_idx, void* out_gmax, void* esprit_deg, void* phase);
 
+/* Spatially smoothed MUSIC: several directions of arrival per cell from one snapshot of a uniform linear array
+ *     (rsl_ssmusic.hip; the reference project has no counterpart, this comment is the specification).
+ *     Cells and n as rsl_doa (n = min(*ncell_dev, ncell); n = 0 launches nothing; slots beyond n are not written).
+ *     M = A antennas, 3 <= M <= 16; sub-array length L, 2 <= L <= min(M, RSL_SS_MAX_L); K = M - L + 1;
+ *     output width nmax, 1 <= nmax <= L - 1; 0 <= num_sources <= nmax (0: estimate the order); rel in (0, 1).
+ *     Per cell:
+ *     1. x = rds[f, :, r, c].  If sum |x|^2 = 0 the cell is empty: nsrc = 0, every pick -1 / NaN, the eig and spec
+ *        rows NaN.  Otherwise s = x / ||x||.
+ *     2. R_f[p][q] = (1/K) sum_{k<K} s[k+p] conj(s[k+q]);  R[p][q] = (R_f[p][q] + conj(R_f[L-1-p][L-1-q])) / 2
+ *        (forward-backward smoothing; Hermitian and persymmetric L x L; its trace is the mean power of the K
+ *        sub-arrays, 1 for L = M).
+ *     3. Eigenvalues l_1 >= ... >= l_L, orthonormal eigenvectors v_i, by cyclic complex Jacobi in fp32: at most
+ *        RSL_SS_MAX_SWEEPS sweeps (round-robin order); a cell stops rotating once its off-diagonal Frobenius norm
+ *        is <= RSL_SS_OFF_TOL ||R||_F at the start of a sweep.
+ *     4. k = num_sources if > 0, else the number of i with l_i >= rel l_1, clamped to [1, nmax].
+ *     5. den[g] = sum_{i>k} |v_i^H a_g|^2 with a_g = steer_sub_c64[g] (device c64 [G][L]: a_g[l] = exp(j l psi_g),
+ *        psi_g = 2 pi d sin(theta_g) / lambda, the first L columns of the array's steering matrix, built by the host
+ *        in fp64).  den in [0, L]; the MUSIC pseudo-spectrum is 1 / den.
+ *     6. g is a local minimum if den[g] < den[g-1] and den[g] <= den[g+1] (g = 0: den[0] < den[1]; g = G-1:
+ *        den[G-1] < den[G-2]).  The picks are the k local minima of smallest den, ties to the lower index, listed in
+ *        ascending den; with fewer than k minima the remaining slots are -1 / NaN.
+ *     out_nsrc i32 [n] = k; out_idx i32 [n][nmax] = the picks; out_den f32 [n][nmax] (nullable) = den at each pick;
+ *     out_eig f32 [n][L] (nullable) = the eigenvalues, descending; out_spec f32 [n][G] (nullable) = the den row.
+ *     RSL_ERR_INVALID: M, L, nmax, num_sources or rel out of range (or rel NaN), G < 3, null rds, lists,
+ *     steer_sub_c64, out_nsrc or out_idx.  Timed under RSL_K_DOA_SCAN. */
+#define RSL_SS_MAX_L 8
+#define RSL_SS_MAX_SWEEPS 12
+#define RSL_SS_OFF_TOL 1e-8f
+int rsl_doa_smoothed(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
+                     const void* ncell_dev, long long ncell, const void* steer_sub_c64, int G, int L, int nmax,
+                     int num_sources, double rel, void* out_nsrc, void* out_idx, void* out_den, void* out_eig,
+                     void* out_spec);
+
 /* a11, a15, a26  normalised signature (c64 [n, A], nullable), ESPRIT closed form (f64 deg, nullable;
  *     angle_estimation.py:178-225 with esprit_scale = lambda / (2 pi d)), spatial phase
  *     angle(s1 conj(s0)) (f64, nullable; velocity_solver.py:136), az_out = az_table[gidx] (f64, nullable). */

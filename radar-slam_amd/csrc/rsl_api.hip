@@ -513,6 +513,33 @@ int rsl_doa_extras(rsl_handle h, const void* rds, int A, int S, int C, const voi
                    "doa_extras");
 }
 
+int rsl_doa_smoothed(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
+                     const void* ncell_dev, long long ncell, const void* steer_sub_c64, int G, int L, int nmax,
+                     int num_sources, double rel, void* out_nsrc, void* out_idx, void* out_den, void* out_eig,
+                     void* out_spec) {
+  if (!h) return RSL_ERR_INVALID;
+  if (A < 3 || A > 16 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: bad shape (3 <= A <= 16)");
+  if (L < 2 || L > A || L > RSL_SS_MAX_L)
+    return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: sub-array length outside [2, min(A, RSL_SS_MAX_L)]");
+  if (nmax < 1 || nmax > L - 1) return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: nmax outside [1, L - 1]");
+  if (num_sources < 0 || num_sources > nmax)
+    return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: num_sources outside [0, nmax]");
+  if (!(rel > 0.0 && rel < 1.0)) return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: rel outside (0, 1)");
+  if (G < 3) return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: G < 3");
+  if (!rds || !c_frame || !c_rc || !steer_sub_c64 || !out_nsrc || !out_idx)
+    return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: null pointer");
+  if (ncell <= 0) return RSL_OK;  // ncell is the launch bound (capacity) when ncell_dev is given
+  hipSetDevice(h->device);
+  Scope sc(h, RSL_K_DOA_SCAN);
+  return hip_check(h,
+                   rsl::launch_doa_smoothed(h->stream, (const float2*)rds, A, S, C, (const int*)c_frame,
+                                            (const int*)c_rc, (const long long*)ncell_dev, ncell,
+                                            (const float2*)steer_sub_c64, G, L, nmax, num_sources, (float)rel,
+                                            (int*)out_nsrc, (int*)out_idx, (float*)out_den, (float*)out_eig,
+                                            (float*)out_spec),
+                   "doa_smoothed");
+}
+
 int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
                     const void* ncell_dev, long long ncell, double esprit_scale, const void* gidx,
                     const void* az_table, void* sig_out, void* esprit_deg, void* phase, void* az_out) {

@@ -81,6 +81,12 @@ hipError_t launch_doa_toep(hipStream_t st, const float2* rds, int A, int S, int 
                            const int* c_rc, const long long* ncell_dev, long long ncell_host, const void* toep_tab,
                            int ntiles32, int G, int music, const double* steerT, int* out_idx, float* out_gmax,
                            double esprit_scale, double* out_esprit, double* out_phase, float* out_spec = nullptr);
+// K5 alternative (rsl_ssmusic.hip): forward-backward spatially smoothed MUSIC, up to nmax angles per cell (the
+// estimator is specified at rsl_doa_smoothed in include/rsl.h).  steer c64 [G][L]; 2 <= L <= RSL_SS_MAX_L.
+hipError_t launch_doa_smoothed(hipStream_t st, const float2* rds, int M, int S, int C, const int* c_frame,
+                               const int* c_rc, const long long* ncell_dev, long long ncell, const float2* steer,
+                               int G, int L, int nmax, int num_sources, float rel, int* out_nsrc, int* out_idx,
+                               float* out_den, float* out_eig, float* out_spec);
 // Host: builds the Toeplitz operand table; returns 1 if the steering matrix is a uniform linear array.
 int toep_table_build(const double* steer_c128, int G, int M, uint16_t* out, int* ntiles32_out);
 bool toep_table_fits(int G, int M);

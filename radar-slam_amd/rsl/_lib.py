@@ -19,6 +19,7 @@ DOA_TOEPLITZ = 0x100
 DOA_SPEC_GMAJOR = 0x200
 DOA_SPEC_BLOCKED = 0x400
 STEER_TOEPLITZ = 1
+SS_MAX_L = 8  # RSL_SS_MAX_L: the longest sub-array of rsl_doa_smoothed
 LOSS_HUBER, LOSS_TUKEY = 1, 2
 LOSS_IDS = {'huber': LOSS_HUBER, 'tukey': LOSS_TUKEY}
 LOSS_DEFAULT_C = {LOSS_HUBER: 1.345, LOSS_TUKEY: 4.685}  # 95 % efficiency at the normal distribution
@@ -54,6 +55,8 @@ SIGNATURES = {
     'rsl_doa': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_longlong, _P, _P, c_int, c_int, _P, _P, _P]),
     'rsl_doa_extras': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_longlong, _P, _P, c_int, c_int, c_double,
                                _P, _P, _P, _P]),
+    'rsl_doa_smoothed': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_longlong, _P, c_int, c_int, c_int, c_int,
+                                 c_double, _P, _P, _P, _P, _P]),
     'rsl_cell_extras': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_longlong, c_double, _P, _P, _P, _P,
                                 _P, _P]),
     'rsl_confidence': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_longlong, _P, _P, _P, _P]),

@@ -64,12 +64,42 @@ class ChainConfig:
     velocity_c: Optional[float] = None         # tuning constant; None: 1.345 (huber) / 4.685 (tukey)
     velocity_iters: int = 30
     velocity_tol: float = 1e-9
+    multi_source: bool = False                 # also run the spatially smoothed MUSIC (rsl_doa_smoothed) on every
+                                               # cell: up to ss_max angles per cell in results()['ss_*']; gidx, esprit,
+                                               # phase and the velocity solve keep using the one-angle scan
+    ss_len: Optional[int] = None               # sub-array length L; None: min(8, A - A // 3)
+    ss_sources: int = 0                        # sources per cell; 0: estimated from the eigenvalues (>= ss_rel * the
+                                               # largest), which depends on the SNR -- a fixed count is the dependable
+                                               # setting
+    ss_rel: float = 0.05
+    ss_max: int = 3                            # angles kept per cell (lowered to L - 1 where it exceeds it)
 
     def __post_init__(self):
+        if self.ss_len is not None and not 2 <= int(self.ss_len) <= _lib.SS_MAX_L:
+            raise ValueError(f'ss_len must lie in [2, {_lib.SS_MAX_L}], not {self.ss_len!r}')
+        if int(self.ss_max) < 1:
+            raise ValueError(f'ss_max must be >= 1, not {self.ss_max!r}')
+        if not 0 <= int(self.ss_sources) <= int(self.ss_max):
+            raise ValueError(f'ss_sources must lie in [0, ss_max], not {self.ss_sources!r}')
+        if not 0.0 < float(self.ss_rel) < 1.0:
+            raise ValueError(f'ss_rel must lie in (0, 1), not {self.ss_rel!r}')
+        if self.multi_source:
+            A = int(self.num_antennas)
+            if not 3 <= A <= 16:
+                raise ValueError(f'multi_source needs 3 to 16 antennas, not {A}')
+            L = self.ss_sub_len
+            if L > A:
+                raise ValueError(f'ss_len {L} exceeds the {A} antennas')
+            if int(self.ss_sources) > min(int(self.ss_max), L - 1):
+                raise ValueError(f'ss_sources {self.ss_sources} exceeds the {L - 1} angles a sub-array of {L} resolves')
         if self.velocity_loss not in ('ls', 'huber', 'tukey'):
             raise ValueError(f"velocity_loss must be 'ls', 'huber' or 'tukey', not {self.velocity_loss!r}")
         if self.detector not in ('threshold', 'cfar'):
             raise ValueError(f"detector must be 'threshold' or 'cfar', not {self.detector!r}")
+
+    @property
+    def ss_sub_len(self) -> int:
+        return tables.default_sub_len(self.num_antennas) if self.ss_len is None else int(self.ss_len)
 
     @property
     def S(self) -> int:
@@ -111,7 +141,8 @@ class RadarChain:
                 cfg.cfar_pfa, tables.cfar_training_cells(cfg.cfar_guard, cfg.cfar_train))
         d = cfg.antenna_spacing or cfg.lambda_c / 2
         self.grid = tables.azimuth_grid(cfg.search_range, cfg.search_resolution)
-        self.steer = ctx.steering(tables.steering_matrix(self.grid, np.arange(A) * d, cfg.lambda_c))
+        steer_c128 = tables.steering_matrix(self.grid, np.arange(A) * d, cfg.lambda_c)
+        self.steer = ctx.steering(steer_c128)
         self.az_table = ctx.to_dev(np.radians(self.grid).astype(np.float64))
         self.esprit_scale = cfg.lambda_c / (2 * np.pi * d)
         lam_v = cfg.velocity_lambda or cfg.lambda_c
@@ -138,6 +169,13 @@ class RadarChain:
         self.vel = vel_out if vel_out is not None else e((F, 8), torch.float64)
         self.vel_weight = e((cc,), torch.float32) if cfg.velocity_loss != 'ls' else None  # IRLS weight of every cell
         self.ncell_dev = self.offs['cell_base'][F:F + 1]
+        self.ss = None
+        if cfg.multi_source:  # smoothed MUSIC: its own outputs on the same cell lists
+            L = cfg.ss_sub_len
+            self.ss_nmax = min(int(cfg.ss_max), L - 1)
+            self.ss_steer = ctx.steering_sub(steer_c128, L)
+            self.ss = dict(nsrc=e((cc,), torch.int32), idx=e((cc, self.ss_nmax), torch.int32),
+                           den=e((cc, self.ss_nmax), torch.float32))
         # one signature gather for DoA + ESPRIT + phase when the Toeplitz path applies (uniform linear array)
         self.fused_doa = bool(self.steer['toeplitz']) and A >= 2 and not cfg.spectrum
         self.spec = None
@@ -232,6 +270,9 @@ class RadarChain:
                 ctx.cell_extras(self.rds, L['c_frame'], L['c_rc'], n=self.cell_cap, n_dev=self.ncell_dev,
                                 esprit_scale=self.esprit_scale, want_esprit=esprit, want_phase=velocity,
                                 bufs=self.ext)
+        if self.ss is not None:
+            ctx.doa_smoothed(self.rds, L['c_frame'], L['c_rc'], self.ss_steer, n=self.cell_cap, n_dev=self.ncell_dev,
+                             nmax=self.ss_nmax, num_sources=cfg.ss_sources, rel=cfg.ss_rel, out=self.ss)
         if velocity and cfg.velocity_loss != 'ls':
             # vel columns 2-7 become {cost, rmse_w, n_in, n, sigma, it} (include/rsl.h)
             ctx.velocity_robust(None, self.ext['phase'], self.offs['cell_base'], k=self.k, loss=cfg.velocity_loss,
@@ -257,6 +298,9 @@ class RadarChain:
         L = self.lists
         h = lambda t, n: t[:n].cpu().numpy()
         extra = dict(vel_weight=h(self.vel_weight, nc)) if self.vel_weight is not None else {}
+        if self.ss is not None:
+            extra.update(ss_nsrc=h(self.ss['nsrc'], nc), ss_gidx=h(self.ss['idx'], nc).astype(np.int64),
+                         ss_den=h(self.ss['den'], nc).astype(np.float64))
         return dict(entry_base=self.offs['entry_base'].cpu().numpy(), cell_base=self.offs['cell_base'].cpu().numpy(),
                     **dict(zip(('e_ant', 'e_rbin', 'e_dbin'), unpack_coord(h(L['e_coord'], ne)))),
                     e_cell=h(L['e_cell'], ne), e_pdb=h(L['e_pdb'], ne).astype(np.float64), c_frame=h(L['c_frame'], nc),

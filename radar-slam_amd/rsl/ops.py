@@ -178,6 +178,68 @@ def doa(method: str, steer_c128: np.ndarray, *, sigs=None, rds=None, rbins=None,
     return to_host(idx[:N]).astype(np.int64), (to_host(spec[:N], np.float64) if want_spec else None)
 
 
+def doa_smoothed(steer_c128: np.ndarray, *, sigs=None, rds=None, rbins=None, dbins=None, sub_len=None, num_sources=0,
+                 rel=0.05, nmax=3, want_eig=False, want_spec=False, grid_deg=None, ctx: Optional[Context] = None):
+    """Spatially smoothed MUSIC (rsl_doa_smoothed, specified in include/rsl.h): up to nmax angles per cell from one
+    snapshot of a uniform linear array with the [G, M] steering matrix steer_c128; signatures given ([N, M]) or
+    gathered from an RDS.  sub_len=None: tables.default_sub_len(M); nmax is lowered to sub_len - 1 where it exceeds
+    it.  num_sources=0 estimates the order per cell as the number of eigenvalues >= rel * the largest: rel depends on
+    the SNR, and forward-backward smoothing leaves some relative phases of two coherent sources close to rank 1, so a
+    fixed num_sources is the dependable setting.  Returns a dict of host arrays: nsrc i32 [N], gidx i64 [N, nmax] (-1
+    where a slot is empty), deg f64 [N, nmax] (grid_deg[gidx]; without grid_deg the angle of a half-wavelength array
+    with that phase step; NaN where empty), den f64 [N, nmax] (null spectrum at the pick, ascending), and on request
+    eig f64 [N, L] (descending) and spec f64 [N, G] (the whole null spectrum; MUSIC's pseudo-spectrum is 1 / spec)."""
+    c = _ctx(ctx)
+    st = np.asarray(steer_c128)
+    G, M = st.shape
+    L = tables.default_sub_len(M) if sub_len is None else int(sub_len)
+    if not 3 <= M <= 16:
+        raise ValueError(f'doa_smoothed: {M} antennas outside [3, 16]')
+    if not 2 <= L <= min(M, _lib.SS_MAX_L):
+        raise ValueError(f'doa_smoothed: sub_len {L} outside [2, {min(M, _lib.SS_MAX_L)}]')
+    nmax, num_sources = min(int(nmax), L - 1), int(num_sources)
+    if not 1 <= nmax <= L - 1:
+        raise ValueError(f'doa_smoothed: nmax {nmax} outside [1, {L - 1}]')
+    if not 0 <= num_sources <= nmax:
+        raise ValueError(f'doa_smoothed: num_sources {num_sources} outside [0, {nmax}]')
+    if not 0.0 < float(rel) < 1.0:
+        raise ValueError(f'doa_smoothed: rel {rel} outside (0, 1)')
+    if G < 3:
+        raise ValueError('doa_smoothed: at least 3 grid points')
+    sub = c.steering_sub(st, L)
+    if sigs is not None:
+        if np.atleast_2d(np.asarray(sigs)).shape[1] != M:
+            raise ValueError(f'doa_smoothed: signatures of {np.atleast_2d(np.asarray(sigs)).shape[1]} antennas, '
+                             f'steering matrix of {M}')
+        d, fr, rc, N = _sig_cells(c, sigs)
+    else:
+        d, fr, rc, N = _rds_cells(c, rds, rbins, dbins)
+        if d.shape[1] != M:
+            raise ValueError(f'doa_smoothed: RDS of {d.shape[1]} antennas, steering matrix of {M}')
+    if grid_deg is None:
+        psi = np.angle(st[:, 1] * st[:, 0].conj())
+        grid_deg = np.degrees(np.arcsin(np.clip(psi / np.pi, -1.0, 1.0)))
+    grid_deg = np.asarray(grid_deg, np.float64)
+    if N == 0:
+        res = dict(nsrc=np.zeros(0, np.int32), gidx=np.zeros((0, nmax), np.int64), deg=np.zeros((0, nmax)),
+                   den=np.zeros((0, nmax)))
+        if want_eig:
+            res['eig'] = np.zeros((0, L))
+        if want_spec:
+            res['spec'] = np.zeros((0, G))
+        return res
+    nsrc, idx, den, eig, spec = c.doa_smoothed(d, fr, rc, sub, n=N, nmax=nmax, num_sources=num_sources, rel=rel,
+                                               want_eig=want_eig, want_spec=want_spec)
+    gi = to_host(idx[:N]).astype(np.int64)
+    res = dict(nsrc=to_host(nsrc[:N]), gidx=gi, deg=np.where(gi >= 0, grid_deg[np.clip(gi, 0, None)], np.nan),
+               den=to_host(den[:N], np.float64))
+    if want_eig:
+        res['eig'] = to_host(eig[:N], np.float64)
+    if want_spec:
+        res['spec'] = to_host(spec[:N], np.float64)
+    return res
+
+
 def subspace_music(sigs, steer_c128: np.ndarray, num_sources: int, ctx: Optional[Context] = None) -> np.ndarray:
     """MUSIC spectrum f64 [n, G] for any num_sources (angle_estimation.py:109-154; rsl_music_subspace)."""
     c = _ctx(ctx)

@@ -347,6 +347,46 @@ class Context:
                                            _ptr(phase)), 'rsl_doa_extras')
         return out_idx, esprit, phase
 
+    def steering_sub(self, steer_c128: np.ndarray, L: int):
+        """Upload the sub-array steering vectors of rsl_doa_smoothed: device c64 [G, L] (tables.subarray_steering;
+        ValueError for a non-uniform array)."""
+        key = ('sub', int(L), steer_c128.shape, hash(steer_c128.tobytes()))
+        hit = self._steer_cache.get(key)
+        if hit is None:
+            hit = self.to_dev(tables.subarray_steering(steer_c128, L).astype(np.complex64))
+            self._steer_cache[key] = hit
+        return hit
+
+    def doa_smoothed(self, rds, c_frame, c_rc, steer_sub, *, n: Optional[int] = None, n_dev=None, nmax: int = 3,
+                     num_sources: int = 0, rel: float = 0.05, want_den: bool = True, want_eig: bool = False,
+                     want_spec: bool = False, out=None):
+        """Forward-backward spatially smoothed MUSIC (rsl_doa_smoothed; the estimator is specified in include/rsl.h):
+        up to nmax angles per cell.  steer_sub: device c64 [G, L] (steering_sub); num_sources = 0 estimates the order
+        from the eigenvalues (those >= rel * the largest).  out: optional dict of preallocated nsrc i32 [cap], idx i32
+        [cap, nmax], den f32 [cap, nmax], eig f32 [cap, L], spec f32 [cap, G].  Returns (nsrc, idx, den, eig, spec),
+        None where not requested; slots beyond n = min(*n_dev, cap) are left as they were."""
+        torch = self.torch
+        _, A, S, C = rds.shape
+        G, L = int(steer_sub.shape[0]), int(steer_sub.shape[1])
+        cap = int(c_frame.shape[0]) if n is None else int(n)
+        o = out or {}
+        rows = max(cap, 1)
+        nmax = int(nmax)
+
+        def get(name, shape, dt, want=True):
+            t = o.get(name)
+            return t if t is not None else (self.empty(shape, dt) if want else None)
+        nsrc = get('nsrc', (rows,), torch.int32)
+        idx = get('idx', (rows, max(nmax, 1)), torch.int32)
+        den = get('den', (rows, max(nmax, 1)), torch.float32, want_den)
+        eig = get('eig', (rows, L), torch.float32, want_eig)
+        spec = get('spec', (rows, G), torch.float32, want_spec)
+        self._bind()
+        self.check(self.lib.rsl_doa_smoothed(self.h, _ptr(rds), A, S, C, _ptr(c_frame), _ptr(c_rc), _ptr(n_dev), cap,
+                                             _ptr(steer_sub), G, L, nmax, int(num_sources), float(rel), _ptr(nsrc),
+                                             _ptr(idx), _ptr(den), _ptr(eig), _ptr(spec)), 'rsl_doa_smoothed')
+        return nsrc, idx, den, eig, spec
+
     def cell_extras(self, rds, c_frame, c_rc, *, n: int, n_dev=None, esprit_scale: float = 1 / math.pi,
                     want_sig=False, want_esprit=False, want_phase=False, gidx=None, az_table=None, bufs=None):
         torch = self.torch

@@ -92,3 +92,26 @@ def steering_matrix(grid_deg, antenna_positions, lambda_c) -> np.ndarray:
     az = np.radians(np.asarray(grid_deg, dtype=np.float64))
     ph = 2 * np.pi * antenna_positions[None, :] * np.sin(az)[:, None] / lambda_c
     return np.exp(1j * ph)
+
+
+def default_sub_len(M: int) -> int:
+    """Sub-array length of the smoothed MUSIC when none is given: min(8, M - M // 3) (6 of 8, 8 of 16 antennas)."""
+    return min(8, int(M) - int(M) // 3)
+
+
+def subarray_steering(steer_c128, L: int) -> np.ndarray:
+    """Steering vectors c128 [G, L] of the first L elements of a uniform linear array, a_g[l] = exp(j l psi_g), from
+    the array's steering matrix [G, M] (rsl_doa_smoothed).  Spatial smoothing needs equal element spacing: raises
+    ValueError when the phase step between neighbouring elements is not the same along the array."""
+    st = np.asarray(steer_c128, dtype=np.complex128)
+    if st.ndim != 2 or st.shape[1] < 2:
+        raise ValueError('subarray_steering: steering matrix [G, M] with M >= 2 expected')
+    G, M = st.shape
+    L = int(L)
+    if not 2 <= L <= M:
+        raise ValueError(f'subarray_steering: sub-array length {L} outside [2, {M}]')
+    step = st[:, 1:] * st[:, :-1].conj()  # exp(j psi_g) between neighbours, for every neighbour pair
+    if not np.allclose(step, step[:, :1], rtol=0.0, atol=1e-9) or not np.allclose(np.abs(st), 1.0, atol=1e-9):
+        raise ValueError('subarray_steering: the element positions are not uniform (spatial smoothing needs a '
+                         'uniform linear array)')
+    return np.ascontiguousarray(st[:, :L] * st[:, :1].conj())  # element 0 as the phase reference

@@ -126,6 +126,45 @@ class AngleEstimator:
         logger.info(f"Processed {len(targets)} targets using {method}")
         return targets
 
+    def process_targets_smoothed(self, rds: np.ndarray, peaks: Dict, num_sources: int = 0, sub_len: Optional[int] = None,
+                                 rel: float = 0.05, max_sources: int = 3) -> List[Dict]:
+        """process_targets with the forward-backward spatially smoothed MUSIC (ops.doa_smoothed): several angles per
+        target.  The dicts of process_targets plus 'angles_deg' (list, deepest null first), 'num_sources' (the model
+        order used: num_sources, or with 0 the number of eigenvalues >= rel * the largest, at most max_sources) and
+        'eigenvalues' (descending, of the smoothed sub_len x sub_len covariance).  'azimuth_deg' is the first angle
+        (NaN when the null spectrum has no local minimum) and 'spectrum' the pseudo-spectrum 1 / den (0 where den <=
+        1e-12, the rule of music_spectrum).  A fixed num_sources is the dependable setting: rel depends on the SNR."""
+        plist = list(peaks['peaks'])
+        A, S, C = rds.shape
+        keep = []
+        for p in plist:
+            r, d = p['range_bin'], p['doppler_bin']
+            if -S <= r < S and -C <= d < C:
+                keep.append(p)
+            else:
+                logger.warning("Error processing target: index out of bounds")
+        rb = np.array([p['range_bin'] % S for p in keep], dtype=np.int64)
+        db = np.array([p['doppler_bin'] % C for p in keep], dtype=np.int64)
+        ctx = get_context()
+        d_rds = ops.as_dev_c64(ctx, rds)
+        sig, _, _ = ops.cell_extras(rds=d_rds, rbins=rb, dbins=db, esprit_scale=self._esprit_scale, want_sig=True)
+        res = ops.doa_smoothed(self._steer, rds=d_rds, rbins=rb, dbins=db, sub_len=sub_len, num_sources=num_sources,
+                               rel=rel, nmax=max_sources, want_eig=True, want_spec=True, grid_deg=self.azimuth_grid)
+        targets = []
+        for n, p in enumerate(keep):
+            angs = [float(a) for a in res['deg'][n] if not np.isnan(a)]
+            ang = angs[0] if angs else float('nan')
+            den = res['spec'][n]
+            spec = np.zeros_like(den)
+            np.divide(1.0, den, out=spec, where=den > 1e-12)
+            targets.append({'range_m': p['range_m'], 'doppler_hz': p['doppler_hz'], 'power_db': p['power_db'],
+                            'azimuth_deg': ang, 'azimuth_rad': np.radians(ang), 'antenna': p['antenna'],
+                            'range_bin': p['range_bin'], 'doppler_bin': p['doppler_bin'],
+                            'spatial_signature': sig[n], 'spectrum': spec, 'angles_deg': angs,
+                            'num_sources': int(res['nsrc'][n]), 'eigenvalues': res['eig'][n]})
+        logger.info(f"Processed {len(targets)} targets using smoothed music")
+        return targets
+
     def visualize_angle_spectrum(self, targets: List[Dict], save_path: Optional[str] = None) -> None:
         if not targets:
             logger.warning("No targets to visualize")
