@@ -13,6 +13,7 @@
 
 #include "../../include/rsl.h"
 #include "rsl_common.h"
+#include "rsl_doa_common.h"
 #include "rsl_internal.h"
 
 struct rsl_context {
@@ -108,6 +109,26 @@ void collect(rsl_context* h) {
     }
     h->ev[k].clear();
   }
+}
+
+// The cell list of a DoA entry point from its untyped arguments.
+rsl::CellList cell_list(const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
+                        const void* ncell_dev, long long ncell) {
+  return {(const float2*)rds, A, S, C, (const int*)c_frame, (const int*)c_rc, (const long long*)ncell_dev, ncell};
+}
+
+// The sections of a steering table that rsl_steer_table_build(G, M) wrote (rsl_doa_common.h SteerLayout).
+struct SteerView {
+  rsl::SteerLayout lay;
+  const float* f32;
+  const float* toep;
+  const double* t64;
+};
+
+SteerView steer_view(const void* tab, int G, int M) {
+  const rsl::SteerLayout lay = rsl::steer_layout(G, M);
+  const float* t = (const float*)tab;
+  return {lay, t, t + lay.f32_floats, reinterpret_cast<const double*>(t + lay.t64_offset)};
 }
 
 }  // namespace
@@ -379,32 +400,15 @@ int rsl_peak_emit(rsl_handle h, const void* rds, const void* mask, const void* u
                    "emit");
 }
 
-static long long steer_f32_floats(int G, int M) {
-  const int KS = (2 * M + 3) / 4, KSG = (KS + 3) / 4;
-  const long long ntiles = (2LL * G + 15) / 16;
-  return ntiles * KSG * 64 * 4;
-}
-
-static long long steer_toep_floats(int G, int M) {
-  const int KB = M <= 8 ? 1 : 2;
-  long long nt = (G + 31) / 32;
-  nt += nt & 1;
-  return nt * KB * 2 * 64 * 4;
-}
-
-// (3) the fp64 steering matrix transposed, steerT[m][g] (double2), for k_doa_fixup's coalesced exact re-scan; at a
-// 16-B aligned float offset (both sections before it are multiples of 4 floats)
-static long long steer_t64_offset(int G, int M) { return steer_f32_floats(G, M) + steer_toep_floats(G, M); }
-
 long long rsl_steer_table_floats(int G, int M) {
   if (G <= 0 || M <= 0) return 0;
-  return steer_t64_offset(G, M) + 4LL * G * M;
+  return rsl::steer_layout(G, M).total_floats;
 }
 
 int rsl_steer_table_build(const double* steer, int G, int M, float* out, int* ntiles_out, int* flags_out) {
   if (!steer || !out || G <= 0 || M <= 0 || M > 16) return RSL_ERR_INVALID;
-  const int KS = (2 * M + 3) / 4, KSG = (KS + 3) / 4;
-  const int ntiles = (2 * G + 15) / 16;
+  const rsl::SteerLayout lay = rsl::steer_layout(G, M);
+  const int KS = lay.ks, KSG = lay.ksg, ntiles = lay.ntiles16;
   for (int t = 0; t < ntiles; ++t)
     for (int sg = 0; sg < KSG; ++sg)
       for (int lane = 0; lane < 64; ++lane)
@@ -423,10 +427,9 @@ int rsl_steer_table_build(const double* steer, int G, int M, float* out, int* nt
           out[(((size_t)t * KSG + sg) * 64 + lane) * 4 + e] = (float)v;
         }
   if (ntiles_out) *ntiles_out = ntiles;
-  const int uni = rsl::toep_table_build(steer, G, M, reinterpret_cast<uint16_t*>(out + steer_f32_floats(G, M)),
-                                        nullptr);
-  if (flags_out) *flags_out = (uni && rsl::toep_table_fits(G, M)) ? RSL_STEER_TOEPLITZ : 0;
-  double* tT = reinterpret_cast<double*>(out + steer_t64_offset(G, M));
+  const int uni = rsl::toep_table_build(steer, G, M, reinterpret_cast<uint16_t*>(out + lay.f32_floats));
+  if (flags_out) *flags_out = (uni && lay.toep_fits) ? RSL_STEER_TOEPLITZ : 0;
+  double* tT = reinterpret_cast<double*>(out + lay.t64_offset);
   for (int m = 0; m < M; ++m)
     for (int g = 0; g < G; ++g) {
       tT[((size_t)m * G + g) * 2] = steer[((size_t)g * M + m) * 2];
@@ -447,41 +450,26 @@ int rsl_doa(rsl_handle h, const void* rds, int A, int S, int C, const void* c_fr
     return fail(h, RSL_ERR_INVALID, "rsl_doa: unknown method");
   const bool music = base_method == RSL_METHOD_MUSIC;
   (void)steer_c128;  // the exact re-scan reads the fp64 copy inside steer_tab (rsl_steer_table_build)
-  const double* steerT = reinterpret_cast<const double*>((const float*)steer_tab + steer_t64_offset(G, A));
+  const SteerView tab = steer_view(steer_tab, G, A);
+  const rsl::CellList cl = cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell);
   if (!ncell_dev && ncell <= 0) return RSL_OK;
   hipSetDevice(h->device);
   Scope sc(h, RSL_K_DOA_SCAN);
   // the Toeplitz f16-MFMA scan: argmax only, or with the whole spectrum in the cell-blocked layout (no gmax there)
   const bool toep_spec = out_spec && (method & RSL_DOA_SPEC_BLOCKED) && !out_gmax;
-  if (toep && (!out_spec || toep_spec) && rsl::toep_table_fits(G, A)) {
-    int nt32 = (G + 31) / 32;
-    nt32 += nt32 & 1;
-    const float* tp = (const float*)steer_tab + steer_f32_floats(G, A);
+  if (toep && (!out_spec || toep_spec) && tab.lay.toep_fits)
     return hip_check(h,
-                     rsl::launch_doa_toep(h->stream, (const float2*)rds, A, S, C, (const int*)c_frame,
-                                          (const int*)c_rc, (const long long*)ncell_dev, ncell, tp, nt32, G, music,
-                                          steerT, (int*)out_idx, (float*)out_gmax, 0.0,
-                                          nullptr, nullptr, toep_spec ? (float*)out_spec : nullptr),
+                     rsl::launch_doa_toep(h->stream, cl, tab.toep, G, music, tab.t64, (int*)out_idx, (float*)out_gmax,
+                                          0.0, nullptr, nullptr, toep_spec ? (float*)out_spec : nullptr),
                      "doa_toep");
-  }
-  long long blocks = 0;  // 0: all resident workgroups (occupancy x CUs)
-  if (!ncell_dev) blocks = (ncell + 127) / 128;  // 4 waves x 32 cells
-  const int ntiles = (2 * G + 15) / 16;
+  const long long spec_ld = (method & RSL_DOA_SPEC_BLOCKED) ? -1 : (method & RSL_DOA_SPEC_GMAJOR) ? ncell : 0;
   if (int r = hip_check(h,
-                        rsl::launch_doa_scan(h->stream, (const float2*)rds, A, S, C, (const int*)c_frame,
-                                             (const int*)c_rc, (const long long*)ncell_dev, ncell,
-                                             (const float*)steer_tab, ntiles, G, music, (int*)out_idx,
-                                             (float*)out_gmax, (float*)out_spec,
-                                             (method & RSL_DOA_SPEC_BLOCKED) ? -1
-                                             : (method & RSL_DOA_SPEC_GMAJOR) ? ncell : 0,
-                                             (int)blocks),
+                        rsl::launch_doa_scan(h->stream, cl, tab.f32, G, music, (int*)out_idx, (float*)out_gmax,
+                                             (float*)out_spec, spec_ld),
                         "doa_scan"))
     return r;
   // the cells the f32 scan marked ambiguous: exact fp64 argmax (rsl_doa_toep.hip k_doa_fixup)
-  return hip_check(h,
-                   rsl::launch_doa_fixup(h->stream, (const float2*)rds, A, S, C, (const int*)c_frame,
-                                         (const int*)c_rc, (const long long*)ncell_dev, ncell, G, music,
-                                         steerT, (int*)out_idx, (float*)out_gmax),
+  return hip_check(h, rsl::launch_doa_fixup(h->stream, cl, G, music, tab.t64, (int*)out_idx, (float*)out_gmax),
                    "doa_fixup");
 }
 
@@ -496,19 +484,15 @@ int rsl_doa_extras(rsl_handle h, const void* rds, int A, int S, int C, const voi
     return fail(h, RSL_ERR_INVALID, "rsl_doa_extras: unknown method");
   const bool music = method == RSL_METHOD_MUSIC;
   (void)steer_c128;  // the exact re-scan reads the fp64 copy inside steer_tab (rsl_steer_table_build)
-  const double* steerT = reinterpret_cast<const double*>((const float*)steer_tab + steer_t64_offset(G, A));
-  if (!rsl::toep_table_fits(G, A))
+  const SteerView tab = steer_view(steer_tab, G, A);
+  if (!tab.lay.toep_fits)
     return fail(h, RSL_ERR_UNSUPPORTED, "rsl_doa_extras: grid too large for the Toeplitz path (use rsl_doa)");
   if (!ncell_dev && ncell <= 0) return RSL_OK;
   hipSetDevice(h->device);
   Scope sc(h, RSL_K_DOA_SCAN);
-  int nt32 = (G + 31) / 32;
-  nt32 += nt32 & 1;
-  const float* tp = (const float*)steer_tab + steer_f32_floats(G, A);
   return hip_check(h,
-                   rsl::launch_doa_toep(h->stream, (const float2*)rds, A, S, C, (const int*)c_frame, (const int*)c_rc,
-                                        (const long long*)ncell_dev, ncell, tp, nt32, G, music,
-                                        steerT, (int*)out_idx, (float*)out_gmax, esprit_scale,
+                   rsl::launch_doa_toep(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell), tab.toep,
+                                        G, music, tab.t64, (int*)out_idx, (float*)out_gmax, esprit_scale,
                                         (double*)esprit_deg, (double*)phase),
                    "doa_extras");
 }
@@ -532,8 +516,7 @@ int rsl_doa_smoothed(rsl_handle h, const void* rds, int A, int S, int C, const v
   hipSetDevice(h->device);
   Scope sc(h, RSL_K_DOA_SCAN);
   return hip_check(h,
-                   rsl::launch_doa_smoothed(h->stream, (const float2*)rds, A, S, C, (const int*)c_frame,
-                                            (const int*)c_rc, (const long long*)ncell_dev, ncell,
+                   rsl::launch_doa_smoothed(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell),
                                             (const float2*)steer_sub_c64, G, L, nmax, num_sources, (float)rel,
                                             (int*)out_nsrc, (int*)out_idx, (float*)out_den, (float*)out_eig,
                                             (float*)out_spec),
@@ -550,9 +533,8 @@ int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const vo
   if (ncell <= 0) return RSL_OK;  // ncell is the launch bound (capacity) when ncell_dev is given
   Scope sc(h, RSL_K_CELL_EXTRAS);
   return hip_check(h,
-                   rsl::launch_cell_extras(h->stream, (const float2*)rds, A, S, C, (const int*)c_frame,
-                                           (const int*)c_rc, (const long long*)ncell_dev, ncell, esprit_scale,
-                                           (const int*)gidx, (const double*)az_table, (float2*)sig_out,
+                   rsl::launch_cell_extras(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell),
+                                           esprit_scale, (const int*)gidx, (const double*)az_table, (float2*)sig_out,
                                            (double*)esprit_deg, (double*)phase, (double*)az_out),
                    "cell_extras");
 }
@@ -565,9 +547,9 @@ int rsl_confidence(rsl_handle h, const void* rds, int A, int S, int C, const voi
     return fail(h, RSL_ERR_INVALID, "rsl_confidence: null pointer");
   Scope sc(h, RSL_K_CONFIDENCE);
   return hip_check(h,
-                   rsl::launch_confidence(h->stream, (const float2*)rds, A, S, C, (const int*)c_frame,
-                                          (const int*)c_rc, n, (const int*)gidx, (const double*)steer_c128,
-                                          (const double*)steer_phase, (double*)conf),
+                   rsl::launch_confidence(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, nullptr, n),
+                                          (const int*)gidx, (const double*)steer_c128, (const double*)steer_phase,
+                                          (double*)conf),
                    "confidence");
 }
 
@@ -649,8 +631,6 @@ int rsl_bvls(rsl_handle h, const void* pos, const void* ang, long long n, const 
                                        ridge, (const double*)lo, (const double*)hi, (double*)out),
                    "bvls");
 }
-
-}  // extern "C"
 
 int rsl_associate(rsl_handle h, const void* cur_xy, int nc, const void* prev_xy, int np, double thr, void* scratch,
                   void* match, void* dist) {
@@ -905,3 +885,5 @@ int rsl_esprit_subspace(rsl_handle h, const void* sigs, long long n, int M, int 
                                                (double*)deg),
                    "esprit_subspace");
 }
+
+}  // extern "C"

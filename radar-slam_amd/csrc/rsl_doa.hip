@@ -17,18 +17,29 @@
 #include <cstdlib>
 
 #include "rsl_common.h"
+#include "rsl_doa_common.h"
 #include "rsl_internal.h"
 
 namespace rsl {
 
-// Loads the B operand (unit-normalised [Re; Im] signature column) of one 16-cell tile for this lane:
+// The f32 steering operand of a workgroup: copied to LDS where the launcher found that it fits (use_lds), else read
+// through the caches.
+RSL_DEV const float4* stage_table(const float4* __restrict__ steer, int nvec, int use_lds, float4* sst) {
+  if (!use_lds) return steer;
+  for (int x = threadIdx.x; x < nvec; x += 256) sst[x] = steer[x];
+  __syncthreads();
+  return sst;
+}
+
+// Loads the B operand (the [Re; Im] signature column, not yet normalised) of one 16-cell tile for this lane:
 // lane (q, jj) holds S'[k = 4 s + q][cell jj], s < KS.  FAST: A == 2*KS, so the two complex loads for
 // antennas q + 4s' (s' < KS/2) give both the real (slot s') and imaginary (slot s' + KS/2) parts.
 template <int KS, bool FAST>
-RSL_DEV void load_sig(const float2* __restrict__ rds, const int* __restrict__ cfr, const int* __restrict__ crc,
-                      long long c, bool ok, int A, int q, size_t plane, size_t fstride, float (&b)[KS]) {
-  const float2* base = rds;
-  if (ok) base = rds + (size_t)cfr[c] * fstride + crc[c];
+RSL_DEV void load_sig(const CellList& cl, long long c, bool ok, int q, float (&b)[KS]) {
+  const size_t plane = cl.plane();
+  const int A = cl.A;
+  const float2* base = cl.rds;
+  if (ok) base = cl.sig(c);
   if constexpr (FAST) {
 #pragma unroll
     for (int s = 0; s < KS / 2; ++s) {
@@ -52,6 +63,49 @@ RSL_DEV void load_sig(const float2* __restrict__ rds, const int* __restrict__ cf
   }
 }
 
+// The NCT 16-cell tiles of chunk ch (cells 16 NCT ch ...), lane (q, jj).
+template <int KS, bool FAST, int NCT>
+RSL_DEV void load_chunk(const CellList& cl, long long ch, long long ncell, int q, int jj, float (&nb)[NCT][KS]) {
+#pragma unroll
+  for (int t2 = 0; t2 < NCT; ++t2) {
+    const long long c = ch * (16 * NCT) + t2 * 16 + jj;
+    load_sig<KS, FAST>(cl, c, c < ncell, q, nb[t2]);
+  }
+}
+
+// b = the loaded column nb scaled to unit norm (angle_estimation.py:86-88; a zero signature stays zero).  Returns the
+// power of the raw signature.
+template <int KS>
+RSL_DEV float normalise(float (&b)[KS]) {
+  float acc = 0.f;
+#pragma unroll
+  for (int s = 0; s < KS; ++s) acc = fmaf(b[s], b[s], acc);
+  acc += __shfl_xor(acc, 16);
+  acc += __shfl_xor(acc, 32);
+  const float sc = acc > 0.f ? 1.0f / sqrtf(acc) : 1.0f;
+#pragma unroll
+  for (int s = 0; s < KS; ++s) b[s] *= sc;
+  return acc;
+}
+
+// Merges the top-2 of the four lanes (q = 0..3) that scanned one cell's grid points: the larger key, on equal keys
+// the lower grid index (np.argmax's first index); `with` travels with the winner where CARRY.
+template <bool CARRY>
+RSL_DEV void merge_top2(float& best, float& second, int& bidx, float& with) {
+#pragma unroll
+  for (int off = 16; off <= 32; off <<= 1) {
+    const float ob = __shfl_xor(best, off), os = __shfl_xor(second, off);
+    const int oi = __shfl_xor(bidx, off);
+    float ow = 0.f;
+    if constexpr (CARRY) ow = __shfl_xor(with, off);
+    const bool take = (ob > best) | ((ob == best) & (oi < bidx));
+    second = fmaxf(fmaxf(second, os), take ? best : ob);
+    best = take ? ob : best;
+    bidx = take ? oi : bidx;
+    if constexpr (CARRY) with = take ? ow : with;
+  }
+}
+
 // Ambiguity bound of the f32 scans (relative top-2 gap): the [Re; Im] products are exact fp32 fmaf chains of <= 32
 // terms, so P = re^2 + im^2 is within a few fp32 ulps of the fp64 value of the same fp32 signature; a cell whose
 // best grid value is not this far above every other one (or, MUSIC, whose maximum is within rounding of M, where
@@ -65,41 +119,27 @@ RSL_DEV int mark_amb(int g, float best, float second, bool music, float Mf) {
   return amb ? -1 : g;  // k_doa_fixup code 0: the whole grid
 }
 
-// One wave = 32 cells (two 16-column MFMA tiles) per pass over all grid tiles; the next pass's signature
-// loads are issued before the current pass's MFMAs (software prefetch).  Grid = resident workgroups only
-// (occupancy query), grid-striding over 32-cell chunks, so no tail wave of late workgroups.
-template <int KS, bool FAST, bool MUSIC, bool SPEC, bool GMAX>
-__global__ __launch_bounds__(256) void k_doa_scan(const float2* __restrict__ rds, int A, int S, int C,
-                                                  const int* __restrict__ cfr, const int* __restrict__ crc,
-                                                  const long long* __restrict__ ncell_dev, long long ncell_host,
-                                                  const float4* __restrict__ steer, int ntiles, int G, int use_lds,
-                                                  int* __restrict__ out_idx, float* __restrict__ out_gmax,
-                                                  float* __restrict__ out_spec, long long spec_ld) {
+// The spectrum-writing scan.  One wave = 32 cells (two 16-column MFMA tiles) per pass over all grid tiles; the next
+// pass's signature loads are issued before the current pass's MFMAs (software prefetch).  Grid = resident workgroups
+// only (occupancy query), grid-striding over 32-cell chunks, so no tail wave of late workgroups.
+template <int KS, bool FAST, bool MUSIC, bool GMAX>
+__global__ __launch_bounds__(256) void k_doa_scan(CellList cl, const float4* __restrict__ steer, int ntiles, int G,
+                                                  int use_lds, int* __restrict__ out_idx,
+                                                  float* __restrict__ out_gmax, float* __restrict__ out_spec,
+                                                  long long spec_ld) {
   constexpr int KSG = (KS + 3) / 4;
   extern __shared__ float4 sst[];
-  __shared__ float4 sstage[SPEC ? 4 * 64 : 1];  // per wave: one tile's 8 grid points x 32 cells (grid-major stores)
-  const float4* st = steer;
-  if (use_lds) {
-    for (int x = threadIdx.x; x < ntiles * KSG * 64; x += 256) sst[x] = steer[x];
-    __syncthreads();
-    st = sst;
-  }
-  const long long ncell = list_count(ncell_dev, ncell_host);
+  __shared__ float4 sstage[4 * 64];  // per wave: one tile's 8 grid points x 32 cells (grid-major stores)
+  const float4* st = stage_table(steer, ntiles * KSG * 64, use_lds, sst);
+  const long long ncell = cl.count();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = lane >> 4, jj = lane & 15;
-  const size_t plane = (size_t)S * C, fstride = (size_t)A * plane;
-  const float Mf = (float)A;
+  const float Mf = (float)cl.A;
   const long long nch = (ncell + 31) >> 5;
   const long long stride = (long long)gridDim.x * 4;
   long long ch = (long long)blockIdx.x * 4 + wave;
   float nb[2][KS];
-  if (ch < nch) {
-#pragma unroll
-    for (int t2 = 0; t2 < 2; ++t2) {
-      const long long c = ch * 32 + t2 * 16 + jj;
-      load_sig<KS, FAST>(rds, cfr, crc, c, c < ncell, A, q, plane, fstride, nb[t2]);
-    }
-  }
+  if (ch < nch) load_chunk<KS, FAST>(cl, ch, ncell, q, jj, nb);
   for (; ch < nch; ch += stride) {
     float b[2][KS];
     float pz[2];
@@ -109,28 +149,13 @@ __global__ __launch_bounds__(256) void k_doa_scan(const float2* __restrict__ rds
     for (int t2 = 0; t2 < 2; ++t2) {
       cidx[t2] = ch * 32 + t2 * 16 + jj;
       ok[t2] = cidx[t2] < ncell;
-      float acc = 0.f;
 #pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        b[t2][s] = nb[t2][s];
-        acc = fmaf(b[t2][s], b[t2][s], acc);
-      }
-      acc += __shfl_xor(acc, 16);
-      acc += __shfl_xor(acc, 32);
-      pz[t2] = acc;
-      const float sc = acc > 0.f ? 1.0f / sqrtf(acc) : 1.0f;  // angle_estimation.py:86-88
-#pragma unroll
-      for (int s = 0; s < KS; ++s) b[t2][s] *= sc;
+      for (int s = 0; s < KS; ++s) b[t2][s] = nb[t2][s];
+      pz[t2] = normalise<KS>(b[t2]);
     }
     // prefetch the next chunk's signatures while this chunk's scan runs
     const long long nx = ch + stride;
-    if (nx < nch) {
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2) {
-        const long long c = nx * 32 + t2 * 16 + jj;
-        load_sig<KS, FAST>(rds, cfr, crc, c, c < ncell, A, q, plane, fstride, nb[t2]);
-      }
-    }
+    if (nx < nch) load_chunk<KS, FAST>(cl, nx, ncell, q, jj, nb);
     float best[2] = {-INFINITY, -INFINITY}, second[2] = {-INFINITY, -INFINITY};
     float bestg[2] = {0.f, 0.f};
     int bidx[2] = {0, 0};
@@ -171,62 +196,45 @@ __global__ __launch_bounds__(256) void k_doa_scan(const float2* __restrict__ rds
               second[t2] = fmaxf(second[t2], key);
             }
           }
-          if constexpr (SPEC) {
-            float val = gv;
-            if constexpr (MUSIC) {
-              const float d = (pz[t2] > 0.f) ? Mf - gv : (Mf - 1.f);
-              val = (d > 1e-12f) ? __builtin_amdgcn_rcpf(d) : 0.f;  // angle_estimation.py:149-152 (v_rcp_f32: 1 ulp)
-            }
-            if (spec_ld != 0) {
-              // grid-major / cell-blocked: stage the tile (8 grid points x 32 cells) in LDS, stored below as 128-B runs
-              reinterpret_cast<float*>(sstage + wave * 64)[(2 * q + h) * 32 + t2 * 16 + jj] = val;
-            } else if (ok[t2] && g < G) {  // cell-major [n][G] (the reference's per-target spectrum rows)
-              out_spec[(size_t)cidx[t2] * G + g] = val;
-            }
+          float val = gv;
+          if constexpr (MUSIC) {
+            const float d = (pz[t2] > 0.f) ? Mf - gv : (Mf - 1.f);
+            val = (d > 1e-12f) ? __builtin_amdgcn_rcpf(d) : 0.f;  // angle_estimation.py:149-152 (v_rcp_f32: 1 ulp)
+          }
+          if (spec_ld != 0) {
+            // grid-major / cell-blocked: stage the tile (8 grid points x 32 cells) in LDS, stored below as 128-B runs
+            reinterpret_cast<float*>(sstage + wave * 64)[(2 * q + h) * 32 + t2 * 16 + jj] = val;
+          } else if (ok[t2] && g < G) {  // cell-major [n][G] (the reference's per-target spectrum rows)
+            out_spec[(size_t)cidx[t2] * G + g] = val;
           }
         }
       }
-      if constexpr (SPEC) {
-        if (spec_ld != 0) {
-          __builtin_amdgcn_wave_barrier();
-          const int r = lane >> 3, c4 = lane & 7;  // grid point 8 t + r, cells 4 c4 .. 4 c4 + 3 of the chunk
-          const float4 v = sstage[wave * 64 + r * 8 + c4];
-          __builtin_amdgcn_wave_barrier();
-          const int g = 8 * t + r;
-          const long long c0 = ch * 32 + 4 * c4;
-          if (g < G && spec_ld < 0) {
-            // cell-blocked [ceil(n / 32)][G][32]: a tile is one contiguous 1 KiB run, a pass one 46 KiB block
-            *reinterpret_cast<float4*>(out_spec + ((size_t)ch * G + g) * 32 + 4 * c4) = v;
-          } else if (g < G) {
-            float* dst = out_spec + (size_t)g * spec_ld + c0;
-            if (c0 + 3 < ncell && (spec_ld & 3) == 0) {
-              *reinterpret_cast<float4*>(dst) = v;
-            } else {
-              if (c0 < ncell) dst[0] = v.x;
-              if (c0 + 1 < ncell) dst[1] = v.y;
-              if (c0 + 2 < ncell) dst[2] = v.z;
-              if (c0 + 3 < ncell) dst[3] = v.w;
-            }
+      if (spec_ld != 0) {
+        __builtin_amdgcn_wave_barrier();
+        const int r = lane >> 3, c4 = lane & 7;  // grid point 8 t + r, cells 4 c4 .. 4 c4 + 3 of the chunk
+        const float4 v = sstage[wave * 64 + r * 8 + c4];
+        __builtin_amdgcn_wave_barrier();
+        const int g = 8 * t + r;
+        const long long c0 = ch * 32 + 4 * c4;
+        if (g < G && spec_ld < 0) {
+          // cell-blocked [ceil(n / 32)][G][32]: a tile is one contiguous 1 KiB run, a pass one 46 KiB block
+          *reinterpret_cast<float4*>(out_spec + ((size_t)ch * G + g) * 32 + 4 * c4) = v;
+        } else if (g < G) {
+          float* dst = out_spec + (size_t)g * spec_ld + c0;
+          if (c0 + 3 < ncell && (spec_ld & 3) == 0) {
+            *reinterpret_cast<float4*>(dst) = v;
+          } else {
+            if (c0 < ncell) dst[0] = v.x;
+            if (c0 + 1 < ncell) dst[1] = v.y;
+            if (c0 + 2 < ncell) dst[2] = v.z;
+            if (c0 + 3 < ncell) dst[3] = v.w;
           }
         }
       }
     }
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
-#pragma unroll
-      for (int off = 16; off <= 32; off <<= 1) {
-        const float ob = __shfl_xor(best[t2], off), os = __shfl_xor(second[t2], off);
-        const int oi = __shfl_xor(bidx[t2], off);
-        float og = 0.f;
-        if constexpr (GMAX) og = __shfl_xor(bestg[t2], off);
-        const bool take = ob > best[t2] || (ob == best[t2] && oi < bidx[t2]);  // first index wins (np.argmax)
-        second[t2] = fmaxf(fmaxf(second[t2], os), take ? best[t2] : ob);
-        if (take) {
-          best[t2] = ob;
-          bidx[t2] = oi;
-          if constexpr (GMAX) bestg[t2] = og;
-        }
-      }
+      merge_top2<GMAX>(best[t2], second[t2], bidx[t2], bestg[t2]);
       if (q == 0 && ok[t2]) {
         out_idx[cidx[t2]] = mark_amb(bidx[t2], best[t2], second[t2], MUSIC, Mf);
         if constexpr (GMAX) out_gmax[cidx[t2]] = bestg[t2];
@@ -296,60 +304,32 @@ RSL_DEV void argmax_scan(const float4* __restrict__ st, int ntiles, int G, float
 }
 
 template <int KS, bool FAST, int NCT, bool MUSIC, bool GMAX>
-__global__ __launch_bounds__(256) void k_doa_argmax(const float2* __restrict__ rds, int A, int S, int C,
-                                                    const int* __restrict__ cfr, const int* __restrict__ crc,
-                                                    const long long* __restrict__ ncell_dev, long long ncell_host,
-                                                    const float4* __restrict__ steer, int ntiles, int G, int use_lds,
-                                                    int* __restrict__ out_idx, float* __restrict__ out_gmax) {
+__global__ __launch_bounds__(256) void k_doa_argmax(CellList cl, const float4* __restrict__ steer, int ntiles, int G,
+                                                    int use_lds, int* __restrict__ out_idx,
+                                                    float* __restrict__ out_gmax) {
   constexpr int KSG = (KS + 3) / 4;
   constexpr int CPW = 16 * NCT;  // cells per wave per pass
   extern __shared__ float4 sst[];
-  const float4* st = steer;
-  if (use_lds) {
-    for (int x = threadIdx.x; x < ntiles * KSG * 64; x += 256) sst[x] = steer[x];
-    __syncthreads();
-    st = sst;
-  }
-  const long long ncell = list_count(ncell_dev, ncell_host);
+  const float4* st = stage_table(steer, ntiles * KSG * 64, use_lds, sst);
+  const long long ncell = cl.count();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = lane >> 4, jj = lane & 15;
-  const size_t plane = (size_t)S * C, fstride = (size_t)A * plane;
-  const float Mf = (float)A;
+  const float Mf = (float)cl.A;
   const long long nch = (ncell + CPW - 1) / CPW;
   const long long stride = (long long)gridDim.x * 4;
   long long ch = (long long)blockIdx.x * 4 + wave;
   float nb[NCT][KS];
-  if (ch < nch) {
-#pragma unroll
-    for (int t2 = 0; t2 < NCT; ++t2) {
-      const long long c = ch * CPW + t2 * 16 + jj;
-      load_sig<KS, FAST>(rds, cfr, crc, c, c < ncell, A, q, plane, fstride, nb[t2]);
-    }
-  }
+  if (ch < nch) load_chunk<KS, FAST>(cl, ch, ncell, q, jj, nb);
   for (; ch < nch; ch += stride) {
     float b[NCT][KS];
 #pragma unroll
     for (int t2 = 0; t2 < NCT; ++t2) {
-      float acc = 0.f;
 #pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        b[t2][s] = nb[t2][s];
-        acc = fmaf(b[t2][s], b[t2][s], acc);
-      }
-      acc += __shfl_xor(acc, 16);
-      acc += __shfl_xor(acc, 32);
-      const float sc = acc > 0.f ? 1.0f / sqrtf(acc) : 1.0f;  // angle_estimation.py:86-88
-#pragma unroll
-      for (int s = 0; s < KS; ++s) b[t2][s] *= sc;
+      for (int s = 0; s < KS; ++s) b[t2][s] = nb[t2][s];
+      normalise<KS>(b[t2]);
     }
     const long long nx = ch + stride;
-    if (nx < nch) {
-#pragma unroll
-      for (int t2 = 0; t2 < NCT; ++t2) {
-        const long long c = nx * CPW + t2 * 16 + jj;
-        load_sig<KS, FAST>(rds, cfr, crc, c, c < ncell, A, q, plane, fstride, nb[t2]);
-      }
-    }
+    if (nx < nch) load_chunk<KS, FAST>(cl, nx, ncell, q, jj, nb);
     float best[NCT], second[NCT];
     int bidx[NCT];
     argmax_scan<KS, FAST, NCT, false>(st, ntiles, G, Mf, q, b, best, second, bidx);
@@ -361,15 +341,8 @@ __global__ __launch_bounds__(256) void k_doa_argmax(const float2* __restrict__ r
     }
 #pragma unroll
     for (int t2 = 0; t2 < NCT; ++t2) {
-#pragma unroll
-      for (int off = 16; off <= 32; off <<= 1) {
-        const float ob = __shfl_xor(best[t2], off), os = __shfl_xor(second[t2], off);
-        const int oi = __shfl_xor(bidx[t2], off);
-        const bool take = (ob > best[t2]) | ((ob == best[t2]) & (oi < bidx[t2]));  // first index wins
-        second[t2] = fmaxf(fmaxf(second[t2], os), take ? best[t2] : ob);
-        best[t2] = take ? ob : best[t2];
-        bidx[t2] = take ? oi : bidx[t2];
-      }
+      float none = 0.f;
+      merge_top2<false>(best[t2], second[t2], bidx[t2], none);
       const long long c = ch * CPW + t2 * 16 + jj;
       if (q == 0 && c < ncell) {
         out_idx[c] = mark_amb(bidx[t2], best[t2], second[t2], MUSIC, Mf);
@@ -379,15 +352,10 @@ __global__ __launch_bounds__(256) void k_doa_argmax(const float2* __restrict__ r
   }
 }
 
-template <int KS, bool FAST, bool MUSIC, bool GMAX>
-static hipError_t launch_argmax_t(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                                  const int* c_rc, const long long* ncell_dev, long long ncell_host, const float4* stp,
-                                  int ntiles, int G, int use_lds, size_t lds, int* out_idx, float* out_gmax,
-                                  int max_blocks) {
-  constexpr int NCT = 4;
-  auto kern = k_doa_argmax<KS, FAST, NCT, MUSIC, GMAX>;
-  static int per_cu[2] = {-1, -1};
-  int& occ = per_cu[use_lds ? 1 : 0];
+// Grid of a grid-striding scan kernel: the resident workgroups (occupancy x CUs; occ caches this kernel instance's
+// occupancy query), or the workgroups that cover the cells where the host knows their count and that is fewer.
+template <class K>
+static unsigned resident_blocks(K kern, size_t lds, int& occ, const CellList& cl, int cells_per_block) {
   if (occ < 0) {
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
@@ -397,112 +365,49 @@ static hipError_t launch_argmax_t(hipStream_t st, const float2* rds, int A, int 
   hipGetDevice(&dev);
   hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
   long long blocks = (long long)occ * ncu;
-  if (max_blocks > 0) {
-    const long long need = (max_blocks * 128LL + 16 * NCT * 4 - 1) / (16 * NCT * 4);  // max_blocks was for 128 cells
+  if (!cl.n_dev) {
+    const long long need = (cl.n_host + cells_per_block - 1) / cells_per_block;
     if (blocks > need) blocks = need;
   }
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, rds, A, S, C, c_frame, c_rc, ncell_dev,
-                     ncell_host, stp, ntiles, G, use_lds, out_idx, out_gmax);
-  return hipGetLastError();
+  return (unsigned)(blocks < 1 ? 1 : blocks);
 }
 
-template <int KS, bool FAST, bool MUSIC, bool SPEC, bool GMAX>
-static hipError_t launch_scan_t(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                                const int* c_rc, const long long* ncell_dev, long long ncell_host, const float4* stp,
-                                int ntiles, int G, int use_lds, size_t lds, int* out_idx, float* out_gmax,
-                                float* out_spec, long long spec_ld, int max_blocks) {
-  auto kern = k_doa_scan<KS, FAST, MUSIC, SPEC, GMAX>;
-  static int per_cu[2] = {-1, -1};  // occupancy per CU for the LDS / no-LDS variants
-  int& occ = per_cu[use_lds ? 1 : 0];
-  if (occ < 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
-    occ = nb;
-  }
-  int dev = 0, ncu = 256;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  long long blocks = (long long)occ * ncu;
-  if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, rds, A, S, C, c_frame, c_rc, ncell_dev,
-                     ncell_host, stp, ntiles, G, use_lds, out_idx, out_gmax, out_spec, spec_ld);
-  return hipGetLastError();
-}
-
-template <int KS, bool FAST>
-static hipError_t launch_scan_f(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                                const int* c_rc, const long long* ncell_dev, long long ncell_host, const float4* stp,
-                                int ntiles, int G, int music, int use_lds, size_t lds, int* out_idx, float* out_gmax,
-                                float* out_spec, long long spec_ld, int max_blocks) {
-  const bool spec = out_spec != nullptr, gmax = out_gmax != nullptr;
-#define L(M, SP, GM)                                                                                               \
-  return launch_scan_t<KS, FAST, M, SP, GM>(st, rds, A, S, C, c_frame, c_rc, ncell_dev, ncell_host, stp, ntiles, G, \
-                                            use_lds, lds, out_idx, out_gmax, out_spec, spec_ld, max_blocks)
-  if (music) {
-    if (spec) { if (gmax) L(true, true, true); else L(true, true, false); }
-    else { if (gmax) L(true, false, true); else L(true, false, false); }
-  } else {
-    if (spec) { if (gmax) L(false, true, true); else L(false, true, false); }
-    else { if (gmax) L(false, false, true); else L(false, false, false); }
-  }
-#undef L
-}
-
-hipError_t launch_doa_scan(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                           const int* c_rc, const long long* ncell_dev, long long ncell_host, const float* steer_tab,
-                           int ntiles, int G, int music, int* out_idx, float* out_gmax, float* out_spec,
-                           long long spec_ld, int grid_blocks) {
-  const int KS = (2 * A + 3) / 4;
-  const int KSG = (KS + 3) / 4;
-  const size_t tab_bytes = (size_t)ntiles * KSG * 64 * sizeof(float4);
+hipError_t launch_doa_scan(hipStream_t st, CellList cl, const float* steer_tab, int G, int music, int* out_idx,
+                           float* out_gmax, float* out_spec, long long spec_ld) {
+  if (!cl.n_dev && cl.n_host <= 0) return hipSuccess;
+  const SteerLayout lay = steer_layout(G, cl.A);
+  const size_t tab_bytes = (size_t)lay.f32_floats * sizeof(float);
   const int use_lds = tab_bytes <= 60 * 1024;
   const size_t lds = use_lds ? tab_bytes : 0;
   const float4* stp = reinterpret_cast<const float4*>(steer_tab);
-  const bool fast = (A == 2 * KS);
-  if (!out_spec) {  // argmax-only fast path
-    const bool gm = out_gmax != nullptr;
-#define AM(n, F_)                                                                                                  \
-  return music ? (gm ? launch_argmax_t<n, F_, true, true>(st, rds, A, S, C, c_frame, c_rc, ncell_dev, ncell_host,  \
-                                                          stp, ntiles, G, use_lds, lds, out_idx, out_gmax,         \
-                                                          grid_blocks)                                             \
-                     : launch_argmax_t<n, F_, true, false>(st, rds, A, S, C, c_frame, c_rc, ncell_dev, ncell_host, \
-                                                           stp, ntiles, G, use_lds, lds, out_idx, out_gmax,        \
-                                                           grid_blocks))                                           \
-               : (gm ? launch_argmax_t<n, F_, false, true>(st, rds, A, S, C, c_frame, c_rc, ncell_dev, ncell_host, \
-                                                           stp, ntiles, G, use_lds, lds, out_idx, out_gmax,        \
-                                                           grid_blocks)                                            \
-                     : launch_argmax_t<n, F_, false, false>(st, rds, A, S, C, c_frame, c_rc, ncell_dev,            \
-                                                            ncell_host, stp, ntiles, G, use_lds, lds, out_idx,     \
-                                                            out_gmax, grid_blocks))
-    switch (KS) {
-      case 2: if (fast) AM(2, true); AM(2, false);
-      case 4: if (fast) AM(4, true); AM(4, false);
-      case 6: if (fast) AM(6, true); AM(6, false);
-      case 8: if (fast) AM(8, true); AM(8, false);
-      case 1: AM(1, false);
-      case 3: AM(3, false);
-      case 5: AM(5, false);
-      case 7: AM(7, false);
-      default: return hipErrorInvalidValue;
-    }
-#undef AM
-  }
-#define CASE(n)                                                                                                    \
-  case n:                                                                                                          \
-    if (fast && (n % 2 == 0))                                                                                      \
-      return launch_scan_f<n, (n % 2 == 0)>(st, rds, A, S, C, c_frame, c_rc, ncell_dev, ncell_host, stp, ntiles, G, \
-                                            music, use_lds, lds, out_idx, out_gmax, out_spec, spec_ld,             \
-                                            grid_blocks);                                                          \
-    return launch_scan_f<n, false>(st, rds, A, S, C, c_frame, c_rc, ncell_dev, ncell_host, stp, ntiles, G, music,   \
-                                   use_lds, lds, out_idx, out_gmax, out_spec, spec_ld, grid_blocks);
-  switch (KS) {
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef CASE
+  const int ntiles = lay.ntiles16;
+  const bool fast = cl.A == 2 * lay.ks && lay.ks % 2 == 0;  // A a multiple of 4: load_sig's paired complex loads
+  return with_int<1, 2, 3, 4, 5, 6, 7, 8>(lay.ks, [&](auto ks) {
+    return with_bool(fast, [&](auto fa) {
+      return with_bool(music != 0, [&](auto mu) {
+        return with_bool(out_gmax != nullptr, [&](auto gm) {
+          constexpr int KS = decltype(ks)::value;
+          constexpr bool FAST = decltype(fa)::value, MUSIC = decltype(mu)::value, GMAX = decltype(gm)::value;
+          static int per_cu[2][2] = {{-1, -1}, {-1, -1}};  // occupancy per CU: [argmax / scan][no LDS / LDS table]
+          if constexpr (FAST && KS % 2 != 0) {
+            return hipErrorInvalidValue;  // never: fast has KS even
+          } else if (!out_spec) {  // argmax only
+            constexpr int NCT = 4;
+            auto kern = k_doa_argmax<KS, FAST, NCT, MUSIC, GMAX>;
+            const unsigned blocks = resident_blocks(kern, lds, per_cu[0][use_lds], cl, 4 * 16 * NCT);
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, st, cl, stp, ntiles, G, use_lds, out_idx, out_gmax);
+            return hipGetLastError();
+          } else {
+            auto kern = k_doa_scan<KS, FAST, MUSIC, GMAX>;
+            const unsigned blocks = resident_blocks(kern, lds, per_cu[1][use_lds], cl, 4 * 32);
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, st, cl, stp, ntiles, G, use_lds, out_idx, out_gmax,
+                               out_spec, spec_ld);
+            return hipGetLastError();
+          }
+        });
+      });
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -517,20 +422,16 @@ constexpr int kMaxA = 32;
 
 // NA > 0: antenna count fixed at compile time (registers only); NA == 0: runtime A (<= kMaxA).
 template <int NA>
-__global__ __launch_bounds__(256) void k_cell_extras(const float2* __restrict__ rds, int A_rt, int S, int C,
-                                                     const int* __restrict__ cfr, const int* __restrict__ crc,
-                                                     const long long* __restrict__ ncell_dev, long long ncell_host,
-                                                     double esprit_scale, const int* __restrict__ gidx,
+__global__ __launch_bounds__(256) void k_cell_extras(CellList cl, double esprit_scale, const int* __restrict__ gidx,
                                                      const double* __restrict__ az_table, float2* __restrict__ sig_out,
                                                      double* __restrict__ esprit_deg, double* __restrict__ phase,
                                                      double* __restrict__ az_out) {
   constexpr int MA = NA > 0 ? NA : kMaxA;
-  const int A = NA > 0 ? NA : A_rt;
-  const long long ncell = list_count(ncell_dev, ncell_host);
+  const int A = NA > 0 ? NA : cl.A;
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= ncell) return;
-  const size_t plane = (size_t)S * C;
-  const float2* base = rds + (size_t)cfr[c] * A * plane + crc[c];
+  if (c >= cl.count()) return;
+  const size_t plane = cl.plane();
+  const float2* base = cl.sig(c);
   float2 zf[MA];
 #pragma unroll
   for (int m = 0; m < MA; ++m)
@@ -574,22 +475,19 @@ __global__ __launch_bounds__(256) void k_cell_extras(const float2* __restrict__ 
   }
 }
 
-hipError_t launch_cell_extras(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                              const int* c_rc, const long long* ncell_dev, long long ncell_host, double esprit_scale,
-                              const int* gidx, const double* az_table, float2* sig_out, double* esprit_deg,
-                              double* phase, double* az_out) {
-  if (A > kMaxA || A < 2) return hipErrorInvalidValue;
-  if (ncell_host <= 0) return hipSuccess;
-  const long long nb = (ncell_host + 255) / 256;
-#define GO(NA)                                                                                                   \
-  hipLaunchKernelGGL(k_cell_extras<NA>, dim3((unsigned)nb), dim3(256), 0, st, rds, A, S, C, c_frame, c_rc,      \
-                     ncell_dev, ncell_host, esprit_scale, gidx, az_table, sig_out, esprit_deg, phase, az_out)
-  if (A == 8) GO(8);
-  else if (A == 16) GO(16);
-  else if (A == 4) GO(4);
-  else GO(0);
-#undef GO
-  return hipGetLastError();
+hipError_t launch_cell_extras(hipStream_t st, CellList cl, double esprit_scale, const int* gidx,
+                              const double* az_table, float2* sig_out, double* esprit_deg, double* phase,
+                              double* az_out) {
+  if (cl.A > kMaxA || cl.A < 2) return hipErrorInvalidValue;
+  if (cl.n_host <= 0) return hipSuccess;
+  const long long nb = (cl.n_host + 255) / 256;
+  auto go = [&](auto na) {
+    hipLaunchKernelGGL(k_cell_extras<decltype(na)::value>, dim3((unsigned)nb), dim3(256), 0, st, cl, esprit_scale,
+                       gidx, az_table, sig_out, esprit_deg, phase, az_out);
+    return hipGetLastError();
+  };
+  const bool fixed = cl.A == 4 || cl.A == 8 || cl.A == 16;  // antenna counts with an instance of their own
+  return with_int<0, 4, 8, 16>(fixed ? cl.A : 0, go);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -597,16 +495,15 @@ hipError_t launch_cell_extras(hipStream_t st, const float2* rds, int A, int S, i
 //   0.4 |a^H s|/||s|| + 0.3 exp(-mean |wrap(arg s - arg a)|) + 0.3 min(1, log10(mean p / pct20(p)) / 3)
 // clipped to [0, 1]; percentile is numpy 'linear' (index 0.2 (M-1)).
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_confidence(const float2* __restrict__ rds, int A, int S, int C,
-                                                    const int* __restrict__ cfr, const int* __restrict__ crc,
-                                                    long long n, const int* __restrict__ gidx,
+__global__ __launch_bounds__(256) void k_confidence(CellList cl, const int* __restrict__ gidx,
                                                     const double* __restrict__ steer,  // complex [G][A]
                                                     const double* __restrict__ sphase,  // [G][A] np.angle(a)
                                                     double* __restrict__ conf_out) {
   const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (c >= n) return;
-  const size_t plane = (size_t)S * C;
-  const float2* base = rds + (size_t)cfr[c] * A * plane + crc[c];
+  if (c >= cl.count()) return;
+  const int A = cl.A;
+  const size_t plane = cl.plane();
+  const float2* base = cl.sig(c);
   double sr[kMaxA], si[kMaxA], p[kMaxA];
   double pw = 0.0;
   for (int m = 0; m < A; ++m) {
@@ -665,13 +562,12 @@ __global__ __launch_bounds__(256) void k_confidence(const float2* __restrict__ r
   conf_out[c] = conf;
 }
 
-hipError_t launch_confidence(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                             const int* c_rc, long long n, const int* gidx, const double* steer_c128,
+hipError_t launch_confidence(hipStream_t st, CellList cl, const int* gidx, const double* steer_c128,
                              const double* steer_phase, double* conf_out) {
-  if (A > kMaxA) return hipErrorInvalidValue;
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_confidence, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rds, A, S, C, c_frame, c_rc,
-                     n, gidx, steer_c128, steer_phase, conf_out);
+  if (cl.A > kMaxA) return hipErrorInvalidValue;
+  if (cl.n_host <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_confidence, dim3((unsigned)((cl.n_host + 255) / 256)), dim3(256), 0, st, cl, gidx, steer_c128,
+                     steer_phase, conf_out);
   return hipGetLastError();
 }
 

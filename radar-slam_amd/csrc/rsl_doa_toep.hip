@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "rsl_common.h"
+#include "rsl_doa_common.h"
 #include "rsl_internal.h"
 
 namespace rsl {
@@ -32,8 +33,6 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr float kToepScale = 256.f;
 
-// The Toeplitz B column of one cell: e = [r0, Re r1, Im r1, ..., Re r_{M-1}, Im r_{M-1}, 0...] of the unit-norm
-// signature, scaled by 2^8 (exact), fp32.
 // Autocorrelation of the raw signature, r_k = sum_n s_{n+k} conj(s_n) (k = 0..MA-1; r_0 = |s|^2 real): shared by the
 // Toeplitz column, ESPRIT and (through s) the spatial phase.
 template <int MA>
@@ -54,22 +53,6 @@ RSL_DEV void acf(const float2 (&s)[MA], float (&ar)[MA], float (&ai)[MA]) {
     ar[k] = re;
     ai[k] = im;
   }
-}
-
-// The Toeplitz B column of one cell: e = [r0, Re r1, Im r1, ..., Re r_{M-1}, Im r_{M-1}, 0...] of the unit-norm
-// signature, scaled by 2^8 (exact), fp32.  inv = 2^8 / |s|^2 (0 for a zero signature).
-template <int MA, int KB>
-RSL_DEV void toep_entries(const float (&ar)[MA], const float (&ai)[MA], float inv, float (&e)[16 * KB]) {
-  // angle_estimation.py:86-88 (unit-norm s).  v_rcp_f32 (1 ulp): a common scale of all of a cell's grid values
-  // cannot move its argmax, and the MUSIC degeneracy test has a 1e-4 margin
-  e[0] = ar[0] > 0.f ? kToepScale : 0.f;
-#pragma unroll
-  for (int k = 1; k < MA; ++k) {
-    e[2 * k - 1] = ar[k] * inv;
-    e[2 * k] = ai[k] * inv;
-  }
-#pragma unroll
-  for (int x = 2 * MA - 1; x < 16 * KB; ++x) e[x] = 0.f;
 }
 
 // ESPRIT (angle_estimation.py:178-225) for a full array (A = M) from the autocorrelation: the 2x2 Gram matrix of
@@ -110,24 +93,13 @@ RSL_DEV void esprit_acf(const float2 (&s)[MA], const float (&ar)[MA], const floa
   dd = n0 * (r0 - el2 - el) + n1 * scc + 2.f * (cr * sar - ci * sai);
 }
 
-// fp16 hi/lo split of 8 consecutive entries, packed two halves per dword (4 + 4 dwords).
-RSL_DEV void split8(const float* v, uint4& hi, uint4& lo) {
-  unsigned h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const _Float16 h0 = (_Float16)v[2 * j], h1 = (_Float16)v[2 * j + 1];
-    const _Float16 l0 = (_Float16)(v[2 * j] - (float)h0), l1 = (_Float16)(v[2 * j + 1] - (float)h1);
-    h[j] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
-    l[j] = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
-  }
-  hi = make_uint4(h[0], h[1], h[2], h[3]);
-  lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
-// The same hi/lo split straight from the unscaled autocorrelation, two entries per packed dword pair: entry x of the
-// Toeplitz column is v_x * g_x (v = r0-flag, Re r1, Im r1, ...; g = 1 for the first, inv for the others, 0 past
-// 2 MA - 1), and v_fma_mix{lo,hi}_f16 write the halves in place (hi = f16(v g), lo = f16(v g - hi), both halves of
-// a dword by one instruction each, no shift / or packing).  Values equal to toep_entries + split8.
+// The Toeplitz B column of one cell, e = [r0, Re r1, Im r1, ..., Re r_{M-1}, Im r_{M-1}, 0...] of the unit-norm
+// signature (angle_estimation.py:86-88) scaled by 2^8 (exact), as its fp16 hi/lo split, 8 consecutive entries per
+// uint4 pair (two halves per dword).  Straight from the unscaled autocorrelation: entry x is v_x * g_x (v = r0-flag,
+// Re r1, Im r1, ...; g = 1 for the first, inv = 2^8 / |s|^2 for the others (0 for a zero signature), 0 past 2 MA - 1), and
+// v_fma_mix{lo,hi}_f16 write the halves in place (hi = f16(v g), lo = f16(v g - hi), both halves of a dword by one
+// instruction each, no shift / or packing).  inv comes from v_rcp_f32 (1 ulp): a common scale of all of a cell's grid
+// values cannot move its argmax, and the MUSIC degeneracy test has a 1e-4 margin.
 template <int MA, int KB>
 RSL_DEV void toep_split(const float (&ar)[MA], const float (&ai)[MA], float inv, uint4 (&hi)[2 * KB],
                         uint4 (&lo)[2 * KB]) {
@@ -212,12 +184,6 @@ RSL_DEV void load_sig_at(const float2* __restrict__ rds, int2 fr, int A, size_t 
   }
 }
 
-template <int MA>
-RSL_DEV void load_sig_c(const float2* __restrict__ rds, const int* __restrict__ cfr, const int* __restrict__ crc,
-                        int c, bool ok, int A, size_t plane, size_t fstride, float2 (&s)[MA]) {
-  load_sig_at<MA>(rds, load_cell(cfr, crc, c, ok), A, plane, fstride, s);
-}
-
 // Max of one 32x32 tile's 16 values held by this lane, as signed-integer max3 on the float bits (v_max3_i32):
 // order-preserving for non-negative floats, and a tile max is one of its inputs exactly.  P = |a^H s|^2 >= 0; a
 // rounding-negative value can only lose to a positive one, and a tile whose values are all <= 0 never holds the
@@ -235,12 +201,11 @@ RSL_DEV float tile_max(const floatx16& a, float lo = __int_as_float(INT_MIN)) {
 // Record-tile copy for the lanes that set a new record: 8 v_pk_mov_b32 (64-bit pairs) under the branch's exec mask
 // instead of 16 v_cndmask_b32 on every tile.  Volatile asm also keeps the compiler from speculating the branch into
 // per-value selects.
-template <int NCOPY = 8>  // NCOPY < 8: ablation (timing only)
 RSL_DEV void copy_tile(double (&dst)[8], const floatx16& src) {
   typedef double doublex8 __attribute__((ext_vector_type(8)));
   const doublex8 s = __builtin_bit_cast(doublex8, src);
 #pragma unroll
-  for (int k = 0; k < NCOPY; ++k) asm volatile("v_pk_mov_b32 %0, %1, %1 op_sel:[0,1]" : "=v"(dst[k]) : "v"(s[k]));
+  for (int k = 0; k < 8; ++k) asm volatile("v_pk_mov_b32 %0, %1, %1 op_sel:[0,1]" : "=v"(dst[k]) : "v"(s[k]));
 }
 
 // Ambiguity bound of the f16 hi/lo scan, relative to a cell's maximum: a cell whose best grid value is not at least
@@ -267,13 +232,6 @@ constexpr float kAmbRel = 1e-6f;
 // real gaps of 1e-13..1e-12 as ties.
 constexpr double kTieRel = 1e-13;
 
-// Exact fp64 scan of ONE cell over grid points [g0, g1) by the whole wave (wave-uniform cell c): the key is P if
-// M - P > 1e-12 (MUSIC, angle_estimation.py:149-152) else -1, P for beamforming; first index of the maximum key, as
-// np.argmax (ties within kTieRel).  P = |a^H s|^2 / |s|^2 from the reference's fp64 steering table [G][A].  Lane =
-// (grid point p = lane >> 3 of 8 per step, antenna m = lane & 7, and m + 8 for A > 8): each steering load is one
-// 16-B complex of a row, so a step's 64 lanes read 8 consecutive rows as contiguous 128-B runs (lanes splitting the
-// grid points with a whole row each read 16 lines per instruction: 16x the L2 requests); the sum over the antennas
-// is three xor shuffles inside the 8-lane group.  Returns (index, P at it) on every lane.
 // One wave = 64 cells per pass: lane (n, h) = (l & 31, l >> 5) loads, normalises and owns cell 64 ch + 32 h + n.
 // The two 32-cell halves are the two column tiles of v_mfma_f32_32x32x16_f16 (B: lane holds K rows 8h..8h+7 of
 // column n), so each lane computes the Toeplitz column of its own cell once and swaps the other K half with
@@ -281,28 +239,26 @@ constexpr double kTieRel = 1e-13;
 // over all 64 lanes.  Per grid tile (32 grid points) the two column tiles are two independent accumulator chains.
 template <int MA, int KB, bool MUSIC, bool GMAX, bool EXTRAS, int DBG = 0, int NTC = 0, bool SKEW = false,
           bool SPEC = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA <= 8 ? 4 : (SPEC ? 1 : 3)))) void k_doa_toep(const float2* __restrict__ rds, int A, int S, int C,
-                                                  const int* __restrict__ cfr, const int* __restrict__ crc,
-                                                  const long long* __restrict__ ncell_dev, long long ncell_host,
-                                                  const uint4* __restrict__ ttab, int ntiles, int G,
-                                                  const double* __restrict__ steer64, int* __restrict__ out_idx,
-                                                  float* __restrict__ out_gmax, float esprit_scale, int esprit_clamp,
-                                                  double* __restrict__ out_esprit, double* __restrict__ out_phase,
-                                                  float* __restrict__ out_spec) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA <= 8 ? 4 : (SPEC ? 1 : 3)))) void k_doa_toep(
+    CellList cl, const uint4* __restrict__ ttab, int ntiles, int G, int* __restrict__ out_idx,
+    float* __restrict__ out_gmax, float esprit_scale, int esprit_clamp, double* __restrict__ out_esprit,
+    double* __restrict__ out_phase, float* __restrict__ out_spec) {
   extern __shared__ uint4 tt[];  // the whole Toeplitz operand table (<= 64 KiB)
   __shared__ float sstg[SPEC ? 4 * 512 : 1];  // SPEC: per-wave store stage
-  {
-    const long long nc = list_count(ncell_dev, ncell_host);
-    if ((long long)blockIdx.x * 256 >= nc) return;  // a block past the cells (capacity-sized grids): no table load
-  }
+  if ((long long)blockIdx.x * 256 >= cl.count()) return;  // a block past the cells (capacity-sized grids): no table
   const int nvec = ntiles * KB * 2 * 64;
   for (int x = threadIdx.x; x < nvec; x += 256) tt[x] = ttab[x];
   __syncthreads();
-  const int ncell = (int)list_count(ncell_dev, ncell_host);
+  // the list's fields as locals of their own (32-bit cell count): the pass loop below is register-tuned around them
+  const float2* __restrict__ rds = cl.rds;
+  const int* __restrict__ cfr = cl.frame;
+  const int* __restrict__ crc = cl.rc;
+  const int A = cl.A;
+  const int ncell = (int)cl.count();
   // the wave index is wave-uniform: in an SGPR, the pass index ch and everything derived from it are scalar
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int h = lane >> 5;
-  const size_t plane = (size_t)S * C, fstride = (size_t)A * plane;
+  const size_t plane = cl.plane(), fstride = cl.fstride();
   const int nch = (ncell + 63) >> 6;
   const int stride = (int)gridDim.x * 4;
   int ch = (int)blockIdx.x * 4 + wave;
@@ -321,7 +277,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA <= 8 ? 4
 #pragma unroll
       for (int m = 0; m < MA; ++m) s[m] = make_float2(0.1f * (lane + m), 0.2f * m - lane * 0.01f);
     } else {
-      load_sig_c<MA>(rds, cfr, crc, c, c < ncell, A, plane, fstride, s);
+      load_sig_at<MA>(rds, load_cell(cfr, crc, c, c < ncell), A, plane, fstride, s);
       const int c2 = (ch + stride) * 64 + lane;
       if (ch + stride < nch) nidx = load_cell(cfr, crc, c2, c2 < ncell);
     }
@@ -427,20 +383,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA <= 8 ? 4
         const half8 al = __builtin_bit_cast(half8, tt[(((t * KB + kb) * 2) + 1) * 64 + lane]);
         const half8 x0h = __builtin_bit_cast(half8, b0h[kb]), x0l = __builtin_bit_cast(half8, b0l[kb]);
         const half8 x1h = __builtin_bit_cast(half8, b1h[kb]), x1l = __builtin_bit_cast(half8, b1l[kb]);
-        if constexpr (DBG == 2) {
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            acc0[i] += (float)ah[i & 7] * (float)x0h[(i + 1) & 7];
-            acc1[i] += (float)al[i & 7] * (float)x1l[(i + 3) & 7];
-          }
-        } else {
-          acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, x0h, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, x1h, acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x0l, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x1l, acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x0h, acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x1h, acc1, 0, 0, 0);
-        }
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, x0h, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, x1h, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x0l, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x1l, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x0h, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, x1h, acc1, 0, 0, 0);
       }
     };
     // record tiles: a real branch (exec-masked 64-bit register copies for the lanes that set a record) instead of
@@ -464,8 +412,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA <= 8 ? 4
         second0 = best0;
         best0 = m0;
         set_bt(0, t);
-        if constexpr (DBG == 7) copy_tile<1>(sv0, acc0);
-        else if constexpr (DBG != 1) copy_tile(sv0, acc0);
+        if constexpr (DBG != 1) copy_tile(sv0, acc0);
       } else {
         second0 = fmaxf(second0, m0);
       }
@@ -473,8 +420,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA <= 8 ? 4
         second1 = best1;
         best1 = m1;
         set_bt(16, t);
-        if constexpr (DBG == 7) copy_tile<1>(sv1, acc1);
-        else if constexpr (DBG != 1) copy_tile(sv1, acc1);
+        if constexpr (DBG != 1) copy_tile(sv1, acc1);
       } else {
         second1 = fmaxf(second1, m1);
       }
@@ -531,7 +477,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MA <= 8 ? 4
         }
       }
     };
-      if constexpr (SKEW && NTC > 0 && KB == 1 && (DBG == 0 || DBG == 1 || DBG == 3 || DBG >= 8)) {
+    if constexpr (SKEW && NTC > 0 && KB == 1) {
       // Skewed schedule: the two column tiles' MFMA chains run half a tile apart, so each chain's epilogue (tile max,
       // record test, record copy) issues while the other chain's MFMAs execute instead of waiting for them; the A
       // operands of tile t + 1 are read from LDS during tile t's first epilogue.  Same products and record order.
@@ -729,18 +675,16 @@ constexpr int kFixCells = 2048;
 constexpr int kFixQ = 256 + 8;  // queue entries per wave: a step adds at most 256
 
 template <int MA, bool MUSIC>
-__global__ __launch_bounds__(256) void k_doa_fixup(const float2* __restrict__ rds, int A, int S, int C,
-                                                   const int* __restrict__ cfr, const int* __restrict__ crc,
-                                                   const long long* __restrict__ ncell_dev, long long ncell_host, int G,
-                                                   const double2* __restrict__ steerT, int* __restrict__ out_idx,
-                                                   float* __restrict__ out_gmax) {
+__global__ __launch_bounds__(256) void k_doa_fixup(CellList cl, int G, const double2* __restrict__ steerT,
+                                                   int* __restrict__ out_idx, float* __restrict__ out_gmax) {
   __shared__ int2 q[4][kFixQ];        // (cell - base, marked index)
   __shared__ float2 sig[4][8][MA];    // the signatures of the 8 cells being re-scanned
   __shared__ int qn[4];
-  const long long ncell = list_count(ncell_dev, ncell_host);
+  const long long ncell = cl.count();
+  const int A = cl.A;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long base = ((long long)blockIdx.x * 4 + wave) * kFixCells;
-  const size_t plane = (size_t)S * C, fstride = (size_t)A * plane;
+  const size_t plane = cl.plane();
   const bool al = (reinterpret_cast<size_t>(out_idx) & 15) == 0;
   auto lds_sync = [] {  // this wave's LDS writes visible to its own later LDS reads
     __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -754,7 +698,7 @@ __global__ __launch_bounds__(256) void k_doa_fixup(const float2* __restrict__ rd
         const int e = e0 + (lane >> 3), m = lane & 7;
         if (e < n) {
           const long long cell = base + q[wave][e].x;
-          const float2* sb = rds + (size_t)cfr[cell] * fstride + crc[cell];
+          const float2* sb = cl.sig(cell);
           sig[wave][lane >> 3][m] = m < A ? sb[(size_t)m * plane] : make_float2(0.f, 0.f);
           if constexpr (MA > 8) sig[wave][lane >> 3][m + 8] = m + 8 < A ? sb[(size_t)(m + 8) * plane] : make_float2(0.f, 0.f);
         }
@@ -879,30 +823,31 @@ __global__ __launch_bounds__(256) void k_doa_fixup(const float2* __restrict__ rd
   }
 }
 
-hipError_t launch_doa_fixup(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                            const int* c_rc, const long long* ncell_dev, long long ncell_host, int G, int music,
-                            const double* steerT, int* out_idx, float* out_gmax) {
-  if (A < 1 || A > 16 || G >= (1 << 24) || !steerT) return hipErrorInvalidValue;
+hipError_t launch_doa_fixup(hipStream_t st, CellList cl, int G, int music, const double* steerT, int* out_idx,
+                            float* out_gmax) {
+  if (cl.A < 1 || cl.A > 16 || G >= (1 << 24) || !steerT) return hipErrorInvalidValue;
 #ifdef RSL_DEV_KNOBS
   if (const char* e = getenv("RSL_DOA_NOFIX"))  // measurement only: marked cells keep -1 - code
     if (atoi(e) == 1) return hipSuccess;
 #endif
-  long long fb = (ncell_host + 4LL * kFixCells - 1) / (4LL * kFixCells);  // kFixCells cells per wave
+  long long fb = (cl.n_host + 4LL * kFixCells - 1) / (4LL * kFixCells);  // kFixCells cells per wave
   if (fb < 1) fb = 1;
   // steerT = the transposed fp64 table [A][G], built once with the steering tables (rsl_steer_table_build)
-  auto kern = A <= 8 ? (music ? k_doa_fixup<8, true> : k_doa_fixup<8, false>)
-                     : (music ? k_doa_fixup<16, true> : k_doa_fixup<16, false>);
-  hipLaunchKernelGGL(kern, dim3((unsigned)fb), dim3(256), 0, st, rds, A, S, C, c_frame, c_rc, ncell_dev, ncell_host, G,
-                     reinterpret_cast<const double2*>(steerT), out_idx, out_gmax);
-  return hipGetLastError();
+  return with_int<8, 16>(cl.A <= 8 ? 8 : 16, [&](auto ma) {
+    return with_bool(music != 0, [&](auto mu) {
+      hipLaunchKernelGGL((k_doa_fixup<decltype(ma)::value, decltype(mu)::value>), dim3((unsigned)fb), dim3(256), 0, st,
+                         cl, G, reinterpret_cast<const double2*>(steerT), out_idx, out_gmax);
+      return hipGetLastError();
+    });
+  });
 }
 
-template <int MA, int KB, bool MUSIC, bool GMAX, bool EXTRAS, bool SPEC = false>
-static hipError_t launch_toep_t(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                                const int* c_rc, const long long* ncell_dev, long long ncell_host, const uint4* tab,
-                                int ntiles, int G, const double* steer64, int* out_idx, float* out_gmax,
-                                double esprit_scale, double* out_esprit, double* out_phase, int max_blocks,
-                                float* out_spec = nullptr) {
+template <int MA, bool MUSIC, bool GMAX, bool EXTRAS, bool SPEC>
+static hipError_t launch_toep_t(hipStream_t st, CellList cl, const uint4* tab, const SteerLayout& lay, int G,
+                                const double* steerT, int* out_idx, float* out_gmax, double esprit_scale,
+                                double* out_esprit, double* out_phase, float* out_spec) {
+  constexpr int KB = MA <= 8 ? 1 : 2;  // = lay.kb
+  const int ntiles = lay.nt32;
   auto kern = k_doa_toep<MA, KB, MUSIC, GMAX, EXTRAS, 0, 0, false, SPEC>;
   if constexpr (MA == 8 && !SPEC) {  // the 0.5-degree grid (G = 361: 12 tiles of 32): unrolled tile loop
     // skewed column-tile chains: tools/doa_var_ab.py, one call, 3.77-3.78 vs 3.83-3.87 ms per 2000 cfg2 frames,
@@ -930,9 +875,7 @@ static hipError_t launch_toep_t(hipStream_t st, const float2* rds, int A, int S,
     }
   }
 #endif
-  size_t lds = (size_t)ntiles * KB * 2 * 64 * sizeof(uint4);
-  if (lds > 64 * 1024) return hipErrorInvalidValue;  // caller checks toep_table_fits()
-  (void)max_blocks;
+  size_t lds = lay.toep_bytes;
 #ifdef RSL_DEV_KNOBS
   // RSL_DOA_WGPC: at most this many workgroups per CU (extra dynamic LDS), i.e. waves per SIMD (occupancy study)
   if (const char* e = getenv("RSL_DOA_WGPC")) {
@@ -944,7 +887,7 @@ static hipError_t launch_toep_t(hipStream_t st, const float2* rds, int A, int S,
   // loading the table) with ~8 passes per wave, instead of a persistent grid of resident blocks: measured 1.52-1.56
   // vs 1.71-1.79 ms per 1000 cfg2 frames (4 or 16 passes per wave: no better, tools/ppw_ab.sh).
   constexpr long long ppw = 8;
-  long long blocks = (ncell_host + 256LL * ppw - 1) / (256LL * ppw);
+  long long blocks = (cl.n_host + 256LL * ppw - 1) / (256LL * ppw);
   if (blocks < 1) blocks = 1;
 #ifdef RSL_DEV_KNOBS
   // RSL_DOA_GRID: at most this many workgroups (the pass loop is grid-strided): a persistent share of the CUs, so
@@ -958,73 +901,51 @@ static hipError_t launch_toep_t(hipStream_t st, const float2* rds, int A, int S,
   // (|angle| <= pi) and only the fp32 rounding of pi * scale can; for d < lambda / 2, |x| > 1 gives NaN as in the
   // reference
   const int clamp = esprit_scale * 3.14159265358979323846 <= 1.0 + 1e-9;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, rds, A, S, C, c_frame, c_rc, ncell_dev,
-                     ncell_host, tab, ntiles, G, steer64, out_idx, out_gmax, (float)esprit_scale, clamp, out_esprit,
-                     out_phase, out_spec);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, cl, tab, ntiles, G, out_idx, out_gmax,
+                     (float)esprit_scale, clamp, out_esprit, out_phase, out_spec);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   // the exact re-scan of the marked cells
-  return launch_doa_fixup(st, rds, A, S, C, c_frame, c_rc, ncell_dev, ncell_host, G, MUSIC, steer64, out_idx,
-                          out_gmax);
+  return launch_doa_fixup(st, cl, G, MUSIC, steerT, out_idx, out_gmax);
 }
 
-hipError_t launch_doa_toep(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                           const int* c_rc, const long long* ncell_dev, long long ncell_host, const void* toep_tab,
-                           int ntiles32, int G, int music, const double* steer64, int* out_idx, float* out_gmax,
-                           double esprit_scale, double* out_esprit, double* out_phase, float* out_spec) {
-  if (A < 1 || A > 16 || (ntiles32 & 1) || ncell_host >= (1LL << 31) - 64) return hipErrorInvalidValue;
-  if (!steer64) return hipErrorInvalidValue;  // steerT: the exact fp64 re-scan of ambiguous cells
+hipError_t launch_doa_toep(hipStream_t st, CellList cl, const void* toep_tab, int G, int music, const double* steerT,
+                           int* out_idx, float* out_gmax, double esprit_scale, double* out_esprit, double* out_phase,
+                           float* out_spec) {
+  const int A = cl.A;
+  if (A < 1 || A > 16 || cl.n_host >= (1LL << 31) - 64) return hipErrorInvalidValue;
+  if (!steerT) return hipErrorInvalidValue;  // the exact fp64 re-scan of ambiguous cells
   if ((out_esprit || out_phase) && A < 2) return hipErrorInvalidValue;
-  const long long max_blocks = ncell_dev ? 0 : (ncell_host + 255) / 256;  // 4 waves x 64 cells
-  if (!ncell_dev && ncell_host <= 0) return hipSuccess;
+  if (out_spec && out_gmax) return hipErrorInvalidValue;  // the spectrum-writing scan (cell-blocked layout): no GMAX
+  const SteerLayout lay = steer_layout(G, A);
+  if (!lay.toep_fits) return hipErrorInvalidValue;
+  if (!cl.n_dev && cl.n_host <= 0) return hipSuccess;
   const uint4* tab = reinterpret_cast<const uint4*>(toep_tab);
-  const bool gm = out_gmax != nullptr, ex = out_esprit || out_phase;
-#define ARGS                                                                                                     \
-  st, rds, A, S, C, c_frame, c_rc, ncell_dev, ncell_host, tab, ntiles32, G, steer64, out_idx, out_gmax,          \
-      esprit_scale, out_esprit, out_phase, (int)max_blocks
-#define GO(MA, KB)                                                                                               \
-  if (music) {                                                                                                   \
-    if (gm) return ex ? launch_toep_t<MA, KB, true, true, true>(ARGS) : launch_toep_t<MA, KB, true, true, false>(ARGS); \
-    return ex ? launch_toep_t<MA, KB, true, false, true>(ARGS) : launch_toep_t<MA, KB, true, false, false>(ARGS);     \
-  }                                                                                                              \
-  if (gm) return ex ? launch_toep_t<MA, KB, false, true, true>(ARGS) : launch_toep_t<MA, KB, false, true, false>(ARGS); \
-  return ex ? launch_toep_t<MA, KB, false, false, true>(ARGS) : launch_toep_t<MA, KB, false, false, false>(ARGS);
-  if (out_spec) {  // the spectrum-writing scan (cell-blocked layout), no GMAX
-    if (gm) return hipErrorInvalidValue;
-#define GOS(MA, KB)                                                                                              \
-  if (music) return ex ? launch_toep_t<MA, KB, true, false, true, true>(ARGS, out_spec)                          \
-                       : launch_toep_t<MA, KB, true, false, false, true>(ARGS, out_spec);                        \
-  return ex ? launch_toep_t<MA, KB, false, false, true, true>(ARGS, out_spec)                                    \
-            : launch_toep_t<MA, KB, false, false, false, true>(ARGS, out_spec);
-    if (A <= 8) {
-      GOS(8, 1)
-    }
-    GOS(16, 2)
-#undef GOS
-  }
-  if (A <= 8) {
-    GO(8, 1)
-  }
-  GO(16, 2)
-#undef GO
-#undef ARGS
-}
-
-bool toep_table_fits(int G, int M) {
-  const int KB = M <= 8 ? 1 : 2;
-  int nt = (G + 31) / 32;
-  nt += nt & 1;
-  return (size_t)nt * KB * 2 * 64 * 16 <= 64 * 1024;
+  return with_int<8, 16>(A <= 8 ? 8 : 16, [&](auto ma) {
+    return with_bool(music != 0, [&](auto mu) {
+      return with_bool(out_gmax != nullptr, [&](auto gm) {
+        return with_bool(out_esprit || out_phase, [&](auto ex) {
+          return with_bool(out_spec != nullptr, [&](auto sp) {
+            constexpr bool GMAX = decltype(gm)::value, SPEC = decltype(sp)::value;
+            if constexpr (SPEC && GMAX) {
+              return hipErrorInvalidValue;  // refused above
+            } else {
+              return launch_toep_t<decltype(ma)::value, decltype(mu)::value, GMAX, decltype(ex)::value, SPEC>(
+                  st, cl, tab, lay, G, steerT, out_idx, out_gmax, esprit_scale, out_esprit, out_phase, out_spec);
+            }
+          });
+        });
+      });
+    });
+  });
 }
 
 // Host: Toeplitz operand table in MFMA A-operand order.  Returns 0 if the steering matrix is not a uniform
 // linear array (then only the f32 path applies).  Layout: [tile t][k-block kb][part hi/lo][lane][8 halves],
 // lane l = row (l & 31) of the tile, k = 16 kb + 8 (l >> 5) + j.  Tiles are padded to an even count with
 // copies of row G-1.
-int toep_table_build(const double* steer, int G, int M, uint16_t* out, int* ntiles32_out) {
-  const int KB = M <= 8 ? 1 : 2;
-  int nt = (G + 31) / 32;
-  nt += nt & 1;
-  if (ntiles32_out) *ntiles32_out = nt;
+int toep_table_build(const double* steer, int G, int M, uint16_t* out) {
+  const SteerLayout lay = steer_layout(G, M);
+  const int KB = lay.kb, nt = lay.nt32;
   if (M < 2) return 0;
   // uniformity: a[g][m] = a[g][0] * (a[g][1] conj(a[g][0]))^m, |a| = 1
   for (int g = 0; g < G; ++g) {

@@ -13,6 +13,8 @@ __device__ __forceinline__ long long list_count(const long long* dev, long long 
   return n < cap ? n : cap;
 }
 
+struct CellList;  // rsl_doa_common.h
+
 // K1 tile queues of one handle (rsl_fft.hip): one 2 KiB queue per stream the handle launches K1 on, allocated on the
 // handle's device at that stream's first K1 launch, freed by rf_queues_free (rsl_destroy).
 struct RfQueues;
@@ -67,37 +69,33 @@ hipError_t launch_emit2(hipStream_t st, const unsigned long long* mask, const un
                         const int* cell_row_off, const long long* entry_base, const long long* cell_base,
                         long long entry_cap, long long cell_cap, unsigned* e_coord, int* e_cell, float* e_pdb,
                         int* c_frame, int* c_rc, unsigned* c_amask);
-// K5: steering scan on MFMA (f32 16x16x4), argmax; optional spectrum.
-hipError_t launch_doa_scan(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                           const int* c_rc, const long long* ncell_dev, long long ncell_host, const float* steer_tab,
-                           int ntiles, int G, int music, int* out_idx, float* out_gmax, float* out_spec,
-                           long long spec_ld, int grid_blocks);
-// K5 fast path: Toeplitz-form argmax on f16 MFMA with hi/lo split (rsl_doa_toep.hip).
+// K4..K7, the direction-of-arrival stage.  CellList (the cells of a call) and steer_layout (the sections of the
+// steering table) are in rsl_doa_common.h.
+// K5: steering scan on MFMA (f32 16x16x4), argmax; optional spectrum (spec_ld 0: cell-major [n][G], > 0: grid-major
+// with that leading dimension, < 0: cell-blocked [ceil(n / 32)][G][32]).  steer_tab: section (1) of the table.
+hipError_t launch_doa_scan(hipStream_t st, CellList cl, const float* steer_tab, int G, int music, int* out_idx,
+                           float* out_gmax, float* out_spec, long long spec_ld);
 // Exact fp64 re-scan of the cells a DoA scan marked ambiguous (out_idx < 0), rsl_doa_toep.hip k_doa_fixup.
-hipError_t launch_doa_fixup(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                            const int* c_rc, const long long* ncell_dev, long long ncell_host, int G, int music,
-                            const double* steerT, int* out_idx, float* out_gmax);
-hipError_t launch_doa_toep(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                           const int* c_rc, const long long* ncell_dev, long long ncell_host, const void* toep_tab,
-                           int ntiles32, int G, int music, const double* steerT, int* out_idx, float* out_gmax,
-                           double esprit_scale, double* out_esprit, double* out_phase, float* out_spec = nullptr);
+hipError_t launch_doa_fixup(hipStream_t st, CellList cl, int G, int music, const double* steerT, int* out_idx,
+                            float* out_gmax);
+// K5 fast path: Toeplitz-form argmax on f16 MFMA with hi/lo split (rsl_doa_toep.hip), followed by its fixup.
+// toep_tab: section (2) of the table, where steer_layout(G, A).toep_fits.
+hipError_t launch_doa_toep(hipStream_t st, CellList cl, const void* toep_tab, int G, int music, const double* steerT,
+                           int* out_idx, float* out_gmax, double esprit_scale, double* out_esprit, double* out_phase,
+                           float* out_spec = nullptr);
 // K5 alternative (rsl_ssmusic.hip): forward-backward spatially smoothed MUSIC, up to nmax angles per cell (the
 // estimator is specified at rsl_doa_smoothed in include/rsl.h).  steer c64 [G][L]; 2 <= L <= RSL_SS_MAX_L.
-hipError_t launch_doa_smoothed(hipStream_t st, const float2* rds, int M, int S, int C, const int* c_frame,
-                               const int* c_rc, const long long* ncell_dev, long long ncell, const float2* steer,
-                               int G, int L, int nmax, int num_sources, float rel, int* out_nsrc, int* out_idx,
-                               float* out_den, float* out_eig, float* out_spec);
+hipError_t launch_doa_smoothed(hipStream_t st, CellList cl, const float2* steer, int G, int L, int nmax,
+                               int num_sources, float rel, int* out_nsrc, int* out_idx, float* out_den, float* out_eig,
+                               float* out_spec);
 // Host: builds the Toeplitz operand table; returns 1 if the steering matrix is a uniform linear array.
-int toep_table_build(const double* steer_c128, int G, int M, uint16_t* out, int* ntiles32_out);
-bool toep_table_fits(int G, int M);
+int toep_table_build(const double* steer_c128, int G, int M, uint16_t* out);
 // K4/K6: normalised signature, ESPRIT closed form (fp64), spatial phase, azimuth lookup.
-hipError_t launch_cell_extras(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                              const int* c_rc, const long long* ncell_dev, long long ncell_host, double esprit_scale,
-                              const int* gidx, const double* az_table, float2* sig_out, double* esprit_deg,
-                              double* phase, double* az_out);
+hipError_t launch_cell_extras(hipStream_t st, CellList cl, double esprit_scale, const int* gidx,
+                              const double* az_table, float2* sig_out, double* esprit_deg, double* phase,
+                              double* az_out);
 // K7: robust confidence for (cell, grid index) pairs (fp64).
-hipError_t launch_confidence(hipStream_t st, const float2* rds, int A, int S, int C, const int* c_frame,
-                             const int* c_rc, long long n, const int* gidx, const double* steer_c128,
+hipError_t launch_confidence(hipStream_t st, CellList cl, const int* gidx, const double* steer_c128,
                              const double* steer_phase, double* conf_out);
 // K8: batched bounded / ridge least squares velocity solve, one segment per frame.
 hipError_t launch_velocity(hipStream_t st, const double* az, const int* gidx, const double* az_table, int G,

@@ -27,6 +27,7 @@
 #endif
 #include "../../include/rsl.h"
 #include "rsl_common.h"
+#include "rsl_doa_common.h"
 #include "rsl_internal.h"
 
 namespace rsl {
@@ -72,10 +73,7 @@ RSL_DEV void rr_pair(int t, int r, int& p, int& q) {
 }  // namespace
 
 template <int L>
-__global__ __launch_bounds__(64) void k_doa_smoothed(const float2* __restrict__ rds, int M, int S, int C,
-                                                     const int* __restrict__ c_frame, const int* __restrict__ c_rc,
-                                                     const long long* __restrict__ ncell_dev, long long ncell,
-                                                     const float2* __restrict__ steer, int G, int nmax,
+__global__ __launch_bounds__(64) void k_doa_smoothed(CellList cl, const float2* __restrict__ steer, int G, int nmax,
                                                      int num_sources, float rel, int* __restrict__ out_nsrc,
                                                      int* __restrict__ out_idx, float* __restrict__ out_den,
                                                      float* __restrict__ out_eig, float* __restrict__ out_spec) {
@@ -83,11 +81,11 @@ __global__ __launch_bounds__(64) void k_doa_smoothed(const float2* __restrict__ 
   constexpr int NP = NT / 2;       // pairs per round
   constexpr int NM = L - 1;        // local minima kept per lane = the largest nmax
   __shared__ SsCell<L> cells[kSsCells];
-  const long long n = list_count(ncell_dev, ncell);
+  const long long n = cl.count();
+  const int M = cl.A;
   const int lane = threadIdx.x & (kSsLanes - 1), grp = threadIdx.x / kSsLanes;
   SsCell<L>& sm = cells[grp];
   const int K = M - L + 1;
-  const size_t SC = (size_t)S * C;
   const float fnan = __builtin_nanf("");
 
   for (long long base = (long long)blockIdx.x * kSsCells; base < n; base += (long long)gridDim.x * kSsCells) {
@@ -95,10 +93,7 @@ __global__ __launch_bounds__(64) void k_doa_smoothed(const float2* __restrict__ 
     const bool live = cell < n;
     // 1. signature: one gather of the cell's M values, norm over the group
     float2 x = make_float2(0.f, 0.f);
-    if (live && lane < M) {
-      const int f = c_frame[cell], rc = c_rc[cell];
-      x = rds[((size_t)f * M + lane) * SC + rc];
-    }
+    if (live && lane < M) x = cl.at(cell, lane);
     const float pw = group_sum(x.x * x.x + x.y * x.y);
     const bool ok = live && pw > 0.f;
     const float inv = ok ? 1.f / sqrtf(pw) : 0.f;
@@ -370,41 +365,18 @@ __global__ __launch_bounds__(64) void k_doa_smoothed(const float2* __restrict__ 
   }
 }
 
-template <int L>
-static hipError_t launch_ss(hipStream_t st, const float2* rds, int M, int S, int C, const int* c_frame,
-                            const int* c_rc, const long long* ncell_dev, long long ncell, const float2* steer, int G,
-                            int nmax, int num_sources, float rel, int* out_nsrc, int* out_idx, float* out_den,
-                            float* out_eig, float* out_spec) {
+hipError_t launch_doa_smoothed(hipStream_t st, CellList cl, const float2* steer, int G, int L, int nmax,
+                               int num_sources, float rel, int* out_nsrc, int* out_idx, float* out_den, float* out_eig,
+                               float* out_spec) {
+  if (cl.n_host <= 0) return hipSuccess;
   // one wave of 4 cells per workgroup; a list whose count lives on the device is walked by at most 8192 workgroups
-  long long blocks = (ncell + kSsCells - 1) / kSsCells;
+  long long blocks = (cl.n_host + kSsCells - 1) / kSsCells;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(k_doa_smoothed<L>, dim3((unsigned)blocks), dim3(64), 0, st, rds, M, S, C, c_frame, c_rc,
-                     ncell_dev, ncell, steer, G, nmax, num_sources, rel, out_nsrc, out_idx, out_den, out_eig,
-                     out_spec);
-  return hipGetLastError();
-}
-
-hipError_t launch_doa_smoothed(hipStream_t st, const float2* rds, int M, int S, int C, const int* c_frame,
-                               const int* c_rc, const long long* ncell_dev, long long ncell, const float2* steer,
-                               int G, int L, int nmax, int num_sources, float rel, int* out_nsrc, int* out_idx,
-                               float* out_den, float* out_eig, float* out_spec) {
-  if (ncell <= 0) return hipSuccess;
-#define RSL_SS_CASE(LL)                                                                                          \
-  case LL:                                                                                                       \
-    return launch_ss<LL>(st, rds, M, S, C, c_frame, c_rc, ncell_dev, ncell, steer, G, nmax, num_sources, rel,    \
-                         out_nsrc, out_idx, out_den, out_eig, out_spec)
-  switch (L) {
-    RSL_SS_CASE(2);
-    RSL_SS_CASE(3);
-    RSL_SS_CASE(4);
-    RSL_SS_CASE(5);
-    RSL_SS_CASE(6);
-    RSL_SS_CASE(7);
-    RSL_SS_CASE(8);
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef RSL_SS_CASE
+  return with_int<2, 3, 4, 5, 6, 7, 8>(L, [&](auto l) {
+    hipLaunchKernelGGL(k_doa_smoothed<decltype(l)::value>, dim3((unsigned)blocks), dim3(64), 0, st, cl, steer, G, nmax,
+                       num_sources, rel, out_nsrc, out_idx, out_den, out_eig, out_spec);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace rsl

@@ -44,7 +44,7 @@ def test_tie_tolerance_against_plain_argmax():
     301, whose keys differ by < 1e-12 relative: 1e-12 takes 300, np.argmax and 1e-13 take 301).  The GPU paths are
     held to the 1e-13 rule below, hence to np.argmax on the whole corpus."""
     moved = {}
-    for A in (8, 4, 16):
+    for A in (8, 4, 16, 3, 5, 7, 10, 13, 15):
         for method in ('music', 'beamforming'):
             rs = np.random.RandomState(100 + A)
             grid = O.azimuth_grid()
@@ -54,8 +54,9 @@ def test_tie_tolerance_against_plain_argmax():
             assert (_expected(sig, steer, method) == plain).all(), (A, method)
             w12 = _expected(sig, steer, method, tie=1e-12)
             moved[(A, method)] = [(int(i), int(w12[i]), int(plain[i])) for i in np.nonzero(w12 != plain)[0]]
-    assert moved == {(8, 'music'): [(26, 300, 301)], (8, 'beamforming'): [(26, 300, 301)], (4, 'music'): [],
-                     (4, 'beamforming'): [], (16, 'music'): [], (16, 'beamforming'): []}, moved
+    want = {(A, method): [] for A in (4, 16, 3, 5, 7, 10, 13, 15) for method in ('music', 'beamforming')}
+    want.update({(8, 'music'): [(26, 300, 301)], (8, 'beamforming'): [(26, 300, 301)]})
+    assert moved == want, moved
 
 
 def _signatures(A, grid, rs):
@@ -84,7 +85,7 @@ def _signatures(A, grid, rs):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('A', [8, 4, 16])
+@pytest.mark.parametrize('A', [8, 4, 16, 3, 5, 7, 10, 12, 13, 15])
 @pytest.mark.parametrize('method', ['music', 'beamforming'])
 def test_exact_argmax_every_path(ctx, A, method):
     import rsl

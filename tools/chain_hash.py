@@ -1,6 +1,7 @@
 """SHA-256 of every output of one cfg2 chain batch (RDS, masks, row counts, peak powers, offsets, lists, DoA, ESPRIT,
-phase, velocity) under the library RSL_LIBRARY: equal hashes across two libraries = bit-identical chains.
-GPU box:  [CFG=cfg1|cfg2|cfg5] [F=frames] RSL_LIBRARY=... python tools/chain_hash.py"""
+phase, velocity) and of the DoA paths the chain does not run (f32 scans, spectra, smoothed MUSIC; on the first NDOA
+cells of the chain's list) under the library RSL_LIBRARY: equal hashes across two libraries = bit-identical chains.
+GPU box:  [CFG=cfg1|cfg2|cfg5] [F=frames] [NDOA=cells] RSL_LIBRARY=... python tools/chain_hash.py"""
 import hashlib
 import json
 import os
@@ -8,9 +9,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, 'radar-slam_amd'), ROOT]
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import rsl  # noqa: E402
+from rsl import tables  # noqa: E402
+from rsl.runtime import spectrum_rows  # noqa: E402
 from bench import make_cubes  # noqa: E402
 
 A, C, TC = {'cfg1': (8, 64, 25.6e-6), 'cfg2': (8, 128, 51.2e-6), 'cfg5': (16, 256, 102.4e-6)}[os.environ.get('CFG', 'cfg2')]
@@ -23,9 +27,34 @@ ch.run(cube)
 torch.cuda.synchronize()
 ne, nc = ch.totals()
 out = {}
+
+
+def sha(t):
+    return hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:12]
+
+
 for name, t in (('rds', ch.rds), ('mask', ch.mask), ('row_count', ch.row_count), ('entry_base', ch.offs['entry_base']),
                 ('peak_pow', ch.peak_pow.view(-1)[:ne]), ('e_pdb', ch.lists['e_pdb'][:ne]),
                 ('c_rc', ch.lists['c_rc'][:nc]), ('gidx', ch.gidx[:nc]), ('esprit', ch.ext['esprit'][:nc]),
                 ('phase', ch.ext['phase'][:nc]), ('vel', ch.vel)):
-    out[name] = hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:12]
+    out[name] = sha(t)
+
+# The DoA paths the chain does not run, on (a prefix of) the chain's own cell list: the f32 scans (argmax with gmax; the
+# three spectrum layouts), the Toeplitz cell-blocked spectrum, and the spatially smoothed MUSIC.
+n = min(nc, int(os.environ.get('NDOA', '100003')))
+L = ch.lists
+args = (ch.rds, L['c_frame'], L['c_rc'], ch.steer, ch.method)
+idx, gmax, _ = ctx.doa(*args, n=n, fast=False, want_gmax=True)
+out['f32_idx'], out['f32_gmax'] = sha(idx[:n]), sha(gmax[:n])
+for name, kw in (('f32_spec_cm', {}), ('f32_spec_gm', {'spec_gmajor': True}), ('f32_spec_bl', {'spec_blocked': True}),
+                 ('toep_spec_bl', {'spec_blocked': True, 'fast': True})):
+    idx, _, spec = ctx.doa(*args, n=n, want_spec=True, **{'fast': False, **kw})
+    out[name] = sha(spectrum_rows(spec, n) if 'spec_blocked' in kw else spec)
+    out[name + '_idx'] = sha(idx[:n])
+    del spec
+d = cfg.antenna_spacing or cfg.lambda_c / 2
+steer = tables.steering_matrix(ch.grid, np.arange(A) * d, cfg.lambda_c)
+sub = ctx.steering_sub(steer, tables.default_sub_len(A))
+nsrc, idx, den, _, _ = ctx.doa_smoothed(ch.rds, L['c_frame'], L['c_rc'], sub, n=n)
+out['ss_nsrc'], out['ss_idx'], out['ss_den'] = sha(nsrc[:n]), sha(idx[:n]), sha(den[:n])
 print(json.dumps(out), flush=True)
