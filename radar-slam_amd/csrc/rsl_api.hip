@@ -140,8 +140,9 @@ int rsl_version(void) { return RSL_VERSION; }
 // 1: radix-{2,3,4,5,7,8} Stockham FFT in LDS; 2: any other length up to 4096 (direct DFT fallback); 0: no.
 int rsl_fft_supported(int n) {
   switch (n) {
-    case 8: case 16: case 32: case 64: case 128: case 256: case 512: case 1024: case 2048: case 4096:
-    case 25: case 50: case 100: case 200: case 400: case 800: case 1600:
+#define CASE(n) case n:
+    RSL_FFT_SIZES(CASE)
+#undef CASE
       return 1;
     default:
       return (n >= 1 && n <= 4096) ? 2 : 0;
@@ -283,20 +284,20 @@ int rsl_rds_detect(rsl_handle h, const void* cube, int F, int A, int C_total, in
   int group = 1;
   hipError_t e;
   // packed range spectra between K1 and K2 (6 B per value, each bin's exponent inside its 48-B unit; the tiles fill
-  // the first 3/4 of the c64-sized work buffer the caller provides; wexp is the launchers' packed-path switch)
-  unsigned char* wexp =
-      rsl::work_packed_supported(C, S) ? (unsigned char*)work + (size_t)F * A * C * S * 6 : nullptr;
+  // the first 3/4 of the c64-sized work buffer the caller provides)
+  const bool packed = rsl::work_packed_supported(C, S);
   {
     Scope sc(h, RSL_K_RANGE_FFT);
     e = rsl::launch_range_fft(h->stream, (const float2*)cube, F, A, C_total, chirp0, C, S, (const float2*)table, tS,
-                              dc_removal, (float2*)work, &sup, h->rfq, wexp);
+                              dc_removal, (float2*)work, &sup, h->rfq, packed);
   }
   if (int r = hip_check(h, e, "range_fft")) return r;
   {
     Scope sc(h, RSL_K_DOPPLER_FFT);
-    e = rsl::launch_doppler_detect(h->stream, (const float2*)work, F, A, C, S, tC, (float2*)rds, thr_power, i_lo,
-                                   i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map,
-                                   (float*)peak_pow, &sup, &group, wexp);
+    const rsl::DetectArgs det{thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map,
+                              (float*)peak_pow};
+    e = rsl::launch_doppler_detect(h->stream, (const float2*)work, F, A, C, S, tC, (float2*)rds, det, &sup, &group,
+                                   packed);
   }
   if (peak_pow_group) *peak_pow_group = group;
   return hip_check(h, e, "doppler_detect");
@@ -310,10 +311,9 @@ int rsl_detect(rsl_handle h, const void* rds, int F, int A, int S, int C, double
   if (!rds || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect: null pointer");
   if ((size_t)(18 * (size_t)C * 4) > 64 * 1024) return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect: C too large");
   Scope sc(h, RSL_K_DETECT);
-  return hip_check(h,
-                   rsl::launch_detect(h->stream, (const float2*)rds, F, A, S, C, thr_power, i_lo, i_hi,
-                                      (unsigned long long*)mask, (int*)row_count, (float*)db_map, (float*)peak_pow),
-                   "detect");
+  const rsl::DetectArgs det{thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map,
+                            (float*)peak_pow};
+  return hip_check(h, rsl::launch_detect(h->stream, (const float2*)rds, F, A, S, C, det), "detect");
 }
 
 int rsl_detect_cfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d, int train_r,
@@ -333,10 +333,11 @@ int rsl_detect_cfar(rsl_handle h, const void* rds, int F, int A, int S, int C, i
   if (F == 0) return RSL_OK;
   if (!rds || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: null pointer");
   Scope sc(h, RSL_K_DETECT);
+  const rsl::DetectArgs det{thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map,
+                            (float*)peak_pow};
   return hip_check(h,
                    rsl::launch_detect_cfar(h->stream, (const float2*)rds, F, A, S, C, guard_r, guard_d, train_r,
-                                           train_d, (float)alpha, thr_power, i_lo, i_hi, (unsigned long long*)mask,
-                                           (int*)row_count, (float*)db_map, (float*)peak_pow),
+                                           train_d, (float)alpha, det),
                    "detect_cfar");
 }
 

@@ -5,7 +5,7 @@
 // Cell (i, j) of a (frame, antenna) power map p = |rds|^2 [S, C] is a peak iff
 //   p * n(i) > alpha * sum   (sum over the training cells: |di| <= hr, |dj| <= hd without the guard box |di| <= gr,
 //                             |dj| <= gd; Doppler wraps, range truncates, n(i) = the cells that exist)
-//   and p >= every existing 3x3 neighbour (k_detect's rule), i_lo <= i <= i_hi, (double)p > thr_p.
+//   and p >= every existing 3x3 neighbour (k_detect's rule, rsl_detect_common.h), i_lo <= i <= i_hi, p > thr_f.
 //
 // The training sum is formed by additions only (a cell 100 dB above its neighbours makes "box minus guard box" or a
 // subtracting sliding window wrong by more than the whole noise sum): per row the side sum HS[j] (gd < |dj| <= hd) and
@@ -20,12 +20,11 @@
 //   C  the rows whose last training row has arrived: vertical sum from the rings, decision, ballots, outputs (the
 //      cell's own power is re-read from the RDS, a row the same workgroup streamed hr + RB rows earlier).
 // The RDS is read (R + 2 max(hr, 1)) / R times for the window (1.16 at R = 128, hr = 10) plus the re-read of phase C.
-#include <cstdlib>
-
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 #include "rsl_common.h"
+#include "rsl_detect_common.h"
 #include "rsl_internal.h"
 
 namespace rsl {
@@ -44,7 +43,7 @@ size_t cfar_lds_bytes(int C, int hr, int hd, int RB) {
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ rds, int S, int C, int W, int gr,
-                                                     int gd, int tr, int td, float alpha, double thr_p, int i_lo,
+                                                     int gd, int tr, int td, float alpha, float thr_f, int i_lo,
                                                      int i_hi, int R, int RB,
                                                      unsigned long long* __restrict__ mask,
                                                      int* __restrict__ row_count, float* __restrict__ dbmap,
@@ -114,17 +113,10 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
       const float* up = PW + (size_t)((u - 1) % NP) * PS + hd;
       const float* mid = PW + (size_t)(u % NP) * PS + hd;
       const float* dn = PW + (size_t)((u + 1) % NP) * PS + hd;
+      const int i = ibase + u;
       for (int w = 0; w < W; ++w) {
         const int j = w * 64 + lane;
-        bool pk = false;
-        if (j < C) {
-          const float p = mid[j];
-          const bool hasl = j > 0, hasr = j + 1 < C;
-          float m = fmaxf(up[j], dn[j]);
-          if (hasl) m = fmaxf(m, fmaxf(mid[j - 1], fmaxf(up[j - 1], dn[j - 1])));
-          if (hasr) m = fmaxf(m, fmaxf(mid[j + 1], fmaxf(up[j + 1], dn[j + 1])));
-          pk = p >= m;
-        }
+        const bool pk = j < C && mid[j] >= window_max3(up, mid, dn, j, C, i > 0, i + 1 < S);
         const unsigned long long b = __ballot(pk);
         if (lane == 0) MX[(size_t)(u % NR) * W + w] = b;
       }
@@ -156,15 +148,11 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
             s += src[(size_t)slot * C + j];
             if (++slot == NR) slot = 0;
           }
-          pk = ((mx >> lane) & 1ull) && (p * fn > alpha * s) && ((double)p > thr_p);
+          pk = ((mx >> lane) & 1ull) && (p * fn > alpha * s) && (p > thr_f);
         }
-        if (dbmap && in) dbmap[orow * C + j] = 10.f * log10f(p + 1e-12f);
-        const unsigned long long b = __ballot(pk);
-        if (lane == 0) mask[orow * W + w] = b;
-        if (pk_pow && pk) pk_pow[orow * C + cnt + lanes_below(b)] = p;
-        cnt += __popcll(b);
+        detect_store_word(pk, p, in, orow, w, W, C, mask, dbmap, pk_pow, cnt);
       }
-      if (lane == 0) row_count[orow] = cnt;
+      detect_store_count(orow, cnt, row_count);
     }
     if (end > done) done = end;
   }
@@ -173,8 +161,7 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
 bool detect_cfar_supported(int C, int hr, int hd) { return cfar_lds_bytes(C, hr, hd, 4) <= kCfarLdsMax; }
 
 hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, int gr, int gd, int tr,
-                              int td, float alpha, double thr_p, int i_lo, int i_hi, unsigned long long* mask,
-                              int* row_count, float* dbmap, float* pk_pow) {
+                              int td, float alpha, const DetectArgs& d) {
   if (F <= 0 || A <= 0 || S <= 0 || C <= 0) return hipSuccess;
   const int hr = gr + tr, hd = gd + td;
   const int W = (C + 63) / 64;
@@ -195,7 +182,7 @@ hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, i
   const long long nblk = (long long)F * A * ((S + R - 1) / R);
   if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_detect_cfar, dim3((unsigned)nblk), dim3(256), lds, st, rds, S, C, W, gr, gd, tr, td, alpha,
-                     thr_p, i_lo, i_hi, R, RB, mask, row_count, dbmap, pk_pow);
+                     threshold_as_float(d.thr_p), d.i_lo, d.i_hi, R, RB, d.mask, d.row_count, d.dbmap, d.pk_pow);
   return hipGetLastError();
 }
 

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define RSL_DEV __device__ __forceinline__
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -244,17 +246,27 @@ RSL_DEV long xcd_tile(long b, long n) {
 RSL_DEV constexpr int lp(int x) { return x + (x >> 3); }
 // Padded row length for N points.
 constexpr int lp_row(int N) { return N + (N + 7) / 8; }
-// The same with the padding optional (P = false: plain rows, for kernels whose FFT is not LDS-bound and that
-// need the smaller tile for residency)
-template <bool P>
-RSL_DEV constexpr int lpp(int x) { return P ? x + (x >> 3) : x; }
-template <bool P>
-constexpr int lp_rowp(int N) { return P ? lp_row(N) : N; }
+
+// Rows per workgroup for an N-point FFT held in LDS (~32 KiB of row data).
+constexpr int rows_for(int N) {
+  int r = 4096 / N;
+  if (r < 1) r = 1;
+  if (r > 64) r = 64;
+  return r;
+}
+
+RSL_DEV float2 w32(int k) {                // exp(-2 pi i k / 32), k < 16
+  constexpr float c[16] = {1.f, 0.98078528040323043f, 0.92387953251128674f, 0.83146961230254524f,
+                           0.70710678118654757f, 0.55557023301960229f, 0.38268343236508984f, 0.19509032201612833f,
+                           0.f, -0.19509032201612819f, -0.38268343236508973f, -0.55557023301960196f,
+                           -0.70710678118654746f, -0.83146961230254535f, -0.92387953251128674f, -0.98078528040323043f};
+  return make_float2(c[k], c[(k + 8) & 15] * (k < 8 ? 1.f : -1.f));  // -sin(2 pi k / 32)
+}
 
 // One Stockham autosort stage over ROWS independent rows of N points held in LDS
 // (row stride LD complex, padded positions).  tw[k] = exp(-2 pi i k / N), k < N (fp64-accurate table).
 // In place: every thread reads its butterflies' inputs, the block syncs, then writes.
-template <int N, int R, int NS, int ROWS, int NT, int LD, bool PADTW, bool PAD>
+template <int N, int R, int NS, int ROWS, int NT, int LD, bool PADTW>
 RSL_DEV void fft_stage(float2* buf, const float2* tw, int tid) {
   constexpr int NB = N / R;
   constexpr int TOT = ROWS * NB;
@@ -266,10 +278,10 @@ RSL_DEV void fft_stage(float2* buf, const float2* tw, int tid) {
     if ((TOT % NT) == 0 || idx < TOT) {
       const int row = idx / NB, j = idx - (idx / NB) * NB;
       const float2* src = buf + row * LD;
-      if constexpr (NB % 8 == 0 || !PAD) {  // lp(j + r NB) = lp(j) + r (NB + NB/8): immediate LDS offsets
-        const float2* s0 = src + lpp<PAD>(j);
+      if constexpr (NB % 8 == 0) {  // lp(j + r NB) = lp(j) + r (NB + NB/8): immediate LDS offsets
+        const float2* s0 = src + lp(j);
 #pragma unroll
-        for (int r = 0; r < R; ++r) v[q][r] = s0[r * lpp<PAD>(NB)];
+        for (int r = 0; r < R; ++r) v[q][r] = s0[r * lp(NB)];
       } else {
 #pragma unroll
         for (int r = 0; r < R; ++r) v[q][r] = src[lp(j + r * NB)];
@@ -291,11 +303,7 @@ RSL_DEV void fft_stage(float2* buf, const float2* tw, int tid) {
       Dft<R>::run(v[q]);
       float2* dst = buf + row * LD;
       const int o = (j / NS) * NS * R + k;
-      if constexpr (!PAD) {
-        float2* d0 = dst + o;
-#pragma unroll
-        for (int r = 0; r < R; ++r) d0[r * NS] = v[q][r];
-      } else if constexpr (NS == 1 && (R & (R - 1)) == 0 && (R <= 8 || R % 8 == 0)) {
+      if constexpr (NS == 1 && (R & (R - 1)) == 0 && (R <= 8 || R % 8 == 0)) {
         // o = j R (a multiple of 8 or of R): lp(o + r) = lp(o) + r + r / 8
         float2* d0 = dst + lp(o);
 #pragma unroll
@@ -313,24 +321,39 @@ RSL_DEV void fft_stage(float2* buf, const float2* tw, int tid) {
   __syncthreads();
 }
 
-template <int N, int S, int ROWS, int NT, int LD, bool PADTW, bool PAD>
+template <int N, int S, int ROWS, int NT, int LD, bool PADTW>
 RSL_DEV void fft_run(float2* buf, const float2* tw, int tid) {
   constexpr FftPlan P = make_plan(N);
   if constexpr (S < P.n) {
-    fft_stage<N, P.r[S], P.ns[S], ROWS, NT, LD, PADTW, PAD>(buf, tw, tid);
-    fft_run<N, S + 1, ROWS, NT, LD, PADTW, PAD>(buf, tw, tid);
+    fft_stage<N, P.r[S], P.ns[S], ROWS, NT, LD, PADTW>(buf, tw, tid);
+    fft_run<N, S + 1, ROWS, NT, LD, PADTW>(buf, tw, tid);
   }
 }
 
 // Forward N-point FFT of ROWS rows in LDS (padded positions, see lp()).  Caller must __syncthreads() before.
 // PADTW: the twiddle table is stored at padded positions lp(k) (spreads the strided twiddle reads of the
 // later stages over the LDS banks)
-// PAD = false: rows hold points at plain positions (row stride LD >= N).
-template <int N, int ROWS, int NT, int LD, bool PADTW = false, bool PAD = true>
+template <int N, int ROWS, int NT, int LD, bool PADTW = false>
 RSL_DEV void fft_rows(float2* buf, const float2* tw, int tid) {
   static_assert(make_plan(N).n > 0, "unsupported FFT size");
-  static_assert(LD >= lp_rowp<PAD>(N), "row stride too small for the row layout");
-  fft_run<N, 0, ROWS, NT, LD, PADTW, PAD>(buf, tw, tid);
+  static_assert(LD >= lp_row(N), "row stride too small for the row layout");
+  fft_run<N, 0, ROWS, NT, LD, PADTW>(buf, tw, tid);
+}
+
+// Run-time flag -> template instance: f is a generic lambda that reads the value from its argument's type
+// (decltype(arg)::value) and instantiates only what it names, so a combination that cannot be launched is kept out
+// with `if constexpr` inside f.
+template <class F>
+auto with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// The same for an integer out of a list; hipErrorInvalidValue for a value outside it.
+template <int... Vs, class F>
+hipError_t with_int(int v, F&& f) {
+  hipError_t r = hipErrorInvalidValue;
+  (void)((v == Vs && ((r = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return r;
 }
 
 // ESPRIT closed form (reference angle_estimation.py:178-225) on a unit-norm fp64 signature s (A antennas):

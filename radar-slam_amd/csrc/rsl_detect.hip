@@ -4,21 +4,27 @@
 //   db = 10 log10(|rds|^2 + 1e-12); peak = (maximum_filter(db, 3, mode='reflect') == db) & (db > thr)
 //   & (min_range <= range_m[i] <= max_range); peaks listed antenna -> range -> doppler (np.where order).
 // The 3x3 test runs on fp32 power p (log10 is monotone); 'reflect' boundary duplicates the edge cell,
-// so out-of-range neighbours simply do not take part.  The threshold is evaluated as
-// (double)p > 10^(thr/10) - 1e-12 and the range gate as an index interval, both precomputed in fp64.
+// so out-of-range neighbours simply do not take part (rsl_detect_common.h).  The threshold 10^(thr/10) - 1e-12 and the
+// range gate, an index interval, are precomputed in fp64.
 // Per-antenna 64-bit ballots give one mask word per 64 Doppler cells; a per-frame scan then turns
 // row counts into entry offsets (antenna-major) and union-cell offsets (range-major), and the emit
 // kernel writes both lists in reference order without any sort.
-#include <cstdlib>
-
 #include "rsl_common.h"
+#include "rsl_detect_common.h"
 #include "rsl_internal.h"
 
 namespace rsl {
 
 constexpr int kDetRows = 16;  // shifted range rows per workgroup
 
-__global__ __launch_bounds__(256) void k_detect(const float2* __restrict__ rds, int S, int C, int W, double thr_p,
+// The largest float t <= thr: for a float p, (double)p > thr  <=>  p > t.
+float threshold_as_float(double thr) {
+  float t = (float)thr;
+  if ((double)t > thr) t = nextafterf(t, -INFINITY);
+  return t;
+}
+
+__global__ __launch_bounds__(256) void k_detect(const float2* __restrict__ rds, int S, int C, int W, float thr_f,
                                                 int i_lo, int i_hi, unsigned long long* __restrict__ mask,
                                                 int* __restrict__ row_count, float* __restrict__ dbmap,
                                                 float* __restrict__ pk_pow) {
@@ -32,7 +38,7 @@ __global__ __launch_bounds__(256) void k_detect(const float2* __restrict__ rds, 
   for (int idx = threadIdx.x; idx < (nrows + 2) * C; idx += 256) {
     const int r = idx / C, j = idx - r * C;
     const int i = i0 - 1 + r;
-    pw[idx] = (i >= 0 && i < S) ? cabs2(base[(size_t)i * C + j]) : -1.f;  // -1: outside (no neighbour)
+    pw[idx] = (i >= 0 && i < S) ? cabs2(base[(size_t)i * C + j]) : -1.f;  // outside the map: never read
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -42,50 +48,50 @@ __global__ __launch_bounds__(256) void k_detect(const float2* __restrict__ rds, 
     const float* up = pw + r * C;
     const float* mid = up + C;
     const float* dn = mid + C;
+    const size_t row = (size_t)fa * S + i;
     int cnt = 0;
     for (int w = 0; w < W; ++w) {
       const int j = w * 64 + lane;
+      const bool in = j < C;
+      float p = 0.f;
       bool pk = false;
-      if (j < C) {
-        const float p = mid[j];
-        pk = gate && ((double)p > thr_p);
-        const bool hasl = j > 0, hasr = j + 1 < C;
-        float m = fmaxf(up[j], dn[j]);
-        if (hasl) m = fmaxf(m, fmaxf(mid[j - 1], fmaxf(up[j - 1], dn[j - 1])));
-        if (hasr) m = fmaxf(m, fmaxf(mid[j + 1], fmaxf(up[j + 1], dn[j + 1])));
-        pk = pk && (p >= m);
-        if (dbmap) dbmap[((size_t)fa * S + i) * C + j] = 10.f * log10f(p + 1e-12f);
+      if (in) {
+        p = mid[j];
+        const float m = window_max3(up, mid, dn, j, C, i > 0, i + 1 < S);  // before the tests: its loads go with p's
+        pk = gate && (p > thr_f) && (p >= m);
       }
-      const unsigned long long b = __ballot(pk);
-      if (lane == 0) mask[((size_t)fa * S + i) * W + w] = b;
-      if (pk_pow && pk)  // row-compact peak powers: slot = rank of the peak within its row
-        pk_pow[((size_t)fa * S + i) * C + cnt + lanes_below(b)] = mid[j];
-      cnt += __popcll(b);
+      detect_store_word(pk, p, in, row, w, W, C, mask, dbmap, pk_pow, cnt);
     }
-    if (lane == 0) row_count[(size_t)fa * S + i] = cnt;
+    detect_store_count(row, cnt, row_count);
   }
 }
 
-// Exclusive scan of one value per thread over an NT-thread block (wave shuffles + one LDS round); *total = the sum.
-template <int NT>
-__device__ long long block_exscan(long long v, long long* lds, long long* total) {
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  long long inc = v;
+// Exclusive scan of one value per thread over an NT-thread block (a wave scan + one LDS round over the NT / 64 wave
+// sums in lds); *total = the block's sum.  A caller that scans again through the same lds puts a barrier in between.
+// Every thread of the block must call it.
+template <class T, int NT>
+RSL_DEV T block_exscan(T v, T* lds, T* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  T inc;
+  if constexpr (sizeof(T) == 4) {
+    inc = wave_incl_scan(v);  // DPP
+  } else {
+    inc = v;
 #pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long long u = __shfl_up(inc, d);
-    if (lane >= d) inc += u;
+    for (int d = 1; d < 64; d <<= 1) {
+      const T u = __shfl_up(inc, d);
+      if (lane >= d) inc += u;
+    }
   }
   if (lane == 63) lds[w] = inc;
   __syncthreads();
-  long long base = 0, tot = 0;
+  T base = 0, tot = 0;
 #pragma unroll
   for (int k = 0; k < NT / 64; ++k) {
-    const long long x = lds[k];
-    base += k < w ? x : 0;
+    const T x = lds[k];
+    if (k < w) base += x;
     tot += x;
   }
-  __syncthreads();
   *total = tot;
   return base + inc - v;
 }
@@ -115,7 +121,7 @@ __device__ long long block_scan_global(const int* in, int* out, int n, long long
       const int4 x = in4[q0 + q];
       s += (long long)x.x + x.y + x.z + x.w;
     }
-    long long run = block_exscan<NT>(s, lds, &total);
+    long long run = block_exscan<long long, NT>(s, lds, &total);
     auto put = [&](int q, const int4& x) {
       int4 o;
       o.x = (int)run; run += x.x;
@@ -132,7 +138,7 @@ __device__ long long block_scan_global(const int* in, int* out, int n, long long
   }
   long long s = 0;
   for (int k = b; k < e; ++k) s += in[k];
-  long long run = block_exscan<NT>(s, lds, &total);
+  long long run = block_exscan<long long, NT>(s, lds, &total);
   for (int k = b; k < e; ++k) {
     const int v = in[k];
     out[k] = (int)run;
@@ -202,8 +208,9 @@ __global__ __launch_bounds__(NT) void k_frame_scan(const long long* __restrict__
     sc += frame_counts[2 * k + 1];
   }
   long long tot_e, tot_c;
-  long long re = block_exscan<NT>(se, lds, &tot_e);
-  long long rc = block_exscan<NT>(sc, lds, &tot_c);
+  long long re = block_exscan<long long, NT>(se, lds, &tot_e);
+  __syncthreads();  // lds is reused
+  long long rc = block_exscan<long long, NT>(sc, lds, &tot_c);
   for (int k = b; k < e; ++k) {
     entry_base[k] = re;
     cell_base[k] = rc;
@@ -285,22 +292,6 @@ __global__ __launch_bounds__(256) void k_emit(const float2* __restrict__ rds, co
 constexpr int kEmitCap = 2048;
 constexpr int kEmitU = 4;  // phase-2 items per lane per trip
 
-RSL_DEV int block_exclusive_scan(int v, int* wsum, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int x = wave_incl_scan(v);
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  int pre = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int ws = wsum[k];
-    if (k < wave) pre += ws;
-    total += ws;
-  }
-  return pre + x - v;
-}
-
 // WPE: minimum waves per SIMD the register allocation must allow (0: unconstrained; A/B knob RSL_EMIT_WPE).
 // (Non-temporal entry stores were measured slower: 0.53 vs 0.48 ms per 1000 cfg2 frames.)
 // CELLS = false: an entries-only launch (the cells go to k_emit_cells): no antenna-mask buffer in LDS (14 instead of 22
@@ -366,7 +357,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? W
   if (!valid) m = 0;
   const int cnt = __popcll(m);
   int total;
-  const int loc = block_exclusive_scan(cnt, wsum, total);
+  const int loc = block_exscan<int, 256>(cnt, wsum, &total);
   // entries: peaks of the earlier words of this row (the row's words are lanes lane-w .. lane of this wave)
   const int r0 = loc - __shfl(loc, lane - w);
   if (t == 0) s_first = fst;
@@ -492,7 +483,7 @@ __global__ __launch_bounds__(256) void k_emit_cells(const unsigned long long* __
 #pragma unroll
   for (int aa = 0; aa < MAXA; ++aa) sa[aa] = (unsigned)(ma[aa] >> (16 * sl)) & 0xffffu;
   int total;
-  const int loc = block_exclusive_scan(__popc(sm16), wsum, total);
+  const int loc = block_exscan<int, 256>((int)__popc(sm16), wsum, &total);
   {
     unsigned mm = sm16;
     int o = loc;
@@ -545,56 +536,37 @@ hipError_t launch_emit2(hipStream_t st, const unsigned long long* mask, const un
   const unsigned nb = (unsigned)(nbe + nbc);
   if (cells4) {
     const unsigned nbc4 = (unsigned)(((long long)F * S * W) / kCellWords);
-#define GOC(WW)                                                                                                  \
-  hipLaunchKernelGGL((A <= 8 ? k_emit_cells<WW, 8> : A <= 16 ? k_emit_cells<WW, 16> : k_emit_cells<WW, 32>),      \
-                     dim3(nbc4), dim3(256), 0, st, mask,                                                        \
-                     umask, (long long)F, A, S, C, cell_row_off, cell_base, cell_cap, c_frame, c_rc, c_amask);
-    switch (W) {
-      case 1: GOC(1) break;
-      case 2: GOC(2) break;
-      case 4: GOC(4) break;
-      case 8: GOC(8) break;
-      case 16: GOC(16) break;
-      case 32: GOC(32) break;
-      case 64: GOC(64) break;
-      default: return hipErrorInvalidValue;
-    }
-#undef GOC
-    hipError_t e = hipGetLastError();
+    const hipError_t e = with_int<1, 2, 4, 8, 16, 32, 64>(W, [&](auto w) {
+      constexpr int WW = decltype(w)::value;
+      hipLaunchKernelGGL((A <= 8 ? k_emit_cells<WW, 8> : A <= 16 ? k_emit_cells<WW, 16> : k_emit_cells<WW, 32>),
+                         dim3(nbc4), dim3(256), 0, st, mask, umask, (long long)F, A, S, C, cell_row_off, cell_base,
+                         cell_cap, c_frame, c_rc, c_amask);
+      return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
   }
   // registers capped for 7 waves per SIMD (72 VGPRs, no spill; 7 workgroups per CU as the LDS allows, instead of 6):
   // emit 0.45-0.47 vs 0.46-0.48 ms per 1000 cfg2 frames (tools/cpb.sh); the entries-only instance (cells by
   // k_emit_cells) holds 14 KiB of LDS and is capped for 8 waves per SIMD
   constexpr int EWPE = 8;
-#define GO(WW)                                                                                                   \
-  hipLaunchKernelGGL((cells4 ? k_emit_block<WW, 8, EWPE, false> /* entries only: MAXA unused */                 \
-                             : (A <= 8 ? k_emit_block<WW, 8, 7> : k_emit_block<WW, 32>)),                         \
-                     dim3(nb), dim3(256), 0, st, mask,                                                           \
-                     umask, pk_pow, pk_group, (long long)F, A, S, C, entry_row_off, cell_row_off, entry_base, cell_base,     \
-                     entry_cap, cell_cap, nbe, e_coord, e_cell, e_pdb, c_frame, c_rc, c_amask);
-  switch (W) {
-    case 1: GO(1) break;
-    case 2: GO(2) break;
-    case 4: GO(4) break;
-    case 8: GO(8) break;
-    case 16: GO(16) break;
-    case 32: GO(32) break;
-    case 64: GO(64) break;
-    default: return hipErrorInvalidValue;
-  }
-#undef GO
-  return hipGetLastError();
+  return with_int<1, 2, 4, 8, 16, 32, 64>(W, [&](auto w) {
+    constexpr int WW = decltype(w)::value;
+    hipLaunchKernelGGL((cells4 ? k_emit_block<WW, 8, EWPE, false> /* entries only: MAXA unused */
+                               : (A <= 8 ? k_emit_block<WW, 8, 7> : k_emit_block<WW, 32>)),
+                       dim3(nb), dim3(256), 0, st, mask, umask, pk_pow, pk_group, (long long)F, A, S, C,
+                       entry_row_off, cell_row_off, entry_base, cell_base, entry_cap, cell_cap, nbe, e_coord, e_cell,
+                       e_pdb, c_frame, c_rc, c_amask);
+    return hipGetLastError();
+  });
 }
 
-hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S, int C, double thr_p, int i_lo,
-                         int i_hi, unsigned long long* mask, int* row_count, float* dbmap, float* pk_pow) {
+hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S, int C, const DetectArgs& d) {
   if (F <= 0 || A <= 0 || S <= 0 || C <= 0) return hipSuccess;
   const int W = (C + 63) / 64;
   const long nblk = (long)F * A * ((S + kDetRows - 1) / kDetRows);
   const size_t lds = sizeof(float) * (kDetRows + 2) * (size_t)C;
-  hipLaunchKernelGGL(k_detect, dim3((unsigned)nblk), dim3(256), lds, st, rds, S, C, W, thr_p, i_lo, i_hi, mask,
-                     row_count, dbmap, pk_pow);
+  hipLaunchKernelGGL(k_detect, dim3((unsigned)nblk), dim3(256), lds, st, rds, S, C, W, threshold_as_float(d.thr_p),
+                     d.i_lo, d.i_hi, d.mask, d.row_count, d.dbmap, d.pk_pow);
   return hipGetLastError();
 }
 

@@ -1,10 +1,7 @@
 // rsl_doa_common.h — what the direction-of-arrival kernels (rsl_doa.hip, rsl_doa_toep.hip, rsl_ssmusic.hip), their
-// launchers and the C-ABI layer share: the cell list, the steering table's layout, and the dispatch of run-time flags
-// to template instances.
+// launchers and the C-ABI layer share: the cell list and the steering table's layout.
 #pragma once
 #include <hip/hip_runtime.h>
-
-#include <type_traits>
 
 #include "rsl_common.h"
 #include "rsl_internal.h"
@@ -71,22 +68,6 @@ inline SteerLayout steer_layout(int G, int M) {
   l.t64_offset = l.f32_floats + l.toep_floats;
   l.total_floats = l.t64_offset + 4LL * G * M;
   return l;
-}
-
-// Run-time flag -> template instance: f is a generic lambda that reads the value from its argument's type
-// (decltype(arg)::value) and instantiates only what it names, so a combination that cannot be launched is kept out
-// with `if constexpr` inside f.
-template <class F>
-auto with_bool(bool b, F&& f) {
-  return b ? f(std::true_type{}) : f(std::false_type{});
-}
-
-// The same for an integer out of a list; hipErrorInvalidValue for a value outside it.
-template <int... Vs, class F>
-hipError_t with_int(int v, F&& f) {
-  hipError_t r = hipErrorInvalidValue;
-  (void)((v == Vs && ((r = f(std::integral_constant<int, Vs>{})), true)) || ...);
-  return r;
 }
 
 }  // namespace rsl

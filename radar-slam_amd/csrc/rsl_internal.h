@@ -15,16 +15,24 @@ __device__ __forceinline__ long long list_count(const long long* dev, long long 
 
 struct CellList;  // rsl_doa_common.h
 
+// The lengths with a Stockham FFT in LDS (every other length up to 4096 takes the direct DFT): the size switches of
+// launch_range_fft / launch_doppler_fft and rsl_fft_supported.
+#define RSL_FFT_SIZES(X) \
+  X(8) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(25) X(50) X(100) X(200) X(400) X(800) X(1600)
+
 // K1 tile queues of one handle (rsl_fft.hip): one 2 KiB queue per stream the handle launches K1 on, allocated on the
 // handle's device at that stream's first K1 launch, freed by rf_queues_free (rsl_destroy).
 struct RfQueues;
 RfQueues* rf_queues_new(int device);
 void rf_queues_free(RfQueues* s);
+// An integer knob of the development build (make dev), by its environment name: 0 when unset, and always 0 in the
+// product build.
+int dev_knob(const char* name);
 // K1: dechirp * window (table), range FFT (S points), DC bin zeroing.
 // cube c64 [F, A, Ct, S] (chirps chirp0 .. chirp0+C-1 used) -> work c64 [F, A, C, S]
 hipError_t launch_range_fft(hipStream_t st, const float2* cube, int F, int A, int Ct, int chirp0, int C, int S,
                             const float2* table, const float2* tw_S, int dc, float2* work, bool* supported,
-                            RfQueues* queues, unsigned char* wexp = nullptr);
+                            RfQueues* queues, bool packed = false);
 // K2: Doppler FFT (C points) + fftshift on both axes, transposed store.
 // work c64 [F, A, C, S] -> rds c64 [F, A, S, C]
 hipError_t launch_doppler_fft(hipStream_t st, const float2* work, int F, int A, int C, int S, const float2* tw_C,
@@ -34,24 +42,32 @@ hipError_t launch_doppler_fft(hipStream_t st, const float2* work, int F, int A, 
 // block's KB range bins tile both halves of S.
 bool doppler_detect_supported(int C, int S);
 float threshold_as_float(double thr);  // largest float t <= thr
+// What a detector is asked and where it answers, as the launcher layers hand it down (host side only: the kernels take
+// the members as separate `__restrict__` arguments).  thr_p: power threshold (the kernels compare against its
+// threshold_as_float); i_lo..i_hi: range gate; mask u64 [F, A, S, W], row_count [F, A, S], optional dbmap, pk_pow.
+struct DetectArgs {
+  double thr_p;
+  int i_lo, i_hi;
+  unsigned long long* mask;
+  int* row_count;
+  float* dbmap;
+  float* pk_pow;
+};
+// *pk_group: the rows per group of the compacted peak powers (1 = row-compact).
 hipError_t launch_doppler_detect(hipStream_t st, const float2* work, int F, int A, int C, int S, const float2* tw_C,
-                                 float2* rds, double thr_p, int i_lo, int i_hi, unsigned long long* mask,
-                                 int* row_count, float* dbmap, float* pk_pow, bool* supported, int* pk_group,
-                                 const unsigned char* wexp = nullptr);
-// wexp non-null (both launches): `work` holds packed rows (rsl_fft.hip pk_pack16: 6 B per value in 24 KiB tiles, each
-// bin's int8 exponent inside its 48-B unit; the pointer is only the switch, nothing is stored there) -- only where
-// work_packed_supported(C, S).
+                                 float2* rds, const DetectArgs& det, bool* supported, int* pk_group,
+                                 bool packed = false);
+// packed (both launches): `work` holds packed rows (rsl_packed.h: 6 B per value in 24 KiB tiles, each bin's int8
+// exponent inside its 48-B unit) -- only where work_packed_supported(C, S).
 bool work_packed_supported(int C, int S);
 // K3: 3x3 local max (reflect), threshold, range gate -> per-antenna bit masks + row counts.
-hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S, int C, double thr_p, int i_lo,
-                         int i_hi, unsigned long long* mask, int* row_count, float* dbmap, float* pk_pow);
+hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S, int C, const DetectArgs& det);
 // K3 alternative (rsl_cfar.hip): 2-D cell-averaging CFAR (guard gr x gd, training tr x td half-sizes; Doppler wraps,
 // range truncates) + 3x3 local max + range gate + power floor -> the same outputs as launch_detect, peak_pow
 // row-compact.  detect_cfar_supported: the rings of a window (hr, hd) = (gr + tr, gd + td) fit the CU's LDS at C.
 bool detect_cfar_supported(int C, int hr, int hd);
 hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, int gr, int gd, int tr,
-                              int td, float alpha, double thr_p, int i_lo, int i_hi, unsigned long long* mask,
-                              int* row_count, float* dbmap, float* pk_pow);
+                              int td, float alpha, const DetectArgs& det);
 // Per-frame offsets of peak entries (antenna-major) and union cells (range-major).
 hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const int* row_count, int F, int A, int S,
                           int C, int* entry_row_off, int* cell_row_off, int* cell_row_cnt, long long* entry_base,
@@ -148,9 +164,6 @@ hipError_t launch_pose_align(hipStream_t st, const double* est, const double* gt
 hipError_t launch_pose_rte(hipStream_t st, const double* aligned, const double* gt, long n, const double* len,
                            int nlen, double* scratch, double* err, unsigned long long* cnt, double* stats);
 
-}  // namespace rsl
-
-namespace rsl {
 hipError_t launch_preprocess_rows(hipStream_t st, const float2* in, long rows, int S, const float2* table, int dc,
                                   float2* out);
 hipError_t launch_phase_model(hipStream_t st, const double* pos, const double* ang, long n, const double* x, double k,

@@ -80,16 +80,15 @@ def range_doppler(frames, table: np.ndarray, *, chirp0=0, num_chirps=None, dc_re
 
 
 # -- a8 -------------------------------------------------------------------------------------------------
-def detect_peaks(rds, *, threshold_db=-20.0, i_lo=0, i_hi=1 << 30, want_db=True, ctx: Optional[Context] = None):
-    """rds [A, S, C] -> (antenna, range_bin, doppler_bin, power_db) arrays in reference order + dB map."""
+def _detect_peaks(rds, ctx: Optional[Context], want_db, detector):
+    """The peak dictionary of detect_peaks from ``detector(c, d)`` -> (mask, row_count, dB map) on the device RDS d."""
     c = _ctx(ctx)
-    torch = c.torch
     d = as_dev_c64(c, rds)
     if d.dim() == 3:
         d = d.unsqueeze(0)
     d = d.contiguous()
     F, A, S, C = d.shape
-    mask, rc, db = c.detect(d, tables.power_threshold(threshold_db), i_lo, i_hi, want_db=want_db)
+    mask, rc, db = detector(c, d)
     offs = c.offsets(mask, rc, C)
     ne = int(offs['entry_base'][F].item())
     nc = int(offs['cell_base'][F].item())
@@ -103,6 +102,12 @@ def detect_peaks(rds, *, threshold_db=-20.0, i_lo=0, i_hi=1 << 30, want_db=True,
         if F == 1:
             res['power_spectrum_db'] = res['power_spectrum_db'][0]
     return res
+
+
+def detect_peaks(rds, *, threshold_db=-20.0, i_lo=0, i_hi=1 << 30, want_db=True, ctx: Optional[Context] = None):
+    """rds [A, S, C] -> (antenna, range_bin, doppler_bin, power_db) arrays in reference order + dB map."""
+    return _detect_peaks(rds, ctx, want_db, lambda c, d: c.detect(d, tables.power_threshold(threshold_db), i_lo, i_hi,
+                                                                  want_db=want_db))
 
 
 def detect_peaks_cfar(rds, *, guard=(2, 2), train=(8, 8), pfa=1e-4, alpha=None, threshold_db=-math.inf, i_lo=0,
@@ -110,29 +115,11 @@ def detect_peaks_cfar(rds, *, guard=(2, 2), train=(8, 8), pfa=1e-4, alpha=None, 
     """rds [A, S, C] -> the dictionary of detect_peaks, with the CA-CFAR detector (rsl_detect_cfar) in place of the
     fixed threshold: guard / train (range, doppler) half-sizes, alpha on the training mean (default: from pfa and the
     full-window count, tables.cfar_alpha); threshold_db remains as a floor (-inf: none)."""
-    c = _ctx(ctx)
-    d = as_dev_c64(c, rds)
-    if d.dim() == 3:
-        d = d.unsqueeze(0)
-    d = d.contiguous()
-    F, A, S, C = d.shape
     if alpha is None:
         alpha = tables.cfar_alpha(pfa, tables.cfar_training_cells(guard, train))
-    mask, rc, db = c.detect_cfar(d, guard, train, alpha, tables.power_threshold(threshold_db), i_lo, i_hi,
-                                 want_db=want_db)
-    offs = c.offsets(mask, rc, C)
-    ne = int(offs['entry_base'][F].item())
-    nc = int(offs['cell_base'][F].item())
-    lists = c.emit(d, mask, offs, ne, nc, want_pdb=True)
-    ant, rbin, dbin = unpack_coord(to_host(lists['e_coord'][:ne]))
-    res = dict(antenna=ant.astype(np.int64), range_bin=rbin.astype(np.int64), doppler_bin=dbin.astype(np.int64),
-               power_db=to_host(lists['e_pdb'][:ne], np.float64),
-               entry_base=to_host(offs['entry_base']), cells=nc)
-    if want_db:
-        res['power_spectrum_db'] = to_host(db, np.float64)
-        if F == 1:
-            res['power_spectrum_db'] = res['power_spectrum_db'][0]
-    return res
+    return _detect_peaks(rds, ctx, want_db, lambda c, d: c.detect_cfar(d, guard, train, alpha,
+                                                                       tables.power_threshold(threshold_db), i_lo, i_hi,
+                                                                       want_db=want_db))
 
 
 # -- signatures as a pseudo-RDS [N, A, 1, 1] -------------------------------------------------------------

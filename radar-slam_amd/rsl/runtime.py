@@ -104,6 +104,11 @@ class Context:
     def empty(self, shape, dtype):
         return self.torch.empty(shape, dtype=dtype, device=self.device)
 
+    def _buf(self, bufs, name, shape, dtype):
+        """The caller's preallocated buffer ``bufs[name]`` where there is one, else a new tensor."""
+        t = bufs.get(name) if bufs else None
+        return t if t is not None else self.empty(shape, dtype)
+
     def empty_contiguous(self, shape, dtype):
         """A device tensor in its own physically contiguous allocation (hipExtMallocWithFlags with
         hipDeviceMallocContiguous), freed when the tensor goes away; None when the driver cannot provide it.  For the
@@ -196,20 +201,19 @@ class Context:
         return int(group.value)
 
     # -- a8 -------------------------------------------------------------------------------------
-    def detect(self, rds, thr_power: float, i_lo: int, i_hi: int, want_db: bool = False, out=None):
+    def _detect_out(self, rds, want_db, out):
+        """Outputs of a detector on rds [F, A, S, C]: (mask, row_count, db map or None, peak_pow or None); mask,
+        row_count and peak_pow from ``out`` where given (peak_pow is never allocated here)."""
         torch = self.torch
         F, A, S, C = rds.shape
-        W = (C + 63) // 64
-        if out is None:
-            out = {}
-        mask = out.get('mask')
-        if mask is None:
-            mask = self.empty((F, A, S, W), torch.int64)
-        rc = out.get('row_count')
-        if rc is None:
-            rc = self.empty((F, A, S), torch.int32)
+        mask = self._buf(out, 'mask', (F, A, S, (C + 63) // 64), torch.int64)
+        rc = self._buf(out, 'row_count', (F, A, S), torch.int32)
         db = self.empty((F, A, S, C), torch.float32) if want_db else None
-        pk = out.get('peak_pow')
+        return mask, rc, db, (out or {}).get('peak_pow')
+
+    def detect(self, rds, thr_power: float, i_lo: int, i_hi: int, want_db: bool = False, out=None):
+        F, A, S, C = rds.shape
+        mask, rc, db, pk = self._detect_out(rds, want_db, out)
         self._bind()
         self.check(self.lib.rsl_detect(self.h, _ptr(rds), F, A, S, C, float(thr_power), int(i_lo), int(i_hi),
                                        _ptr(mask), _ptr(rc), _ptr(db), _ptr(pk)), 'rsl_detect')
@@ -219,19 +223,8 @@ class Context:
                     want_db: bool = False, out=None):
         """CA-CFAR detector (rsl_detect_cfar): guard / train = (range, doppler) half-sizes, alpha on the training
         mean, thr_power the power floor (negative: none).  Outputs as detect (peak_pow row-compact, group 1)."""
-        torch = self.torch
         F, A, S, C = rds.shape
-        W = (C + 63) // 64
-        if out is None:
-            out = {}
-        mask = out.get('mask')
-        if mask is None:
-            mask = self.empty((F, A, S, W), torch.int64)
-        rc = out.get('row_count')
-        if rc is None:
-            rc = self.empty((F, A, S), torch.int32)
-        db = self.empty((F, A, S, C), torch.float32) if want_db else None
-        pk = out.get('peak_pow')
+        mask, rc, db, pk = self._detect_out(rds, want_db, out)
         self._bind()
         self.check(self.lib.rsl_detect_cfar(self.h, _ptr(rds), F, A, S, C, int(guard[0]), int(guard[1]),
                                             int(train[0]), int(train[1]), float(alpha), float(thr_power), int(i_lo),
@@ -241,14 +234,13 @@ class Context:
     def offsets(self, mask, row_count, C: int, bufs=None):
         torch = self.torch
         F, A, S, W = mask.shape
-        b = bufs or {}
-        eo = b.get('entry_row_off') if b.get('entry_row_off') is not None else self.empty((F * A * S,), torch.int32)
-        co = b.get('cell_row_off') if b.get('cell_row_off') is not None else self.empty((F * S,), torch.int32)
-        sc = b.get('scratch') if b.get('scratch') is not None else self.empty((F * S,), torch.int32)
-        eb = b.get('entry_base') if b.get('entry_base') is not None else self.empty((F + 1,), torch.int64)
-        cb = b.get('cell_base') if b.get('cell_base') is not None else self.empty((F + 1,), torch.int64)
-        fc = b.get('frame_counts') if b.get('frame_counts') is not None else self.empty((2 * F,), torch.int64)
-        um = b.get('union_mask') if b.get('union_mask') is not None else self.empty((F, S, W), torch.int64)
+        eo = self._buf(bufs, 'entry_row_off', (F * A * S,), torch.int32)
+        co = self._buf(bufs, 'cell_row_off', (F * S,), torch.int32)
+        sc = self._buf(bufs, 'scratch', (F * S,), torch.int32)
+        eb = self._buf(bufs, 'entry_base', (F + 1,), torch.int64)
+        cb = self._buf(bufs, 'cell_base', (F + 1,), torch.int64)
+        fc = self._buf(bufs, 'frame_counts', (2 * F,), torch.int64)
+        um = self._buf(bufs, 'union_mask', (F, S, W), torch.int64)
         self._bind()
         self.check(self.lib.rsl_peak_offsets(self.h, _ptr(mask), _ptr(row_count), F, A, S, C, _ptr(eo), _ptr(co),
                                              _ptr(sc), _ptr(eb), _ptr(cb), _ptr(fc), _ptr(um)), 'rsl_peak_offsets')
@@ -261,11 +253,9 @@ class Context:
         the grouping it returned) and the offsets' union mask the RDS is not re-read."""
         torch = self.torch
         F, A, S, C = rds.shape
-        b = bufs or {}
 
         def get(name, n, dt):
-            t = b.get(name)
-            return t if t is not None else self.empty((max(n, 1),), dt)
+            return self._buf(bufs, name, (max(n, 1),), dt)
         # e_coord = antenna << 26 | range_bin << 13 | doppler_bin (u32 bits in an int32 tensor; unpack_coord)
         e_co, e_c = get('e_coord', entry_cap, torch.int32), get('e_cell', entry_cap, torch.int32)
         e_pdb = get('e_pdb', entry_cap, torch.float32) if want_pdb else None
@@ -369,13 +359,11 @@ class Context:
         _, A, S, C = rds.shape
         G, L = int(steer_sub.shape[0]), int(steer_sub.shape[1])
         cap = int(c_frame.shape[0]) if n is None else int(n)
-        o = out or {}
         rows = max(cap, 1)
         nmax = int(nmax)
 
-        def get(name, shape, dt, want=True):
-            t = o.get(name)
-            return t if t is not None else (self.empty(shape, dt) if want else None)
+        def get(name, shape, dt, want=True):  # a buffer the caller gave is filled whether wanted or not
+            return self._buf(out, name, shape, dt) if want else (out or {}).get(name)
         nsrc = get('nsrc', (rows,), torch.int32)
         idx = get('idx', (rows, max(nmax, 1)), torch.int32)
         den = get('den', (rows, max(nmax, 1)), torch.float32, want_den)
@@ -391,14 +379,11 @@ class Context:
                     want_sig=False, want_esprit=False, want_phase=False, gidx=None, az_table=None, bufs=None):
         torch = self.torch
         _, A, S, C = rds.shape
-        b = bufs or {}
         cap = max(int(n), 1)
         sig = self.empty((cap, A), torch.complex64) if want_sig else None
-        esp = (b.get('esprit') if b.get('esprit') is not None else self.empty((cap,), torch.float64)) if want_esprit else None
-        ph = (b.get('phase') if b.get('phase') is not None else self.empty((cap,), torch.float64)) if want_phase else None
-        az = None
-        if az_table is not None:
-            az = b.get('az') if b.get('az') is not None else self.empty((cap,), torch.float64)
+        esp = self._buf(bufs, 'esprit', (cap,), torch.float64) if want_esprit else None
+        ph = self._buf(bufs, 'phase', (cap,), torch.float64) if want_phase else None
+        az = self._buf(bufs, 'az', (cap,), torch.float64) if az_table is not None else None
         self._bind()
         self.check(self.lib.rsl_cell_extras(self.h, _ptr(rds), A, S, C, _ptr(c_frame), _ptr(c_rc), _ptr(n_dev),
                                             int(n), float(esprit_scale), _ptr(gidx), _ptr(az_table), _ptr(sig),

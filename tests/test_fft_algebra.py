@@ -1,4 +1,4 @@
-"""CPU restatement of the register-form FFT decompositions the packed front half uses (rsl_fft.hip), checked against
+"""CPU restatement of the register-form FFT decompositions the packed front half uses (rsl_fft.hip, rsl_doppler_detect.hip), checked against
 numpy's 2-D FFT: the index algebra of each kernel pair, not its rounding (that is the GPU parity tests' job).
   S = 512,  C = 128: k_range_fft_r512 (16 x 32: DFT16 over m, DFT16 over j = 2 i + h, radix-2 across the lane pair),
                      Doppler step W128^(c k1) DFT8 over q (chirps c + 16 q), k_doppler_detect_r128 DFT16 over classes;

@@ -73,8 +73,8 @@ def test_scheduling_invariance(ctx, name):
 
 
 def test_concurrent_streams(ctx):
-    """K1 launches in flight on several streams at once: each stream owns its dequeue slot (rsl_fft.hip
-    rf_slot), so chains of two shapes on three streams, 8 launches each, all enqueued before any completes, give the
+    """K1 launches in flight on several streams at once: each stream owns its dequeue queue (rsl_fft.hip
+    rf_queue), so chains of two shapes on three streams, 8 launches each, all enqueued before any completes, give the
     serial results bit for bit."""
     import rsl
     shapes = [(6, 8, 128, 51.2e-6), (6, 8, 128, 51.2e-6), (2, 16, 256, 102.4e-6)]

@@ -1,7 +1,9 @@
 """SHA-256 of every output of one cfg2 chain batch (RDS, masks, row counts, peak powers, offsets, lists, DoA, ESPRIT,
-phase, velocity) and of the DoA paths the chain does not run (f32 scans, spectra, smoothed MUSIC; on the first NDOA
-cells of the chain's list) under the library RSL_LIBRARY: equal hashes across two libraries = bit-identical chains.
-GPU box:  [CFG=cfg1|cfg2|cfg5] [F=frames] [NDOA=cells] RSL_LIBRARY=... python tools/chain_hash.py"""
+phase, velocity), of the detectors the chain does not run (rsl_detect and rsl_detect_cfar on the chain's RDS) and of the
+DoA paths it does not run (f32 scans, spectra, smoothed MUSIC; on the first NDOA cells of the chain's list) under the
+library RSL_LIBRARY: equal hashes across two libraries = bit-identical chains.  cfg1 / cfg2 / cfg5 reach the packed
+kernels, gen32 the general fused tile body, gen64 the register body on padded rows, unf48 the unfused fall-back.
+GPU box:  [CFG=cfg1|cfg2|cfg5|gen32|gen64|unf48] [F=frames] [NDOA=cells] RSL_LIBRARY=... python tools/chain_hash.py"""
 import hashlib
 import json
 import os
@@ -17,7 +19,8 @@ from rsl import tables  # noqa: E402
 from rsl.runtime import spectrum_rows  # noqa: E402
 from bench import make_cubes  # noqa: E402
 
-A, C, TC = {'cfg1': (8, 64, 25.6e-6), 'cfg2': (8, 128, 51.2e-6), 'cfg5': (16, 256, 102.4e-6)}[os.environ.get('CFG', 'cfg2')]
+A, C, TC = {'cfg1': (8, 64, 25.6e-6), 'cfg2': (8, 128, 51.2e-6), 'cfg5': (16, 256, 102.4e-6), 'gen32': (4, 32, 12.8e-6),
+            'gen64': (2, 64, 6.4e-6), 'unf48': (6, 48, 9.6e-6)}[os.environ.get('CFG', 'cfg2')]
 F = int(os.environ.get('F', '200'))
 ctx = rsl.get_context(0)
 cfg = rsl.ChainConfig(num_antennas=A, num_chirps=C, chirp_duration=TC)
@@ -39,6 +42,19 @@ for name, t in (('rds', ch.rds), ('mask', ch.mask), ('row_count', ch.row_count),
                 ('phase', ch.ext['phase'][:nc]), ('vel', ch.vel)):
     out[name] = sha(t)
 
+# The detectors the chain does not run, on the chain's RDS: mask, row counts and the row-compact peak powers' prefix.
+W = (C + 63) // 64
+for name, run in (('det', lambda o: ctx.detect(ch.rds, ch.thr_p, ch.i_lo, ch.i_hi, out=o)),
+                  ('cfar', lambda o: ctx.detect_cfar(ch.rds, (2, 2), (8, 8), 12.0, ch.thr_p, ch.i_lo, ch.i_hi, out=o))):
+    o = dict(mask=torch.zeros((F, A, ch.S, W), dtype=torch.int64, device=ctx.device),
+             row_count=torch.zeros((F, A, ch.S), dtype=torch.int32, device=ctx.device),
+             peak_pow=torch.zeros((F, A, ch.S, C), dtype=torch.float32, device=ctx.device))
+    run(o)
+    torch.cuda.synchronize()
+    out[name + '_mask'], out[name + '_rows'], out[name + '_pk'] = sha(o['mask']), sha(o['row_count']), sha(o['peak_pow'])
+    out[name + '_n'] = int(o['row_count'].sum().item())
+    del o
+
 # The DoA paths the chain does not run, on (a prefix of) the chain's own cell list: the f32 scans (argmax with gmax; the
 # three spectrum layouts), the Toeplitz cell-blocked spectrum, and the spatially smoothed MUSIC.
 n = min(nc, int(os.environ.get('NDOA', '100003')))
@@ -54,7 +70,9 @@ for name, kw in (('f32_spec_cm', {}), ('f32_spec_gm', {'spec_gmajor': True}), ('
     del spec
 d = cfg.antenna_spacing or cfg.lambda_c / 2
 steer = tables.steering_matrix(ch.grid, np.arange(A) * d, cfg.lambda_c)
-sub = ctx.steering_sub(steer, tables.default_sub_len(A))
-nsrc, idx, den, _, _ = ctx.doa_smoothed(ch.rds, L['c_frame'], L['c_rc'], sub, n=n)
-out['ss_nsrc'], out['ss_idx'], out['ss_den'] = sha(nsrc[:n]), sha(idx[:n]), sha(den[:n])
+if A >= 3:  # the smoothed estimator needs three antennas
+    sub_len = tables.default_sub_len(A)
+    sub = ctx.steering_sub(steer, sub_len)
+    nsrc, idx, den, _, _ = ctx.doa_smoothed(ch.rds, L['c_frame'], L['c_rc'], sub, n=n, nmax=min(3, sub_len - 1))
+    out['ss_nsrc'], out['ss_idx'], out['ss_den'] = sha(nsrc[:n]), sha(idx[:n]), sha(den[:n])
 print(json.dumps(out), flush=True)
