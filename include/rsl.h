@@ -126,6 +126,32 @@ int rsl_detect_cfar(rsl_handle h, const void* rds, int F, int A, int S, int C, i
                     int train_d, double alpha, double thr_power, int i_lo, int i_hi, void* mask, void* row_count,
                     void* db_map, void* peak_pow);
 
+/* OS-CFAR detector (ordered statistic, Rohling 1983): rsl_detect_cfar with the k-th smallest training cell in place
+ *     of the training mean, so that a second reflector inside the window does not raise the noise estimate.  There is
+ *     no reference counterpart: this comment is the specification.
+ *     Training cells: exactly those of rsl_detect_cfar (offsets |di| <= hr, |dj| <= hd without the guard box; Doppler
+ *     wraps, range truncates; no window reads another antenna's or frame's map); n(i) is the number of training cells
+ *     that exist for range row i.
+ *     Rank: k(i) = min(n(i), max(1, ceil(rank * n(i)))), evaluated in fp64, rank in (0, 1].  Truncated edge rows keep
+ *     the same fraction; rank = 1 is the window maximum, a tiny rank the minimum.
+ *     Decision: with p = |rds|^2 in fp32 and alpha_f = (float)alpha, cell (i, j) is a peak iff
+ *       the number of existing training cells q with alpha_f * q < p (one fp32 multiply) is >= k(i)  -- fp32
+ *       multiplication by a positive constant is monotone, so this is p > fl32(alpha_f * x_(k(i))), x_(k) the k-th
+ *       smallest training power; strict: an all-zero map has no peak,
+ *       p >= every existing 3x3 neighbour (rsl_detect's rule and boundary),  i_lo <= i <= i_hi,  and
+ *       (double)p > thr_power (a negative thr_power disables the floor).
+ *     The count is exact and independent of the order in which the cells are visited.
+ *     Factor: alpha multiplies the order statistic, not a mean.  For a square-law detector in exponential noise with
+ *     N training cells and rank k:  Pfa = prod_{m=0}^{k-1} (N - m) / (N - m + alpha)  (N = 16, k = 12, Pfa 1e-6:
+ *     alpha = 20.95); the host inverts it with N the full-window count.
+ *     Outputs, F = 0 and timing (RSL_K_DETECT) as rsl_detect_cfar; peak_pow row-compact, group 1.
+ *     RSL_ERR_INVALID: every case of rsl_detect_cfar; rank not in (0, 1] or NaN; (float)alpha not finite and > 0.
+ *     RSL_ERR_UNSUPPORTED: C > RSL_CFAR_MAX_C.  Every window up to RSL_CFAR_MAX_HALF is supported at every
+ *     C <= RSL_CFAR_MAX_C. */
+int rsl_detect_oscfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d,
+                      int train_r, int train_d, double rank, double alpha, double thr_power, int i_lo, int i_hi,
+                      void* mask, void* row_count, void* db_map, void* peak_pow);
+
 /* a7 + a8 fused: range FFT, then Doppler FFT + fftshift + RDS store + peak detection in one kernel (the RDS is
  *     not re-read for detection).  Arguments as rsl_rds and rsl_detect; falls back to the two calls when the
  *     shape is not covered (C not a power of two <= 1024, or its range-bin tiling does not divide S/2).

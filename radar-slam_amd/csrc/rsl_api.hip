@@ -316,20 +316,29 @@ int rsl_detect(rsl_handle h, const void* rds, int F, int A, int S, int C, double
   return hip_check(h, rsl::launch_detect(h->stream, (const float2*)rds, F, A, S, C, det), "detect");
 }
 
+// The checks that rsl_detect_cfar and rsl_detect_oscfar share, in the order the header lists them; `fn` names the
+// entry point in the error text.  Returns RSL_OK when the shape, the window and alpha are usable.
+static int cfar_check(rsl_handle h, const std::string& fn, int F, int A, int S, int C, int guard_r, int guard_d,
+                      int train_r, int train_d, double alpha, bool (*supported)(int, int, int)) {
+  if (F < 0 || A <= 0 || S <= 0 || C <= 0 || S > 8192) return fail(h, RSL_ERR_INVALID, fn + ": bad shape");
+  if (guard_r < 0 || guard_d < 0 || train_r < 0 || train_d < 0 || train_r + train_d < 1)
+    return fail(h, RSL_ERR_INVALID, fn + ": bad window (half-sizes >= 0, at least one training cell)");
+  const int hr = guard_r + train_r, hd = guard_d + train_d;
+  if (hr > RSL_CFAR_MAX_HALF || hd > RSL_CFAR_MAX_HALF)
+    return fail(h, RSL_ERR_INVALID, fn + ": window half-size above RSL_CFAR_MAX_HALF");
+  if (2 * hd + 1 > C || 2 * hr + 1 > S) return fail(h, RSL_ERR_INVALID, fn + ": window larger than the map");
+  if (!(alpha > 0) || !std::isfinite(alpha)) return fail(h, RSL_ERR_INVALID, fn + ": alpha must be finite, > 0");
+  if (C > RSL_CFAR_MAX_C || !supported(C, hr, hd)) return fail(h, RSL_ERR_UNSUPPORTED, fn + ": C above RSL_CFAR_MAX_C");
+  return RSL_OK;
+}
+
 int rsl_detect_cfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d, int train_r,
                     int train_d, double alpha, double thr_power, int i_lo, int i_hi, void* mask, void* row_count,
                     void* db_map, void* peak_pow) {
   if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || A <= 0 || S <= 0 || C <= 0 || S > 8192) return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: bad shape");
-  if (guard_r < 0 || guard_d < 0 || train_r < 0 || train_d < 0 || train_r + train_d < 1)
-    return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: bad window (half-sizes >= 0, at least one training cell)");
-  const int hr = guard_r + train_r, hd = guard_d + train_d;
-  if (hr > RSL_CFAR_MAX_HALF || hd > RSL_CFAR_MAX_HALF)
-    return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: window half-size above RSL_CFAR_MAX_HALF");
-  if (2 * hd + 1 > C || 2 * hr + 1 > S) return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: window larger than the map");
-  if (!(alpha > 0) || !std::isfinite(alpha)) return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: alpha must be finite, > 0");
-  if (C > RSL_CFAR_MAX_C || !rsl::detect_cfar_supported(C, hr, hd))
-    return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect_cfar: C above RSL_CFAR_MAX_C");
+  if (int r = cfar_check(h, "rsl_detect_cfar", F, A, S, C, guard_r, guard_d, train_r, train_d, alpha,
+                         rsl::detect_cfar_supported))
+    return r;
   if (F == 0) return RSL_OK;
   if (!rds || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: null pointer");
   Scope sc(h, RSL_K_DETECT);
@@ -339,6 +348,26 @@ int rsl_detect_cfar(rsl_handle h, const void* rds, int F, int A, int S, int C, i
                    rsl::launch_detect_cfar(h->stream, (const float2*)rds, F, A, S, C, guard_r, guard_d, train_r,
                                            train_d, (float)alpha, det),
                    "detect_cfar");
+}
+
+int rsl_detect_oscfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d,
+                      int train_r, int train_d, double rank, double alpha, double thr_power, int i_lo, int i_hi,
+                      void* mask, void* row_count, void* db_map, void* peak_pow) {
+  if (!h) return RSL_ERR_INVALID;
+  // the factor is checked as the float the kernel multiplies by
+  if (int r = cfar_check(h, "rsl_detect_oscfar", F, A, S, C, guard_r, guard_d, train_r, train_d, (float)alpha,
+                         rsl::detect_oscfar_supported))
+    return r;
+  if (!(rank > 0 && rank <= 1)) return fail(h, RSL_ERR_INVALID, "rsl_detect_oscfar: rank must lie in (0, 1]");
+  if (F == 0) return RSL_OK;
+  if (!rds || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect_oscfar: null pointer");
+  Scope sc(h, RSL_K_DETECT);
+  const rsl::DetectArgs det{thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map,
+                            (float*)peak_pow};
+  return hip_check(h,
+                   rsl::launch_detect_oscfar(h->stream, (const float2*)rds, F, A, S, C, guard_r, guard_d, train_r,
+                                             train_d, rank, (float)alpha, det),
+                   "detect_oscfar");
 }
 
 int rsl_peak_offsets(rsl_handle h, const void* mask, const void* row_count, int F, int A, int S, int C,

@@ -56,11 +56,9 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
   float* PW = HS + (size_t)NR * C;  // [NP][PS] power rows, hd wrapped cells on both sides (-1: row outside the map)
   unsigned long long* MX = reinterpret_cast<unsigned long long*>(PW + (size_t)NP * PS);  // [NR][W] 3x3 maxima
 
-  const int nstrip = (S + R - 1) / R;
-  const int strip = blockIdx.x % nstrip;
-  const size_t fa = blockIdx.x / nstrip;
-  const int i0 = strip * R;
-  const int Re = min(R, S - i0);
+  const CfarStrip sp = cfar_strip(S, R);
+  const size_t fa = sp.fa;
+  const int i0 = sp.i0, Re = sp.Re;
   const int UL = Re + 2 * hh;  // rows the strip loads: u = 0 .. UL-1 is range row ibase + u
   const int ibase = i0 - hh;
   const float2* base = rds + fa * S * C;
@@ -70,19 +68,7 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
   int done = hh;  // next row (u) to decide
   for (int uk = 0; uk < UL; uk += RB) {
     // A: powers of the step's rows
-    for (int r = wave; r < RB; r += 4) {
-      const int u = uk + r;
-      if (u >= UL) break;
-      const int i = ibase + u;
-      const bool valid = i >= 0 && i < S;
-      float* pr = PW + (size_t)(u % NP) * PS;
-      for (int j = lane; j < C; j += 64) {
-        const float p = valid ? cabs2(base[(size_t)i * C + j]) : -1.f;
-        pr[hd + j] = p;
-        if (j < hd) pr[hd + C + j] = p;         // right halo: columns 0 .. hd-1
-        if (j >= C - hd) pr[j - (C - hd)] = p;  // left halo: columns C-hd .. C-1
-      }
-    }
+    power_rows_halo(PW, NP, PS, base, ibase, uk + wave, min(uk + RB, UL), S, C, hd, -1.f);
     __syncthreads();
     // B: row sums of the step's rows (rows of the map only)
     for (int r = wave; r < RB; r += 4) {
@@ -176,9 +162,7 @@ hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, i
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  // strips of 128 rows (halo re-read 1.16x at hr = 10); 32 rows when that leaves the device short of workgroups
-  int R = 128;
-  if ((long long)F * A * ((S + R - 1) / R) < 1024) R = 32;
+  const int R = cfar_strip_rows(F, A, S);
   const long long nblk = (long long)F * A * ((S + R - 1) / R);
   if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_detect_cfar, dim3((unsigned)nblk), dim3(256), lds, st, rds, S, C, W, gr, gd, tr, td, alpha,

@@ -68,6 +68,12 @@ hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S,
 bool detect_cfar_supported(int C, int hr, int hd);
 hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, int gr, int gd, int tr,
                               int td, float alpha, const DetectArgs& det);
+// K3 alternative (rsl_oscfar.hip): 2-D ordered-statistic CFAR on the same window and with the same outputs: the
+// rank-th fraction of the training cells (k(i) = min(n(i), max(1, ceil(rank n(i))))) in place of their mean.
+// detect_oscfar_supported: the power ring of a window (hr, hd) fits the CU's LDS at C.
+bool detect_oscfar_supported(int C, int hr, int hd);
+hipError_t launch_detect_oscfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, int gr, int gd, int tr,
+                                int td, double rank, float alpha, const DetectArgs& det);
 // Per-frame offsets of peak entries (antenna-major) and union cells (range-major).
 hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const int* row_count, int F, int A, int S,
                           int C, int* entry_row_off, int* cell_row_off, int* cell_row_cnt, long long* entry_base,

@@ -46,6 +46,8 @@ SIGNATURES = {
     'rsl_detect': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_double, c_int, c_int, _P, _P, _P, _P]),
     'rsl_detect_cfar': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double,
                                 c_int, c_int, _P, _P, _P, _P]),
+    'rsl_detect_oscfar': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double,
+                                  c_double, c_int, c_int, _P, _P, _P, _P]),
     'rsl_peak_offsets': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     'rsl_peak_emit': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_longlong,
                               c_longlong, _P, _P, _P, _P, _P, _P]),

@@ -56,6 +56,10 @@ class ChainConfig:
     cfar_train: tuple = (8, 8)                 # training half-sizes (range, doppler)
     cfar_pfa: float = 1e-4                     # false-alarm rate -> alpha (tables.cfar_alpha)
     cfar_alpha: Optional[float] = None         # factor on the training mean; overrides cfar_pfa when set
+    cfar_method: str = 'ca'                    # 'ca': cell averaging (rsl_detect_cfar); 'os': ordered statistic
+                                               # (rsl_detect_oscfar), cfar_alpha / cfar_pfa then refer to the
+                                               # order statistic (tables.os_cfar_alpha)
+    cfar_rank: float = 0.75                    # 'os': the ceil(cfar_rank * cells)-th smallest training cell, (0, 1]
     velocity_loss: str = 'ls'                  # 'ls': rsl_velocity (plain box-constrained LS); 'huber' | 'tukey':
                                                # rsl_velocity_robust (IRLS from the LS start, include/rsl.h)
     velocity_scale: Optional[float] = None     # residual scale sigma (the sensor's phase-noise sigma, radians); None:
@@ -96,6 +100,10 @@ class ChainConfig:
             raise ValueError(f"velocity_loss must be 'ls', 'huber' or 'tukey', not {self.velocity_loss!r}")
         if self.detector not in ('threshold', 'cfar'):
             raise ValueError(f"detector must be 'threshold' or 'cfar', not {self.detector!r}")
+        if self.cfar_method not in ('ca', 'os'):
+            raise ValueError(f"cfar_method must be 'ca' or 'os', not {self.cfar_method!r}")
+        if not 0.0 < float(self.cfar_rank) <= 1.0:
+            raise ValueError(f'cfar_rank must lie in (0, 1], not {self.cfar_rank!r}')
 
     @property
     def ss_sub_len(self) -> int:
@@ -137,8 +145,13 @@ class RadarChain:
         self.thr_p = tables.power_threshold(cfg.threshold_db)
         self.cfar_alpha = None
         if cfg.detector == 'cfar':
-            self.cfar_alpha = float(cfg.cfar_alpha) if cfg.cfar_alpha is not None else tables.cfar_alpha(
-                cfg.cfar_pfa, tables.cfar_training_cells(cfg.cfar_guard, cfg.cfar_train))
+            n = tables.cfar_training_cells(cfg.cfar_guard, cfg.cfar_train)
+            if cfg.cfar_alpha is not None:
+                self.cfar_alpha = float(cfg.cfar_alpha)
+            elif cfg.cfar_method == 'os':
+                self.cfar_alpha = tables.os_cfar_alpha(cfg.cfar_pfa, n, tables.os_cfar_rank(n, cfg.cfar_rank))
+            else:
+                self.cfar_alpha = tables.cfar_alpha(cfg.cfar_pfa, n)
         d = cfg.antenna_spacing or cfg.lambda_c / 2
         self.grid = tables.azimuth_grid(cfg.search_range, cfg.search_resolution)
         steer_c128 = tables.steering_matrix(self.grid, np.arange(A) * d, cfg.lambda_c)
@@ -235,8 +248,13 @@ class RadarChain:
                                dc_removal=cfg.dc_removal)
         self._group = group
         if cfg.detector == 'cfar':  # the CFAR detector rewrites the fused detector's mask, counts and peak powers
-            ctx.detect_cfar(self.rds, cfg.cfar_guard, cfg.cfar_train, self.cfar_alpha, self.thr_p, self.i_lo,
-                            self.i_hi, out=dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow))
+            out = dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow)
+            if cfg.cfar_method == 'os':
+                ctx.detect_oscfar(self.rds, cfg.cfar_guard, cfg.cfar_train, cfg.cfar_rank, self.cfar_alpha,
+                                  self.thr_p, self.i_lo, self.i_hi, out=out)
+            else:
+                ctx.detect_cfar(self.rds, cfg.cfar_guard, cfg.cfar_train, self.cfar_alpha, self.thr_p, self.i_lo,
+                                self.i_hi, out=out)
             self._group = 1
         if offsets:
             ctx.offsets(self.mask, self.row_count, self.C, bufs=self.offs)

@@ -111,14 +111,24 @@ def detect_peaks(rds, *, threshold_db=-20.0, i_lo=0, i_hi=1 << 30, want_db=True,
 
 
 def detect_peaks_cfar(rds, *, guard=(2, 2), train=(8, 8), pfa=1e-4, alpha=None, threshold_db=-math.inf, i_lo=0,
-                      i_hi=1 << 30, want_db=True, ctx: Optional[Context] = None):
-    """rds [A, S, C] -> the dictionary of detect_peaks, with the CA-CFAR detector (rsl_detect_cfar) in place of the
-    fixed threshold: guard / train (range, doppler) half-sizes, alpha on the training mean (default: from pfa and the
-    full-window count, tables.cfar_alpha); threshold_db remains as a floor (-inf: none)."""
+                      i_hi=1 << 30, want_db=True, ctx: Optional[Context] = None, method='ca', rank=0.75):
+    """rds [A, S, C] -> the dictionary of detect_peaks, with a CFAR detector in place of the fixed threshold: guard /
+    train (range, doppler) half-sizes; threshold_db remains as a floor (-inf: none).
+    method 'ca' (rsl_detect_cfar): alpha on the training mean (default: from pfa and the full-window count,
+    tables.cfar_alpha).  method 'os' (rsl_detect_oscfar): alpha on the training cells' order statistic of rank
+    ceil(rank * cells) (default: tables.os_cfar_alpha for the full window)."""
+    if method not in ('ca', 'os'):
+        raise ValueError(f"method must be 'ca' or 'os', not {method!r}")
+    n = tables.cfar_training_cells(guard, train)
+    thr = tables.power_threshold(threshold_db)
+    if method == 'os':
+        if alpha is None:
+            alpha = tables.os_cfar_alpha(pfa, n, tables.os_cfar_rank(n, rank))
+        return _detect_peaks(rds, ctx, want_db, lambda c, d: c.detect_oscfar(d, guard, train, rank, alpha, thr, i_lo,
+                                                                             i_hi, want_db=want_db))
     if alpha is None:
-        alpha = tables.cfar_alpha(pfa, tables.cfar_training_cells(guard, train))
-    return _detect_peaks(rds, ctx, want_db, lambda c, d: c.detect_cfar(d, guard, train, alpha,
-                                                                       tables.power_threshold(threshold_db), i_lo, i_hi,
+        alpha = tables.cfar_alpha(pfa, n)
+    return _detect_peaks(rds, ctx, want_db, lambda c, d: c.detect_cfar(d, guard, train, alpha, thr, i_lo, i_hi,
                                                                        want_db=want_db))
 
 

@@ -231,6 +231,19 @@ class Context:
                                             int(i_hi), _ptr(mask), _ptr(rc), _ptr(db), _ptr(pk)), 'rsl_detect_cfar')
         return mask, rc, db
 
+    def detect_oscfar(self, rds, guard, train, rank: float, alpha: float, thr_power: float, i_lo: int, i_hi: int,
+                      want_db: bool = False, out=None):
+        """OS-CFAR detector (rsl_detect_oscfar): the window of detect_cfar, alpha on the training cells' order
+        statistic of rank k = ceil(rank * cells) (rank in (0, 1]).  Outputs as detect_cfar."""
+        F, A, S, C = rds.shape
+        mask, rc, db, pk = self._detect_out(rds, want_db, out)
+        self._bind()
+        self.check(self.lib.rsl_detect_oscfar(self.h, _ptr(rds), F, A, S, C, int(guard[0]), int(guard[1]),
+                                              int(train[0]), int(train[1]), float(rank), float(alpha),
+                                              float(thr_power), int(i_lo), int(i_hi), _ptr(mask), _ptr(rc), _ptr(db),
+                                              _ptr(pk)), 'rsl_detect_oscfar')
+        return mask, rc, db
+
     def offsets(self, mask, row_count, C: int, bufs=None):
         torch = self.torch
         F, A, S, W = mask.shape

@@ -11,6 +11,8 @@ computes in fp32):
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 C_LIGHT = 3e8
@@ -82,6 +84,41 @@ def cfar_alpha(pfa: float, n_train: int) -> float:
     if n < 1 or not (0.0 < pfa < 1.0):
         raise ValueError('cfar_alpha: pfa must lie in (0, 1) and n_train be >= 1')
     return float(n * (pfa ** (-1.0 / n) - 1.0))
+
+
+def os_cfar_rank(n: int, rank: float) -> int:
+    """Rank k of the OS-CFAR order statistic among n training cells: min(n, max(1, ceil(rank * n))), rank in (0, 1]
+    (the rule rsl_detect_oscfar applies per range row, in fp64)."""
+    n = int(n)
+    if n < 1 or not (0.0 < rank <= 1.0):
+        raise ValueError('os_cfar_rank: rank must lie in (0, 1] and n be >= 1')
+    return min(n, max(1, int(math.ceil(float(rank) * n))))
+
+
+def os_cfar_pfa(alpha: float, n_train: int, k: int) -> float:
+    """False-alarm rate of OS-CFAR with factor alpha on the k-th smallest of N training cells (square-law detector,
+    exponential noise; Rohling 1983): prod_{m=0}^{k-1} (N - m) / (N - m + alpha)."""
+    m = np.arange(int(k), dtype=np.float64)
+    return float(np.exp(-np.log1p(alpha / (int(n_train) - m)).sum()))
+
+
+def os_cfar_alpha(pfa: float, n_train: int, k: int) -> float:
+    """OS-CFAR factor on the k-th smallest training cell for false-alarm rate pfa: os_cfar_pfa (strictly decreasing
+    in alpha) inverted by bisection to fp64 precision."""
+    n, k = int(n_train), int(k)
+    if not (0.0 < pfa < 1.0) or not 1 <= k <= n:
+        raise ValueError('os_cfar_alpha: pfa must lie in (0, 1) and k in [1, n_train]')
+    lo, hi = 0.0, 1.0
+    while os_cfar_pfa(hi, n, k) > pfa:
+        lo, hi = hi, 2.0 * hi
+    while True:
+        mid = 0.5 * (lo + hi)
+        if not lo < mid < hi:
+            return mid
+        if os_cfar_pfa(mid, n, k) > pfa:
+            lo = mid
+        else:
+            hi = mid
 
 
 def azimuth_grid(search_range=(-90, 90), search_resolution=0.5):

@@ -124,17 +124,18 @@ class SignalPreprocessor:
 
     def extract_range_doppler_peaks_cfar(self, rds: np.ndarray, guard=(2, 2), train=(8, 8), pfa: float = 1e-4,
                                          threshold_db: Optional[float] = None, min_range: float = 1.0,
-                                         max_range: float = 200.0) -> Dict:
-        """extract_range_doppler_peaks with a 2-D CA-CFAR detector (not in the reference): 3x3 local maxima above
-        alpha x the mean of the training cells (guard / train = (range, doppler) half-sizes, alpha from pfa) within
-        the range gate; threshold_db is an optional floor on top (None: no floor).  Same dict."""
+                                         max_range: float = 200.0, method: str = 'ca', rank: float = 0.75) -> Dict:
+        """extract_range_doppler_peaks with a 2-D CFAR detector (not in the reference): 3x3 local maxima above
+        alpha x the mean (method 'ca') or the ceil(rank * cells)-th smallest (method 'os') of the training cells
+        (guard / train = (range, doppler) half-sizes, alpha from pfa) within the range gate; threshold_db is an
+        optional floor on top (None: no floor).  Same dict."""
         A, S, C = rds.shape
         range_bins_m = tables.range_axis(self.bandwidth, S)
         doppler_bins_hz = np.linspace(-self.sampling_rate / 2, self.sampling_rate / 2, C)
         i_lo, i_hi = tables.range_gate(self.bandwidth, S, min_range, max_range)
         r = ops.detect_peaks_cfar(rds, guard=guard, train=train, pfa=pfa,
                                   threshold_db=-np.inf if threshold_db is None else threshold_db, i_lo=i_lo,
-                                  i_hi=i_hi, want_db=True)
+                                  i_hi=i_hi, want_db=True, method=method, rank=rank)
         ant, ib, jb, pdb = r['antenna'], r['range_bin'], r['doppler_bin'], r['power_db']
         peaks = [{'antenna': int(a), 'range_bin': i, 'doppler_bin': j, 'range_m': range_bins_m[i],
                   'doppler_hz': doppler_bins_hz[j], 'power_db': p}
