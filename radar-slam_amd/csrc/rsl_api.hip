@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/rsl.h"
+#include "rsl_cfar_common.h"
 #include "rsl_common.h"
 #include "rsl_doa_common.h"
 #include "rsl_internal.h"
@@ -261,6 +262,12 @@ int rsl_rds(rsl_handle h, const void* cube, int F, int A, int C_total, int chirp
   return hip_check(h, e, "doppler_fft");
 }
 
+// What a detector entry point hands its launcher, from the untyped arguments of the C ABI.
+static rsl::DetectArgs detect_args(double thr_power, int i_lo, int i_hi, void* mask, void* row_count, void* db_map,
+                                   void* peak_pow) {
+  return {thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map, (float*)peak_pow};
+}
+
 int rsl_rds_detect(rsl_handle h, const void* cube, int F, int A, int C_total, int chirp0, int C, int S,
                    const void* table, int dc_removal, void* work, void* rds, double thr_power, int i_lo, int i_hi,
                    void* mask, void* row_count, void* db_map, void* peak_pow, int* peak_pow_group) {
@@ -294,8 +301,7 @@ int rsl_rds_detect(rsl_handle h, const void* cube, int F, int A, int C_total, in
   if (int r = hip_check(h, e, "range_fft")) return r;
   {
     Scope sc(h, RSL_K_DOPPLER_FFT);
-    const rsl::DetectArgs det{thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map,
-                              (float*)peak_pow};
+    const rsl::DetectArgs det = detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow);
     e = rsl::launch_doppler_detect(h->stream, (const float2*)work, F, A, C, S, tC, (float2*)rds, det, &sup, &group,
                                    packed);
   }
@@ -311,63 +317,48 @@ int rsl_detect(rsl_handle h, const void* rds, int F, int A, int S, int C, double
   if (!rds || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect: null pointer");
   if ((size_t)(18 * (size_t)C * 4) > 64 * 1024) return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect: C too large");
   Scope sc(h, RSL_K_DETECT);
-  const rsl::DetectArgs det{thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map,
-                            (float*)peak_pow};
+  const rsl::DetectArgs det = detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow);
   return hip_check(h, rsl::launch_detect(h->stream, (const float2*)rds, F, A, S, C, det), "detect");
 }
 
-// The checks that rsl_detect_cfar and rsl_detect_oscfar share, in the order the header lists them; `fn` names the
-// entry point in the error text.  Returns RSL_OK when the shape, the window and alpha are usable.
-static int cfar_check(rsl_handle h, const std::string& fn, int F, int A, int S, int C, int guard_r, int guard_d,
-                      int train_r, int train_d, double alpha, bool (*supported)(int, int, int)) {
+// rsl_detect_cfar (rank null) and rsl_detect_oscfar (its rank): the checks in the order the header lists them, `fn`
+// naming the entry point in the error text, then the launch.  No LDS check: every window within the limits fits at
+// every C <= RSL_CFAR_MAX_C, which rsl_cfar.hip and rsl_oscfar.hip assert at compile time.
+static int detect_cfar_family(rsl_handle h, const std::string& fn, const void* rds, int F, int A, int S, int C,
+                              rsl::CfarWindow win, const double* rank, double alpha, const rsl::DetectArgs& det) {
+  if (!h) return RSL_ERR_INVALID;
   if (F < 0 || A <= 0 || S <= 0 || C <= 0 || S > 8192) return fail(h, RSL_ERR_INVALID, fn + ": bad shape");
-  if (guard_r < 0 || guard_d < 0 || train_r < 0 || train_d < 0 || train_r + train_d < 1)
+  if (win.gr < 0 || win.gd < 0 || win.tr < 0 || win.td < 0 || win.tr + win.td < 1)
     return fail(h, RSL_ERR_INVALID, fn + ": bad window (half-sizes >= 0, at least one training cell)");
-  const int hr = guard_r + train_r, hd = guard_d + train_d;
-  if (hr > RSL_CFAR_MAX_HALF || hd > RSL_CFAR_MAX_HALF)
+  if (win.hr() > RSL_CFAR_MAX_HALF || win.hd() > RSL_CFAR_MAX_HALF)
     return fail(h, RSL_ERR_INVALID, fn + ": window half-size above RSL_CFAR_MAX_HALF");
-  if (2 * hd + 1 > C || 2 * hr + 1 > S) return fail(h, RSL_ERR_INVALID, fn + ": window larger than the map");
+  if (win.nfull() > C || 2 * win.hr() + 1 > S) return fail(h, RSL_ERR_INVALID, fn + ": window larger than the map");
   if (!(alpha > 0) || !std::isfinite(alpha)) return fail(h, RSL_ERR_INVALID, fn + ": alpha must be finite, > 0");
-  if (C > RSL_CFAR_MAX_C || !supported(C, hr, hd)) return fail(h, RSL_ERR_UNSUPPORTED, fn + ": C above RSL_CFAR_MAX_C");
-  return RSL_OK;
+  if (C > RSL_CFAR_MAX_C) return fail(h, RSL_ERR_UNSUPPORTED, fn + ": C above RSL_CFAR_MAX_C");
+  if (rank && !(*rank > 0 && *rank <= 1)) return fail(h, RSL_ERR_INVALID, fn + ": rank must lie in (0, 1]");
+  if (F == 0) return RSL_OK;
+  if (!rds || !det.mask || !det.row_count) return fail(h, RSL_ERR_INVALID, fn + ": null pointer");
+  Scope sc(h, RSL_K_DETECT);
+  const float2* z = (const float2*)rds;
+  if (rank)
+    return hip_check(h, rsl::launch_detect_oscfar(h->stream, z, F, A, S, C, win, *rank, (float)alpha, det),
+                     "detect_oscfar");
+  return hip_check(h, rsl::launch_detect_cfar(h->stream, z, F, A, S, C, win, (float)alpha, det), "detect_cfar");
 }
 
 int rsl_detect_cfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d, int train_r,
                     int train_d, double alpha, double thr_power, int i_lo, int i_hi, void* mask, void* row_count,
                     void* db_map, void* peak_pow) {
-  if (!h) return RSL_ERR_INVALID;
-  if (int r = cfar_check(h, "rsl_detect_cfar", F, A, S, C, guard_r, guard_d, train_r, train_d, alpha,
-                         rsl::detect_cfar_supported))
-    return r;
-  if (F == 0) return RSL_OK;
-  if (!rds || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect_cfar: null pointer");
-  Scope sc(h, RSL_K_DETECT);
-  const rsl::DetectArgs det{thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map,
-                            (float*)peak_pow};
-  return hip_check(h,
-                   rsl::launch_detect_cfar(h->stream, (const float2*)rds, F, A, S, C, guard_r, guard_d, train_r,
-                                           train_d, (float)alpha, det),
-                   "detect_cfar");
+  return detect_cfar_family(h, "rsl_detect_cfar", rds, F, A, S, C, {guard_r, guard_d, train_r, train_d}, nullptr,
+                            alpha, detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow));
 }
 
 int rsl_detect_oscfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d,
                       int train_r, int train_d, double rank, double alpha, double thr_power, int i_lo, int i_hi,
                       void* mask, void* row_count, void* db_map, void* peak_pow) {
-  if (!h) return RSL_ERR_INVALID;
   // the factor is checked as the float the kernel multiplies by
-  if (int r = cfar_check(h, "rsl_detect_oscfar", F, A, S, C, guard_r, guard_d, train_r, train_d, (float)alpha,
-                         rsl::detect_oscfar_supported))
-    return r;
-  if (!(rank > 0 && rank <= 1)) return fail(h, RSL_ERR_INVALID, "rsl_detect_oscfar: rank must lie in (0, 1]");
-  if (F == 0) return RSL_OK;
-  if (!rds || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect_oscfar: null pointer");
-  Scope sc(h, RSL_K_DETECT);
-  const rsl::DetectArgs det{thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map,
-                            (float*)peak_pow};
-  return hip_check(h,
-                   rsl::launch_detect_oscfar(h->stream, (const float2*)rds, F, A, S, C, guard_r, guard_d, train_r,
-                                             train_d, rank, (float)alpha, det),
-                   "detect_oscfar");
+  return detect_cfar_family(h, "rsl_detect_oscfar", rds, F, A, S, C, {guard_r, guard_d, train_r, train_d}, &rank,
+                            (float)alpha, detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow));
 }
 
 int rsl_peak_offsets(rsl_handle h, const void* mask, const void* row_count, int F, int A, int S, int C,

@@ -13,7 +13,8 @@
 // rows |di| <= gr.  At most 33 * 33 - 1 = 1088 fp32 additions of non-negative terms: relative error < 1088 * 2^-24 =
 // 6.5e-5.
 //
-// One workgroup walks a strip of R range rows of one map, RB rows per step, three phases per step:
+// One workgroup walks a strip of R range rows of one map (the window, the strip walk and the launcher are the CFAR
+// family's, rsl_cfar_common.h), RB rows per step, three phases per step:
 //   A  load RB rows, power to a small LDS ring PW (RB + 2 rows, with the wrapped Doppler halo copied to both ends);
 //   B  HS / HF of the new rows into LDS rings of NR = RB + hr + max(hr, 1) rows; the 3x3 local-maximum ballots of the
 //      rows one behind into MX (64 bits per mask word);
@@ -23,33 +24,32 @@
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
-#include "rsl_common.h"
-#include "rsl_detect_common.h"
-#include "rsl_internal.h"
+#include "../../include/rsl.h"
+#include "rsl_cfar_common.h"
 
 namespace rsl {
 
 namespace {
 
-constexpr size_t kCfarLdsMax = 160 * 1024;  // LDS of one gfx950 CU
-
 // LDS bytes of k_detect_cfar with RB rows per step: HF + HS rings, the power ring, the local-maximum words
-size_t cfar_lds_bytes(int C, int hr, int hd, int RB) {
-  const int hh = hr > 1 ? hr : 1;
-  const size_t NR = (size_t)RB + hr + hh, NP = (size_t)RB + 2, W = ((size_t)C + 63) / 64;
-  return 4 * (2 * NR * C + NP * ((size_t)C + 2 * hd)) + 8 * NR * W;
+constexpr size_t cfar_lds_bytes(int C, CfarWindow win, int RB) {
+  const size_t NR = (size_t)RB + win.hr() + win.hh(), NP = (size_t)RB + 2, W = ((size_t)C + 63) / 64;
+  return 4 * (2 * NR * C + NP * ((size_t)C + 2 * win.hd())) + 8 * NR * W;
 }
+// Monotone in C, hr and hd, so every window that rsl_detect_cfar admits fits at the launcher's smallest RB.
+static_assert(cfar_lds_bytes(RSL_CFAR_MAX_C, CfarWindow{0, 0, RSL_CFAR_MAX_HALF, RSL_CFAR_MAX_HALF}, 4) <= kCfarLdsMax,
+              "the largest CA-CFAR window must fit the LDS of a CU");
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ rds, int S, int C, int W, int gr,
-                                                     int gd, int tr, int td, float alpha, float thr_f, int i_lo,
-                                                     int i_hi, int R, int RB,
+__global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ rds, int S, int C, int W,
+                                                     CfarWindow win, float alpha, float thr_f, int i_lo, int i_hi,
+                                                     int R, int RB,
                                                      unsigned long long* __restrict__ mask,
                                                      int* __restrict__ row_count, float* __restrict__ dbmap,
                                                      float* __restrict__ pk_pow) {
   extern __shared__ float cf_lds[];
-  const int hr = gr + tr, hd = gd + td, hh = max(hr, 1);
+  const int gr = win.gr, gd = win.gd, hr = win.hr(), hd = win.hd(), hh = win.hh();
   const int NR = RB + hr + hh, NP = RB + 2, PS = C + 2 * hd;
   float* HF = cf_lds;               // [NR][C]  row sums over |dj| <= hd
   float* HS = HF + (size_t)NR * C;  // [NR][C]  row sums over gd < |dj| <= hd
@@ -63,7 +63,6 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
   const int ibase = i0 - hh;
   const float2* base = rds + fa * S * C;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nfull = 2 * hd + 1, nguard = 2 * gd + 1;
 
   int done = hh;  // next row (u) to decide
   for (int uk = 0; uk < UL; uk += RB) {
@@ -115,8 +114,7 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
       const int i = ibase + u;
       const size_t orow = fa * S + i;
       const bool gate = (i >= i_lo && i <= i_hi);
-      const int vh = min(i, hr) + 1 + min(S - 1 - i, hr), vg = min(i, gr) + 1 + min(S - 1 - i, gr);
-      const float fn = (float)(vh * nfull - vg * nguard);  // n(i) >= 1 (2 hr + 1 <= S), exact in fp32 (<= 1088)
+      const float fn = (float)win.cells(i, S);  // n(i), exact in fp32 (<= 1088)
       const int dlo = -min(i, hr), dhi = min(S - 1 - i, hr);
       int cnt = 0;
       for (int w = 0; w < W; ++w) {
@@ -144,30 +142,9 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
   }
 }
 
-bool detect_cfar_supported(int C, int hr, int hd) { return cfar_lds_bytes(C, hr, hd, 4) <= kCfarLdsMax; }
-
-hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, int gr, int gd, int tr,
-                              int td, float alpha, const DetectArgs& d) {
-  if (F <= 0 || A <= 0 || S <= 0 || C <= 0) return hipSuccess;
-  const int hr = gr + tr, hd = gd + td;
-  const int W = (C + 63) / 64;
-  // rows per step: the largest of 16 / 8 / 4 whose rings leave room for three workgroups per CU, else 4
-  int RB = 4;
-  if (cfar_lds_bytes(C, hr, hd, 16) <= 48 * 1024) RB = 16;
-  else if (cfar_lds_bytes(C, hr, hd, 8) <= 48 * 1024) RB = 8;
-  const size_t lds = cfar_lds_bytes(C, hr, hd, RB);
-  if (lds > kCfarLdsMax) return hipErrorInvalidValue;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_detect_cfar),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const int R = cfar_strip_rows(F, A, S);
-  const long long nblk = (long long)F * A * ((S + R - 1) / R);
-  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_detect_cfar, dim3((unsigned)nblk), dim3(256), lds, st, rds, S, C, W, gr, gd, tr, td, alpha,
-                     threshold_as_float(d.thr_p), d.i_lo, d.i_hi, R, RB, d.mask, d.row_count, d.dbmap, d.pk_pow);
-  return hipGetLastError();
+hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, CfarWindow win,
+                              float alpha, const DetectArgs& d) {
+  return launch_cfar_strips(st, k_detect_cfar, cfar_lds_bytes, rds, F, A, S, C, win, d, alpha);
 }
 
 }  // namespace rsl

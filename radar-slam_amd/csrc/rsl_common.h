@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #define RSL_DEV __device__ __forceinline__
+#define RSL_HD __host__ __device__ __forceinline__
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 

@@ -62,18 +62,17 @@ hipError_t launch_doppler_detect(hipStream_t st, const float2* work, int F, int 
 bool work_packed_supported(int C, int S);
 // K3: 3x3 local max (reflect), threshold, range gate -> per-antenna bit masks + row counts.
 hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S, int C, const DetectArgs& det);
-// K3 alternative (rsl_cfar.hip): 2-D cell-averaging CFAR (guard gr x gd, training tr x td half-sizes; Doppler wraps,
-// range truncates) + 3x3 local max + range gate + power floor -> the same outputs as launch_detect, peak_pow
-// row-compact.  detect_cfar_supported: the rings of a window (hr, hd) = (gr + tr, gd + td) fit the CU's LDS at C.
-bool detect_cfar_supported(int C, int hr, int hd);
-hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, int gr, int gd, int tr,
-                              int td, float alpha, const DetectArgs& det);
-// K3 alternative (rsl_oscfar.hip): 2-D ordered-statistic CFAR on the same window and with the same outputs: the
-// rank-th fraction of the training cells (k(i) = min(n(i), max(1, ceil(rank n(i))))) in place of their mean.
-// detect_oscfar_supported: the power ring of a window (hr, hd) fits the CU's LDS at C.
-bool detect_oscfar_supported(int C, int hr, int hd);
-hipError_t launch_detect_oscfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, int gr, int gd, int tr,
-                                int td, double rank, float alpha, const DetectArgs& det);
+// K3 alternatives, the CFAR family (CfarWindow and the launcher both share: rsl_cfar_common.h).  Every window within
+// RSL_CFAR_MAX_HALF fits the CU's LDS at every C <= RSL_CFAR_MAX_C: each kernel file asserts it at compile time.
+// rsl_cfar.hip: 2-D cell-averaging CFAR (guard and training half-sizes of the window; Doppler wraps, range truncates)
+// + 3x3 local max + range gate + power floor -> the same outputs as launch_detect, peak_pow row-compact.
+struct CfarWindow;
+hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, CfarWindow win,
+                              float alpha, const DetectArgs& det);
+// rsl_oscfar.hip: 2-D ordered-statistic CFAR on the same window and with the same outputs: the rank-th fraction of the
+// training cells (k(i) = min(n(i), max(1, ceil(rank n(i))))) in place of their mean.
+hipError_t launch_detect_oscfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, CfarWindow win,
+                                double rank, float alpha, const DetectArgs& det);
 // Per-frame offsets of peak entries (antenna-major) and union cells (range-major).
 hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const int* row_count, int F, int A, int S,
                           int C, int* entry_row_off, int* cell_row_off, int* cell_row_cnt, long long* entry_base,

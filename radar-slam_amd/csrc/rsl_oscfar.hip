@@ -7,10 +7,11 @@
 //   and p >= every existing 3x3 neighbour (rsl_detect_common.h), i_lo <= i <= i_hi, p > thr_f,
 // with k(i) = min(n(i), max(1, ceil(rank * n(i)))) in fp64, n(i) the training cells that exist for range row i.
 //
-// One workgroup walks a strip of R range rows of one map (cfar_strip), RB rows per step.  A ring PW of RB + 2 hh
-// (hh = max(hr, 1)) fp32 power rows in LDS holds the whole window of every row it decides, each row with the wrapped
-// Doppler halo on both ends; a row outside the map holds +inf, which is never below p, so range truncation needs no
-// test in the count.  Per step, for the rows whose last window row has arrived:
+// One workgroup walks a strip of R range rows of one map (cfar_strip, rsl_cfar_common.h, which also holds the window
+// and the family's launcher), RB rows per step.  A ring PW of RB + 2 hh (hh = max(hr, 1)) fp32 power rows in LDS holds
+// the whole window of every row it decides, each row with the wrapped Doppler halo on both ends; a row outside the map
+// holds +inf, which is never below p, so range truncation needs no test in the count.  Per step, for the rows whose
+// last window row has arrived:
 //   1  gate: the cells that pass the 3x3 test, the range gate and the floor (about 1/9 of the cells in noise) are
 //      compacted into an LDS list (ballot, one LDS atomic per 64-cell word);
 //   2  count: one WAVE per candidate.  The lanes split the N training cells through a table of their ring offsets
@@ -27,24 +28,24 @@
 #endif
 #include <cmath>
 
-#include "rsl_common.h"
-#include "rsl_detect_common.h"
-#include "rsl_internal.h"
+#include "../../include/rsl.h"
+#include "rsl_cfar_common.h"
 
 namespace rsl {
 
 namespace {
 
-constexpr size_t kOscfarLdsMax = 160 * 1024;  // LDS of one gfx950 CU
-
 // LDS bytes of k_detect_oscfar with RB rows per step: the power ring (padded to 8 B), the result words, the
 // candidate list, its count and the rows' ranks, the offset table
-size_t oscfar_lds_bytes(int C, int hr, int hd, int RB) {
-  const int hh = hr > 1 ? hr : 1;
-  const size_t NP = (size_t)RB + 2 * hh, PS = (size_t)C + 2 * hd, W = ((size_t)C + 63) / 64;
-  const size_t box = (size_t)(2 * hr + 1) * (2 * hd + 1);
+constexpr size_t oscfar_lds_bytes(int C, CfarWindow win, int RB) {
+  const size_t NP = (size_t)RB + 2 * win.hh(), PS = (size_t)C + 2 * win.hd(), W = ((size_t)C + 63) / 64;
+  const size_t box = (size_t)(2 * win.hr() + 1) * win.nfull();
   return 8 * ((NP * PS + 1) / 2) + 8 * RB * W + 4 * ((size_t)RB * C + 1 + RB) + 4 * box;
 }
+// Monotone in C, hr and hd, so every window that rsl_detect_oscfar admits fits at the launcher's smallest RB.
+static_assert(oscfar_lds_bytes(RSL_CFAR_MAX_C, CfarWindow{0, 0, RSL_CFAR_MAX_HALF, RSL_CFAR_MAX_HALF}, 4) <=
+                  kCfarLdsMax,
+              "the largest OS-CFAR window must fit the LDS of a CU");
 
 // A float of the power ring by its byte offset (the ring starts the workgroup's LDS).
 RSL_DEV float ring_at(const float* PW, unsigned byte_off) {
@@ -53,16 +54,16 @@ RSL_DEV float ring_at(const float* PW, unsigned byte_off) {
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void k_detect_oscfar(const float2* __restrict__ rds, int S, int C, int W, int gr,
-                                                       int gd, int tr, int td, double rank, float alpha, float thr_f,
+__global__ __launch_bounds__(256) void k_detect_oscfar(const float2* __restrict__ rds, int S, int C, int W,
+                                                       CfarWindow win, double rank, float alpha, float thr_f,
                                                        int i_lo, int i_hi, int R, int RB,
                                                        unsigned long long* __restrict__ mask,
                                                        int* __restrict__ row_count, float* __restrict__ dbmap,
                                                        float* __restrict__ pk_pow) {
   extern __shared__ unsigned long long os_lds[];
-  const int hr = gr + tr, hd = gd + td, hh = max(hr, 1);
+  const int gr = win.gr, tr = win.tr, td = win.td, hr = win.hr(), hd = win.hd(), hh = win.hh();
   const int NP = RB + 2 * hh, PS = C + 2 * hd;
-  const int nfull = 2 * hd + 1, nguard = 2 * gd + 1;
+  const int nfull = win.nfull(), nguard = win.nguard();
   const int box = (2 * hr + 1) * nfull, N = box - (2 * gr + 1) * nguard;  // full-window training cells
   float* PW = reinterpret_cast<float*>(os_lds);                  // [NP][PS] power rows (+inf: row outside the map)
   unsigned long long* RES = os_lds + ((size_t)NP * PS + 1) / 2;  // [RB][W] decisions of the step's rows
@@ -110,8 +111,7 @@ __global__ __launch_bounds__(256) void k_detect_oscfar(const float2* __restrict_
       const float* dn = PW + (size_t)((u + 1) % NP) * PS + hd;
       const bool gate = (i >= i_lo && i <= i_hi);
       if (lane == 0) {  // the row's rank
-        const int vh = min(i, hr) + 1 + min(S - 1 - i, hr), vg = min(i, gr) + 1 + min(S - 1 - i, gr);
-        const int n = vh * nfull - vg * nguard;  // n(i) >= 1 (2 hr + 1 <= S)
+        const int n = win.cells(i, S);
         KR[r] = min(n, max(1, (int)ceil(rank * (double)n)));
       }
       for (int w = 0; w < W; ++w) {
@@ -182,31 +182,9 @@ __global__ __launch_bounds__(256) void k_detect_oscfar(const float2* __restrict_
   }
 }
 
-bool detect_oscfar_supported(int C, int hr, int hd) { return oscfar_lds_bytes(C, hr, hd, 4) <= kOscfarLdsMax; }
-
-hipError_t launch_detect_oscfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, int gr, int gd, int tr,
-                                int td, double rank, float alpha, const DetectArgs& d) {
-  if (F <= 0 || A <= 0 || S <= 0 || C <= 0) return hipSuccess;
-  const int hr = gr + tr, hd = gd + td;
-  const int W = (C + 63) / 64;
-  // rows per step: the largest of 16 / 8 / 4 that leaves room for three workgroups per CU, else 4
-  int RB = 4;
-  if (oscfar_lds_bytes(C, hr, hd, 16) <= 48 * 1024) RB = 16;
-  else if (oscfar_lds_bytes(C, hr, hd, 8) <= 48 * 1024) RB = 8;
-  const size_t lds = oscfar_lds_bytes(C, hr, hd, RB);
-  if (lds > kOscfarLdsMax) return hipErrorInvalidValue;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_detect_oscfar),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const int R = cfar_strip_rows(F, A, S);
-  const long long nblk = (long long)F * A * ((S + R - 1) / R);
-  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_detect_oscfar, dim3((unsigned)nblk), dim3(256), lds, st, rds, S, C, W, gr, gd, tr, td, rank,
-                     alpha, threshold_as_float(d.thr_p), d.i_lo, d.i_hi, R, RB, d.mask, d.row_count, d.dbmap,
-                     d.pk_pow);
-  return hipGetLastError();
+hipError_t launch_detect_oscfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, CfarWindow win,
+                                double rank, float alpha, const DetectArgs& d) {
+  return launch_cfar_strips(st, k_detect_oscfar, oscfar_lds_bytes, rds, F, A, S, C, win, d, rank, alpha);
 }
 
 }  // namespace rsl

@@ -100,7 +100,7 @@ class ChainConfig:
             raise ValueError(f"velocity_loss must be 'ls', 'huber' or 'tukey', not {self.velocity_loss!r}")
         if self.detector not in ('threshold', 'cfar'):
             raise ValueError(f"detector must be 'threshold' or 'cfar', not {self.detector!r}")
-        if self.cfar_method not in ('ca', 'os'):
+        if self.cfar_method not in tables.CFAR_METHODS:
             raise ValueError(f"cfar_method must be 'ca' or 'os', not {self.cfar_method!r}")
         if not 0.0 < float(self.cfar_rank) <= 1.0:
             raise ValueError(f'cfar_rank must lie in (0, 1], not {self.cfar_rank!r}')
@@ -145,13 +145,8 @@ class RadarChain:
         self.thr_p = tables.power_threshold(cfg.threshold_db)
         self.cfar_alpha = None
         if cfg.detector == 'cfar':
-            n = tables.cfar_training_cells(cfg.cfar_guard, cfg.cfar_train)
-            if cfg.cfar_alpha is not None:
-                self.cfar_alpha = float(cfg.cfar_alpha)
-            elif cfg.cfar_method == 'os':
-                self.cfar_alpha = tables.os_cfar_alpha(cfg.cfar_pfa, n, tables.os_cfar_rank(n, cfg.cfar_rank))
-            else:
-                self.cfar_alpha = tables.cfar_alpha(cfg.cfar_pfa, n)
+            self.cfar_alpha = float(cfg.cfar_alpha) if cfg.cfar_alpha is not None else tables.cfar_design_alpha(
+                cfg.cfar_method, cfg.cfar_pfa, cfg.cfar_guard, cfg.cfar_train, cfg.cfar_rank)
         d = cfg.antenna_spacing or cfg.lambda_c / 2
         self.grid = tables.azimuth_grid(cfg.search_range, cfg.search_resolution)
         steer_c128 = tables.steering_matrix(self.grid, np.arange(A) * d, cfg.lambda_c)
@@ -249,12 +244,8 @@ class RadarChain:
         self._group = group
         if cfg.detector == 'cfar':  # the CFAR detector rewrites the fused detector's mask, counts and peak powers
             out = dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow)
-            if cfg.cfar_method == 'os':
-                ctx.detect_oscfar(self.rds, cfg.cfar_guard, cfg.cfar_train, cfg.cfar_rank, self.cfar_alpha,
-                                  self.thr_p, self.i_lo, self.i_hi, out=out)
-            else:
-                ctx.detect_cfar(self.rds, cfg.cfar_guard, cfg.cfar_train, self.cfar_alpha, self.thr_p, self.i_lo,
-                                self.i_hi, out=out)
+            ctx.detect_cfar(self.rds, cfg.cfar_guard, cfg.cfar_train, self.cfar_alpha, self.thr_p, self.i_lo,
+                            self.i_hi, out=out, method=cfg.cfar_method, rank=cfg.cfar_rank)
             self._group = 1
         if offsets:
             ctx.offsets(self.mask, self.row_count, self.C, bufs=self.offs)

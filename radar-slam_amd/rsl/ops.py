@@ -117,19 +117,13 @@ def detect_peaks_cfar(rds, *, guard=(2, 2), train=(8, 8), pfa=1e-4, alpha=None, 
     method 'ca' (rsl_detect_cfar): alpha on the training mean (default: from pfa and the full-window count,
     tables.cfar_alpha).  method 'os' (rsl_detect_oscfar): alpha on the training cells' order statistic of rank
     ceil(rank * cells) (default: tables.os_cfar_alpha for the full window)."""
-    if method not in ('ca', 'os'):
+    if method not in tables.CFAR_METHODS:
         raise ValueError(f"method must be 'ca' or 'os', not {method!r}")
-    n = tables.cfar_training_cells(guard, train)
     thr = tables.power_threshold(threshold_db)
-    if method == 'os':
-        if alpha is None:
-            alpha = tables.os_cfar_alpha(pfa, n, tables.os_cfar_rank(n, rank))
-        return _detect_peaks(rds, ctx, want_db, lambda c, d: c.detect_oscfar(d, guard, train, rank, alpha, thr, i_lo,
-                                                                             i_hi, want_db=want_db))
     if alpha is None:
-        alpha = tables.cfar_alpha(pfa, n)
+        alpha = tables.cfar_design_alpha(method, pfa, guard, train, rank)
     return _detect_peaks(rds, ctx, want_db, lambda c, d: c.detect_cfar(d, guard, train, alpha, thr, i_lo, i_hi,
-                                                                       want_db=want_db))
+                                                                       want_db=want_db, method=method, rank=rank))
 
 
 # -- signatures as a pseudo-RDS [N, A, 1, 1] -------------------------------------------------------------

@@ -220,29 +220,26 @@ class Context:
         return mask, rc, db
 
     def detect_cfar(self, rds, guard, train, alpha: float, thr_power: float, i_lo: int, i_hi: int,
-                    want_db: bool = False, out=None):
-        """CA-CFAR detector (rsl_detect_cfar): guard / train = (range, doppler) half-sizes, alpha on the training
-        mean, thr_power the power floor (negative: none).  Outputs as detect (peak_pow row-compact, group 1)."""
+                    want_db: bool = False, out=None, *, method: str = 'ca', rank: float = 0.75):
+        """CFAR detector: guard / train = (range, doppler) half-sizes, thr_power the power floor (negative: none).
+        method 'ca' (rsl_detect_cfar): alpha on the training mean.  method 'os' (rsl_detect_oscfar): alpha on the
+        training cells' order statistic of rank k = ceil(rank * cells) (rank in (0, 1]).  Outputs as detect (peak_pow
+        row-compact, group 1)."""
         F, A, S, C = rds.shape
         mask, rc, db, pk = self._detect_out(rds, want_db, out)
         self._bind()
-        self.check(self.lib.rsl_detect_cfar(self.h, _ptr(rds), F, A, S, C, int(guard[0]), int(guard[1]),
-                                            int(train[0]), int(train[1]), float(alpha), float(thr_power), int(i_lo),
-                                            int(i_hi), _ptr(mask), _ptr(rc), _ptr(db), _ptr(pk)), 'rsl_detect_cfar')
+        head = (self.h, _ptr(rds), F, A, S, C, int(guard[0]), int(guard[1]), int(train[0]), int(train[1]))
+        tail = (float(alpha), float(thr_power), int(i_lo), int(i_hi), _ptr(mask), _ptr(rc), _ptr(db), _ptr(pk))
+        if method == 'os':
+            self.check(self.lib.rsl_detect_oscfar(*head, float(rank), *tail), 'rsl_detect_oscfar')
+        else:
+            self.check(self.lib.rsl_detect_cfar(*head, *tail), 'rsl_detect_cfar')
         return mask, rc, db
 
     def detect_oscfar(self, rds, guard, train, rank: float, alpha: float, thr_power: float, i_lo: int, i_hi: int,
                       want_db: bool = False, out=None):
-        """OS-CFAR detector (rsl_detect_oscfar): the window of detect_cfar, alpha on the training cells' order
-        statistic of rank k = ceil(rank * cells) (rank in (0, 1]).  Outputs as detect_cfar."""
-        F, A, S, C = rds.shape
-        mask, rc, db, pk = self._detect_out(rds, want_db, out)
-        self._bind()
-        self.check(self.lib.rsl_detect_oscfar(self.h, _ptr(rds), F, A, S, C, int(guard[0]), int(guard[1]),
-                                              int(train[0]), int(train[1]), float(rank), float(alpha),
-                                              float(thr_power), int(i_lo), int(i_hi), _ptr(mask), _ptr(rc), _ptr(db),
-                                              _ptr(pk)), 'rsl_detect_oscfar')
-        return mask, rc, db
+        """detect_cfar with method 'os'."""
+        return self.detect_cfar(rds, guard, train, alpha, thr_power, i_lo, i_hi, want_db, out, method='os', rank=rank)
 
     def offsets(self, mask, row_count, C: int, bufs=None):
         torch = self.torch

@@ -121,6 +121,16 @@ def os_cfar_alpha(pfa: float, n_train: int, k: int) -> float:
             hi = mid
 
 
+CFAR_METHODS = ('ca', 'os')  # cell averaging (rsl_detect_cfar), ordered statistic (rsl_detect_oscfar)
+
+
+def cfar_design_alpha(method: str, pfa: float, guard, train, rank: float = 0.75) -> float:
+    """The factor of a CFAR design, from its false-alarm rate and the full-window training-cell count: 'ca' on the
+    training mean (cfar_alpha), 'os' on the order statistic of rank ceil(rank * cells) (os_cfar_alpha)."""
+    n = cfar_training_cells(guard, train)
+    return os_cfar_alpha(pfa, n, os_cfar_rank(n, rank)) if method == 'os' else cfar_alpha(pfa, n)
+
+
 def azimuth_grid(search_range=(-90, 90), search_resolution=0.5):
     return np.arange(search_range[0], search_range[1] + search_resolution, search_resolution)
 

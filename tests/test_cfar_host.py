@@ -1,36 +1,22 @@
 """CPU checks of the CA-CFAR detector's host surface: the C ABI symbol, the alpha tables, the chain option and the
-numpy oracle (tests/cfar_ref.py) that the GPU tests compare against."""
-import ctypes
-import os
+numpy oracle (tests/cfar_ref.py) that the GPU tests compare against.  What the OS-CFAR host file checks in the same
+way is in tests/cfar_cases.py."""
 import re
 
 import numpy as np
 import pytest
 
+import cfar_cases as K
 import cfar_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'rsl.h')
-LIB = os.path.join(ROOT, 'radar-slam_amd', 'lib', 'librsl.so')
 
 
 def test_header_declares_detect_cfar():
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    m = re.search(r'int\s+rsl_detect_cfar\s*\(([^)]*)\)', src)
-    assert m, 'rsl_detect_cfar not declared in include/rsl.h'
-    names = [a.strip().split()[-1].lstrip('*') for a in m.group(1).split(',')]
-    assert names == ['h', 'rds', 'F', 'A', 'S', 'C', 'guard_r', 'guard_d', 'train_r', 'train_d', 'alpha', 'thr_power',
-                     'i_lo', 'i_hi', 'mask', 'row_count', 'db_map', 'peak_pow']
-    assert re.search(r'#define\s+RSL_CFAR_MAX_C\s+512\b', src)
+    K.header_declares('rsl_detect_cfar', [])
+    assert re.search(r'#define\s+RSL_CFAR_MAX_C\s+512\b', K.header_source())
 
 
 def test_library_exports_detect_cfar_and_rejects_null_handle():
-    from rsl import _lib
-    assert 'rsl_detect_cfar' in _lib.SIGNATURES
-    lib = _lib.load()
-    assert hasattr(lib, 'rsl_detect_cfar')
-    rc = lib.rsl_detect_cfar(None, None, 1, 1, 64, 64, 2, 2, 8, 8, 9.0, -1.0, 0, 63, None, None, None, None)
-    assert rc == _lib.RSL_ERR_INVALID == 1
+    K.library_exports_and_rejects_null_handle('rsl_detect_cfar', [])
 
 
 def test_cfar_tables():
@@ -48,6 +34,10 @@ def test_cfar_tables():
         assert (1 + a / n) ** (-n) == pytest.approx(1e-3, rel=1e-12)
     with pytest.raises(ValueError):
         tables.cfar_alpha(0.0, 16)
+    # the factor of a design is one of the two tables, bit for bit
+    assert tables.CFAR_METHODS == ('ca', 'os')
+    assert tables.cfar_design_alpha('ca', 1e-2, (2, 2), (8, 8)) == tables.cfar_alpha(1e-2, 416)
+    assert tables.cfar_design_alpha('os', 1e-2, (2, 2), (8, 8), 0.5) == tables.os_cfar_alpha(1e-2, 416, 208)
 
 
 def test_chain_config_detector_option():
@@ -61,28 +51,20 @@ def test_chain_config_detector_option():
 
 @pytest.mark.parametrize('window', [(1, 1, 2, 2), (0, 1, 0, 3), (1, 0, 3, 0), (2, 1, 3, 3)])
 def test_oracle_agrees_with_brute_force(window):
-    rng = np.random.default_rng(3)
-    z = (rng.standard_normal((12, 9)) + 1j * rng.standard_normal((12, 9))).astype(np.complex64)
-    z[4, 4] = 30.0
-    z[0, 8] = 20.0
+    z = K.brute_force_map()
     for alpha in (1.5, 4.0):
-        ref = R.cfar_reference(z, window, alpha)
+        ref = R.reference(z, window, alpha, method='ca')
         assert (ref['mask'] == R.brute_force(R.power(z), window, alpha)).all()
-    # the count of training cells: full window in the middle rows, truncated at the range edges
-    _, n = R.training_sum(R.power(z), window)
-    gr, gd, tr, td = window
-    full = (2 * (gr + tr) + 1) * (2 * (gd + td) + 1) - (2 * gr + 1) * (2 * gd + 1)
-    assert n[6] == full and n[11] == n[0]
-    assert n[0] < full if tr else n[0] == full  # a Doppler-only window loses nothing at the range edges
+    K.check_training_cells(R.training_sum(R.power(z), window)[1], window)
 
 
 def test_oracle_gate_and_floor():
     rng = np.random.default_rng(4)
     z = (rng.standard_normal((2, 20, 16)) + 1j * rng.standard_normal((2, 20, 16))).astype(np.complex64)
-    free = R.cfar_reference(z, (1, 1, 2, 2), 2.0)['mask']
-    gated = R.cfar_reference(z, (1, 1, 2, 2), 2.0, gate=(3, 10))['mask']
+    free = R.reference(z, (1, 1, 2, 2), 2.0)['mask']
+    gated = R.reference(z, (1, 1, 2, 2), 2.0, gate=(3, 10))['mask']
     assert (gated[:, 3:11] == free[:, 3:11]).all() and not gated[:, :3].any() and not gated[:, 11:].any()
-    floor = R.cfar_reference(z, (1, 1, 2, 2), 2.0, thr_power=6.0)
+    floor = R.reference(z, (1, 1, 2, 2), 2.0, thr_power=6.0)
     assert (floor['mask'] == (free & (floor['p'] > 6.0))).all()
     words = np.zeros((2, 20, 1), np.uint64)
     for a, i, j in zip(*np.nonzero(free)):

@@ -6,7 +6,7 @@ switched off.
 Switching the CFAR level off: with guard (0, 0), train (1, 1) and alpha = 1e-20 the CFAR condition p n > alpha sum
 holds for every cell the power floor thr_power > 0 lets through (sum <= 8 max p, and 1e-20 * 8 max p is far below
 thr_power n), so the rule reduces to k_detect's: 3x3 'reflect' local maximum, range gate, p > thr_power.
-test_cfar_rule_reduces_to_threshold_rule confirms that reduction on the CPU, cfar_ref.cfar_reference against the plain
+test_cfar_rule_reduces_to_threshold_rule confirms that reduction on the CPU, cfar_ref.reference against the plain
 rule on a random map.
 
 The cube is complex noise of variance 0.02 per sample, so the mean RDS power is S * C * 0.02; with that as the threshold
@@ -41,7 +41,7 @@ def test_cfar_rule_reduces_to_threshold_rule():
         g = np.zeros(S, bool)
         g[gate[0]:gate[1] + 1] = True
         plain = (p > thr) & (p >= R.neighbour_max(p)) & g[:, None]
-        ref = R.cfar_reference(z, CFAR_OFF['guard'] + CFAR_OFF['train'], CFAR_OFF['alpha'], thr_power=thr, gate=gate)
+        ref = R.reference(z, CFAR_OFF['guard'] + CFAR_OFF['train'], CFAR_OFF['alpha'], thr_power=thr, gate=gate)
         assert plain.any() and (ref['mask'] == plain).all()
         assert plain[:, gate[0]].any() or plain[:, gate[1]].any()
 

@@ -1,37 +1,24 @@
 """CPU checks of the OS-CFAR detector's host surface: the C ABI symbol, the rank and alpha tables, the chain option
-and the numpy oracle (tests/oscfar_ref.py) that the GPU tests compare against."""
+and the 'os' method of the numpy oracle (tests/cfar_ref.py) that the GPU tests compare against.  What the CA-CFAR
+host file checks in the same way is in tests/cfar_cases.py."""
 import math
-import os
 import re
 
 import numpy as np
 import pytest
 
-import cfar_ref as CA
-import oscfar_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'rsl.h')
+import cfar_cases as K
+import cfar_ref as R
 
 
 # -- 1. header and library ---------------------------------------------------------------------------------
 def test_header_declares_detect_oscfar():
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    m = re.search(r'int\s+rsl_detect_oscfar\s*\(([^)]*)\)', src)
-    assert m, 'rsl_detect_oscfar not declared in include/rsl.h'
-    names = [a.strip().split()[-1].lstrip('*') for a in m.group(1).split(',')]
-    assert names == ['h', 'rds', 'F', 'A', 'S', 'C', 'guard_r', 'guard_d', 'train_r', 'train_d', 'rank', 'alpha',
-                     'thr_power', 'i_lo', 'i_hi', 'mask', 'row_count', 'db_map', 'peak_pow']
-    assert re.search(r'#define\s+RSL_VERSION\s+2\b', src)  # additive: the ABI version stays
+    K.header_declares('rsl_detect_oscfar', ['rank'])
+    assert re.search(r'#define\s+RSL_VERSION\s+2\b', K.header_source())  # additive: the ABI version stays
 
 
 def test_library_exports_detect_oscfar_and_rejects_null_handle():
-    from rsl import _lib
-    assert 'rsl_detect_oscfar' in _lib.SIGNATURES
-    lib = _lib.load()
-    assert hasattr(lib, 'rsl_detect_oscfar')
-    rc = lib.rsl_detect_oscfar(None, None, 1, 1, 64, 64, 2, 2, 8, 8, 0.75, 9.0, -1.0, 0, 63, None, None, None, None)
-    assert rc == _lib.RSL_ERR_INVALID == 1
+    K.library_exports_and_rejects_null_handle('rsl_detect_oscfar', [0.75])
 
 
 # -- 2. alpha ----------------------------------------------------------------------------------------------
@@ -101,46 +88,34 @@ def test_chain_config_cfar_method():
 # -- 5. oracle against the counting form -------------------------------------------------------------------
 @pytest.mark.parametrize('window', [(1, 1, 2, 2), (0, 1, 0, 3), (1, 0, 3, 0), (2, 1, 3, 3)])
 def test_oracle_agrees_with_counting_brute_force(window):
-    rng = np.random.default_rng(3)  # the map of test_cfar_host
-    z = (rng.standard_normal((12, 9)) + 1j * rng.standard_normal((12, 9))).astype(np.complex64)
-    z[4, 4] = 30.0
-    z[0, 8] = 20.0
+    z = K.brute_force_map()
     p32 = R.power(z).astype(np.float32)
     for rank in (0.5, 0.75, 1.0):
         for alpha in (1.5, 4.0):
-            ref = R.oscfar_reference(z, window, rank, alpha)
+            ref = R.reference(z, window, alpha, method='os', rank=rank)
             assert not ref['near'].any()
             assert (ref['mask'] == R.brute_force_count(p32, window, rank, alpha)).all(), (rank, alpha)
-    ref = R.oscfar_reference(z, window, 0.75, 1.5)
-    n, k = ref['n'], ref['k']
-    gr, gd, tr, td = window
-    full = (2 * (gr + tr) + 1) * (2 * (gd + td) + 1) - (2 * gr + 1) * (2 * gd + 1)
-    assert n[6] == full and n[11] == n[0] and k[6] == R.rank_of(full, 0.75)
-    if tr:  # a truncated edge row keeps the fraction, not the rank
-        assert n[0] < full and k[0] < k[6] and k[11] < k[6]
+    ref = R.reference(z, window, 1.5, method='os', rank=0.75)
+    k = ref['k']
+    assert k[6] == R.rank_of(K.check_training_cells(ref['n'], window), 0.75)
+    if window[2]:  # a truncated edge row keeps the fraction, not the rank
+        assert k[0] < k[6] and k[11] < k[6]
     else:
-        assert n[0] == full and k[0] == k[6]
+        assert k[0] == k[6]
 
 
-# -- 6. two reflectors inside each other's window ----------------------------------------------------------
-def masking_scene():
-    rng = np.random.default_rng(11)
-    z = ((rng.standard_normal((64, 32)) + 1j * rng.standard_normal((64, 32))) / math.sqrt(2)).astype(np.complex64)
-    z[20, 10] = z[20, 13] = z[20, 16] = 30
-    return z
-
-
+# -- 6. three reflectors inside each other's window --------------------------------------------------------
 def test_masking_scene():
     from rsl import tables
-    z = masking_scene()
+    z = K.masking_scene()
     window, targets = (0, 1, 0, 6), [(20, 10), (20, 13), (20, 16)]
     n = tables.cfar_training_cells(window[:2], window[2:])
     assert n == 12
-    ca = CA.cfar_reference(z, window, tables.cfar_alpha(1e-4, n))['mask']
+    ca = R.reference(z, window, tables.cfar_alpha(1e-4, n), method='ca')['mask']
     assert not any(ca[t] for t in targets)  # the targets raise each other's training mean
     k = tables.os_cfar_rank(n, 0.75)
     assert k == 9
-    os_ = R.oscfar_reference(z, window, 0.75, tables.os_cfar_alpha(1e-4, n, k))['mask']
+    os_ = R.reference(z, window, tables.os_cfar_alpha(1e-4, n, k), method='os', rank=0.75)['mask']
     assert sorted(zip(*np.nonzero(os_))) == targets
 
 
@@ -153,9 +128,8 @@ def test_false_alarm_rate():
     S, Cn = 256, 128
     z = ((rng.standard_normal((S, Cn)) + 1j * rng.standard_normal((S, Cn))) / math.sqrt(2)).astype(np.complex64)
     window = (1, 1, 4, 4)
-    n = tables.cfar_training_cells(window[:2], window[2:])
-    alpha = tables.os_cfar_alpha(1e-2, n, tables.os_cfar_rank(n, 0.75))
-    ref = R.oscfar_reference(z, window, 0.75, alpha)
+    alpha = tables.cfar_design_alpha('os', 1e-2, window[:2], window[2:], 0.75)
+    ref = R.reference(z, window, alpha, method='os', rank=0.75)
     inner = slice(10, S - 10)
     rate = float((ref['p'][inner] > ref['level'][inner]).mean())
     print(f'\nOS-CFAR level crossings: {rate:.5f} at design 1e-2')

@@ -1,0 +1,108 @@
+"""What the measurement tools (cfar_bench, oscfar_bench, ssmusic_bench, vel_robust_bench) share: the event timer, the
+timed launches through rsl_timing_*, the whole-step measurement of a chain at configs[2], and the part runner.
+
+The part runner starts one child process per part (the tool itself with --part NAME), each under its own time limit;
+a child prints its result as one 'RESULT ' + JSON line.  The first part that fails or reaches its time limit ends the
+run with that exit status (124 for the time limit): nothing more is started on the GPU after it.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, 'radar-slam_amd'), ROOT]
+A, C, S, TC = 8, 128, 512, 51.2e-6  # configs[2]
+
+
+def events_ms(torch, fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def timing_read(ctx, torch, fn, reps):
+    """rsl_timing_read() after reps calls of fn with the handle's timing on."""
+    ctx.timing(True)
+    ctx.timing_reset()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    t = ctx.timing_read()
+    ctx.timing(False)
+    return t
+
+
+def timed(ctx, torch, fn, reps, kernel):
+    """Two warm-up calls, then ms per launch of fn from stream events and from rsl_timing_* under `kernel`."""
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    ev_ms = events_ms(torch, fn, reps)
+    ms, n = timing_read(ctx, torch, fn, reps)[kernel]
+    return {'ms_events': ev_ms, 'ms_rsl_timing': ms / max(n, 1), 'launches_timed': n}
+
+
+def chain_step(F, reps, head, **cfg_kw):
+    """ms per ch.run() of a configs[2] chain with the ChainConfig fields cfg_kw, its entry and cell totals and the
+    per-kernel times; head(ch) gives the leading keys of the result."""
+    import torch
+    import rsl
+    from bench import make_cubes
+    ctx = rsl.get_context(0)
+    cfg = rsl.ChainConfig(num_antennas=A, num_chirps=C, chirp_duration=TC, ridge=0.01, **cfg_kw)
+    ch = rsl.RadarChain(cfg, F, ctx)
+    cube = make_cubes(ctx, 1, F, A, C, TC, 0)[0]
+    for _ in range(2):
+        ch.run(cube)
+    torch.cuda.synchronize()
+    ms_step = events_ms(torch, lambda: ch.run(cube), reps)
+    t = timing_read(ctx, torch, lambda: ch.run(cube), reps)
+    ne, nc = ch.totals()
+    return {**head(ch), 'frames': F, 'reps': reps, 'ms_per_step': ms_step, 'frames_per_s': F / (ms_step * 1e-3),
+            'entries': ne, 'cells': nc, 'entries_per_frame': ne / F, 'cells_per_frame': nc / F,
+            'kernel_ms_per_step': {k: v[0] / reps for k, v in t.items() if v[1]}}
+
+
+def add_arguments(ap, out_name, limit=240):
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--limit', type=int, default=limit, help='seconds per measurement (child process)')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', out_name))
+    ap.add_argument('--part', help=argparse.SUPPRESS)  # the child: one measurement in this process
+
+
+def emit_result(res):
+    print('RESULT ' + json.dumps(res), flush=True)
+
+
+def run_parts(script, parts, passthrough, limit):
+    """Runs `script --part p *passthrough` for every p of parts, in order.  Returns (exit status, {p: result}); a
+    non-zero status is that of the first part that failed, and no part after it was started."""
+    results = {}
+    for p in parts:
+        cmd = [sys.executable, os.path.abspath(script), '--part', p, *map(str, passthrough)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
+        except subprocess.TimeoutExpired:
+            print(f'{p}: time limit of {limit} s reached; stopping', file=sys.stderr)
+            return 124, results
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith('RESULT ')]
+        if r.returncode != 0 or not line:
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+            print(f'{p}: failed with exit status {r.returncode}; stopping', file=sys.stderr)
+            return r.returncode or 1, results
+        results[p] = json.loads(line[-1][7:])
+        print(p, json.dumps(results[p]), flush=True)
+    return 0, results
+
+
+def write_json(path, out):
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')

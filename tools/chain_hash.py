@@ -1,5 +1,6 @@
 """SHA-256 of every output of one cfg2 chain batch (RDS, masks, row counts, peak powers, offsets, lists, DoA, ESPRIT,
-phase, velocity), of the detectors the chain does not run (rsl_detect and rsl_detect_cfar on the chain's RDS) and of the
+phase, velocity), of the detectors the chain does not run (rsl_detect, rsl_detect_cfar and rsl_detect_oscfar on the
+chain's RDS; window (2, 2) / (8, 8), fixed alpha, rank 0.75) and of the
 DoA paths it does not run (f32 scans, spectra, smoothed MUSIC; on the first NDOA cells of the chain's list) under the
 library RSL_LIBRARY: equal hashes across two libraries = bit-identical chains.  cfg1 / cfg2 / cfg5 reach the packed
 kernels, gen32 the general fused tile body, gen64 the register body on padded rows, unf48 the unfused fall-back.
@@ -45,7 +46,9 @@ for name, t in (('rds', ch.rds), ('mask', ch.mask), ('row_count', ch.row_count),
 # The detectors the chain does not run, on the chain's RDS: mask, row counts and the row-compact peak powers' prefix.
 W = (C + 63) // 64
 for name, run in (('det', lambda o: ctx.detect(ch.rds, ch.thr_p, ch.i_lo, ch.i_hi, out=o)),
-                  ('cfar', lambda o: ctx.detect_cfar(ch.rds, (2, 2), (8, 8), 12.0, ch.thr_p, ch.i_lo, ch.i_hi, out=o))):
+                  ('cfar', lambda o: ctx.detect_cfar(ch.rds, (2, 2), (8, 8), 12.0, ch.thr_p, ch.i_lo, ch.i_hi, out=o)),
+                  ('oscfar', lambda o: ctx.detect_oscfar(ch.rds, (2, 2), (8, 8), 0.75, 6.0, ch.thr_p, ch.i_lo, ch.i_hi,
+                                                         out=o))):
     o = dict(mask=torch.zeros((F, A, ch.S, W), dtype=torch.int64, device=ctx.device),
              row_count=torch.zeros((F, A, ch.S), dtype=torch.int32, device=ctx.device),
              peak_pow=torch.zeros((F, A, ch.S, C), dtype=torch.float32, device=ctx.device))

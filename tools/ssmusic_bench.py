@@ -9,35 +9,13 @@ Each (M, L) runs in a child process of its own under its own time limit; the fir
 Writes profiles/ssmusic_bench.json.   python tools/ssmusic_bench.py [--frames 64] [--cells 35000] [--reps 5]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, 'radar-slam_amd'), ROOT]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bench_parts as B  # noqa: E402
+
 S, C, G = 512, 128, 361
-
-
-def _timed(ctx, torch, fn, reps):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    ev_ms = a.elapsed_time(b) / reps
-    ctx.timing(True)
-    ctx.timing_reset()
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    ms, n = ctx.timing_read()['doa_scan']
-    ctx.timing(False)
-    return {'ms_events': ev_ms, 'ms_rsl_timing': ms / max(n, 1), 'launches_timed': n}
 
 
 def part(M, L, F, per_frame, reps):
@@ -68,7 +46,7 @@ def part(M, L, F, per_frame, reps):
     res = {'M': M, 'L': L, 'G': G, 'frames': F, 'cells_per_frame': per_frame, 'cells': N, 'reps': reps,
            'toeplitz_path': bool(steer['toeplitz'])}
     for name, fn in runs.items():
-        r = _timed(ctx, torch, fn, reps)
+        r = B.timed(ctx, torch, fn, reps, 'doa_scan')
         r['cells_per_s'] = N / (r['ms_rsl_timing'] * 1e-3)
         res[name] = r
     runs['doa_smoothed_estimate']()  # the order the estimate mode chose on these cells
@@ -83,37 +61,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=64)
     ap.add_argument('--cells', type=int, default=35000, help='cells per frame')
-    ap.add_argument('--reps', type=int, default=5)
-    ap.add_argument('--limit', type=int, default=240, help='seconds per measurement (child process)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ssmusic_bench.json'))
-    ap.add_argument('--part', help=argparse.SUPPRESS)
+    B.add_arguments(ap, 'ssmusic_bench.json')
     args = ap.parse_args()
     if args.part:
         M, L = (int(v) for v in args.part.split(':'))
-        print('RESULT ' + json.dumps(part(M, L, args.frames, args.cells, args.reps)), flush=True)
+        B.emit_result(part(M, L, args.frames, args.cells, args.reps))
         return 0
-    out = {'what': 'spatially smoothed MUSIC (rsl_doa_smoothed) next to the Toeplitz one-angle scan (rsl_doa) on the '
-                   'same cells, one GPU, one stream (tools/ssmusic_bench.py)', 'runs': []}
-    for p in ('8:6', '16:8'):
-        cmd = [sys.executable, os.path.abspath(__file__), '--part', p, '--frames', str(args.frames), '--cells',
-               str(args.cells), '--reps', str(args.reps)]
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
-        except subprocess.TimeoutExpired:
-            print(f'{p}: time limit of {args.limit} s reached; stopping', file=sys.stderr)
-            return 124
-        line = [ln for ln in r.stdout.splitlines() if ln.startswith('RESULT ')]
-        if r.returncode != 0 or not line:
-            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
-            print(f'{p}: failed with exit status {r.returncode}; stopping', file=sys.stderr)
-            return r.returncode or 1
-        res = json.loads(line[-1][7:])
-        print(p, json.dumps(res), flush=True)
-        out['runs'].append(res)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(out, f, indent=1)
-        f.write('\n')
+    parts = ('8:6', '16:8')
+    rc, res = B.run_parts(__file__, parts, ['--frames', args.frames, '--cells', args.cells, '--reps', args.reps],
+                          args.limit)
+    if rc:
+        return rc
+    B.write_json(args.out, {
+        'what': 'spatially smoothed MUSIC (rsl_doa_smoothed) next to the Toeplitz one-angle scan (rsl_doa) on the '
+                'same cells, one GPU, one stream (tools/ssmusic_bench.py)', 'runs': [res[p] for p in parts]})
     return 0
 
 

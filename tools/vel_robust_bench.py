@@ -11,25 +11,14 @@ The measurement runs in a child process under a time limit.  Writes profiles/vel
     python tools/vel_robust_bench.py [--frames 2000] [--reps 5]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, 'radar-slam_amd'), ROOT]
-A, C, S, TC = 8, 128, 512, 51.2e-6
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bench_parts as B  # noqa: E402
+from bench_parts import A, C, S, TC  # noqa: E402
+
 ITERS, TOL = 30, 1e-9
-
-
-def _events(torch, fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def measure(F, reps):
@@ -59,18 +48,7 @@ def measure(F, reps):
     res = {'frames': F, 'reps': reps, 'cells': nc, 'cells_per_frame': nc / F, 'iters': ITERS, 'tol': TOL,
            'given_scale': sigma, 'bytes_per_pass': nc * 16, 'variants': {}}
     for name, fn in runs.items():
-        for _ in range(2):
-            fn()
-        torch.cuda.synchronize()
-        ev_ms = _events(torch, fn, reps)
-        ctx.timing(True)
-        ctx.timing_reset()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        ms, n = ctx.timing_read()['velocity']
-        ctx.timing(False)
-        r = {'ms_events': ev_ms, 'ms_rsl_timing': ms / max(n, 1), 'launches_timed': n}
+        r = B.timed(ctx, torch, fn, reps, 'velocity')
         if name != 'k_velocity':
             o = out.cpu().numpy()
             it = np.abs(o[:, 7])
@@ -91,35 +69,17 @@ def measure(F, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=2000)
-    ap.add_argument('--reps', type=int, default=5)
-    ap.add_argument('--limit', type=int, default=300, help='seconds for the measurement (child process)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'vel_robust_bench.json'))
-    ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)
+    B.add_arguments(ap, 'vel_robust_bench.json', limit=300)
     args = ap.parse_args()
-    if args.child:
-        print('RESULT ' + json.dumps(measure(args.frames, args.reps)), flush=True)
+    if args.part:
+        B.emit_result(measure(args.frames, args.reps))
         return 0
-    cmd = [sys.executable, os.path.abspath(__file__), '--child', '--frames', str(args.frames), '--reps',
-           str(args.reps)]
-    try:
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
-    except subprocess.TimeoutExpired:
-        print(f'time limit of {args.limit} s reached; stopping', file=sys.stderr)
-        return 124
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith('RESULT ')]
-    if r.returncode != 0 or not line:
-        sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
-        print(f'failed with exit status {r.returncode}', file=sys.stderr)
-        return r.returncode or 1
-    res = json.loads(line[-1][7:])
-    out = {'what': 'robust velocity solve at configs[2] (A8 C128 S512) on the chain\'s own lists, one GPU, one stream '
-                   '(tools/vel_robust_bench.py)', **res}
-    for name, v in res['variants'].items():
-        print(name, json.dumps(v), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(out, f, indent=1)
-        f.write('\n')
+    rc, res = B.run_parts(__file__, ['measure'], ['--frames', args.frames, '--reps', args.reps], args.limit)
+    if rc:
+        return rc
+    B.write_json(args.out, {
+        'what': 'robust velocity solve at configs[2] (A8 C128 S512) on the chain\'s own lists, one GPU, one stream '
+                '(tools/vel_robust_bench.py)', **res['measure']})
     return 0
 
 
