@@ -152,6 +152,42 @@ int rsl_detect_oscfar(rsl_handle h, const void* rds, int F, int A, int S, int C,
                       int train_r, int train_d, double rank, double alpha, double thr_power, int i_lo, int i_hi,
                       void* mask, void* row_count, void* db_map, void* peak_pow);
 
+/* Non-coherent integration: the antenna-summed power map, the input of rsl_detect_power and an output in its own
+ *     right (the integrated range-Doppler map).  There is no reference counterpart: this comment is the specification.
+ *     rds c64 [F, A, S, C] -> power f32 [F, S, C]:
+ *       P[f, i, j] = ((p_0 + p_1) + p_2) + ... + p_{A-1}   in fp32,
+ *     where p_a is the fp32 power of rds[f, a, i, j] exactly as the detectors form it (fmaf(re, re, im * im)).  The
+ *     antenna order is fixed, so the result is deterministic; its relative error against the exact sum is at most
+ *     (A + 2) 2^-24.  For A = 1 it is bit-identical to the power that rsl_detect / rsl_detect_cfar /
+ *     rsl_detect_oscfar compute for that cell.
+ *     F = 0 is valid and launches nothing.  RSL_ERR_INVALID: a null pointer with F > 0, A, S or C <= 0, A > 32 (the
+ *     width of c_amask).  Timed under RSL_K_DETECT. */
+int rsl_power_integrate(rsl_handle h, const void* rds, int F, int A, int S, int C, void* power);
+
+/* The three detection rules on a real power map: power f32 [F, S, C], F maps, one per frame (rsl_power_integrate's
+ *     output, or any non-negative map).  rule selects
+ *       RSL_RULE_THRESHOLD  rsl_detect's rule (guard_*, train_*, rank and alpha are ignored),
+ *       RSL_RULE_CA         rsl_detect_cfar's rule (rank is ignored),
+ *       RSL_RULE_OS         rsl_detect_oscfar's rule,
+ *     word for word as specified there, with p read from the map instead of formed from a complex value: the same
+ *     window (Doppler wraps, range truncates), n(i) and k(i), the same strict comparisons, the add-only fp32 training
+ *     sum of CA, the exact count of OS, the 3x3 rule, the range gate and the floor (double)p > thr_power.  The kernels
+ *     are those of the per-antenna entry points, instantiated for a real element.
+ *     Outputs as rsl_detect* with A = 1: mask u64 [F, S, W], row_count i32 [F, S], db_map f32 [F, S, C] (nullable) =
+ *     10 log10f(P + 1e-12f), peak_pow f32 [F, S, C] (nullable) row-compact, group 1; rsl_peak_offsets / rsl_peak_emit
+ *     take them with A = 1 (every cell is then one entry of antenna 0 and its c_amask is 1).
+ *     Factor: in exponential noise the sum of A looks is Gamma(A)-distributed, so alpha for a false-alarm rate differs
+ *     from the one-look formulas above; the host layer designs it (rsl/tables.py: cfar_alpha_nci, os_cfar_alpha_nci).
+ *     Errors: the cases of the per-antenna function of the rule (RSL_RULE_THRESHOLD: those of rsl_detect); an unknown
+ *     rule is RSL_ERR_INVALID.  A negative, non-finite or NaN value in power is the caller's business.
+ *     F = 0 is valid and launches nothing.  Timed under RSL_K_DETECT. */
+#define RSL_RULE_THRESHOLD 0
+#define RSL_RULE_CA 1
+#define RSL_RULE_OS 2
+int rsl_detect_power(rsl_handle h, const void* power, int F, int S, int C, int rule, int guard_r, int guard_d,
+                     int train_r, int train_d, double rank, double alpha, double thr_power, int i_lo, int i_hi,
+                     void* mask, void* row_count, void* db_map, void* peak_pow);
+
 /* a7 + a8 fused: range FFT, then Doppler FFT + fftshift + RDS store + peak detection in one kernel (the RDS is
  *     not re-read for detection).  Arguments as rsl_rds and rsl_detect; falls back to the two calls when the
  *     shape is not covered (C not a power of two <= 1024, or its range-bin tiling does not divide S/2).

@@ -321,11 +321,13 @@ int rsl_detect(rsl_handle h, const void* rds, int F, int A, int S, int C, double
   return hip_check(h, rsl::launch_detect(h->stream, (const float2*)rds, F, A, S, C, det), "detect");
 }
 
-// rsl_detect_cfar (rank null) and rsl_detect_oscfar (its rank): the checks in the order the header lists them, `fn`
-// naming the entry point in the error text, then the launch.  No LDS check: every window within the limits fits at
-// every C <= RSL_CFAR_MAX_C, which rsl_cfar.hip and rsl_oscfar.hip assert at compile time.
-static int detect_cfar_family(rsl_handle h, const std::string& fn, const void* rds, int F, int A, int S, int C,
-                              rsl::CfarWindow win, const double* rank, double alpha, const rsl::DetectArgs& det) {
+// rsl_detect_cfar (rank null) and rsl_detect_oscfar (its rank), and rsl_detect_power's two CFAR rules (power: `maps`
+// holds F fp32 power maps and A is 1): the checks in the order the header lists them, `fn` naming the entry point in the
+// error text, then the launch.  No LDS check: every window within the limits fits at every C <= RSL_CFAR_MAX_C, which
+// rsl_cfar.hip and rsl_oscfar.hip assert at compile time.
+static int detect_cfar_family(rsl_handle h, const std::string& fn, const void* maps, bool power, int F, int A, int S,
+                              int C, rsl::CfarWindow win, const double* rank, double alpha,
+                              const rsl::DetectArgs& det) {
   if (!h) return RSL_ERR_INVALID;
   if (F < 0 || A <= 0 || S <= 0 || C <= 0 || S > 8192) return fail(h, RSL_ERR_INVALID, fn + ": bad shape");
   if (win.gr < 0 || win.gd < 0 || win.tr < 0 || win.td < 0 || win.tr + win.td < 1)
@@ -337,28 +339,72 @@ static int detect_cfar_family(rsl_handle h, const std::string& fn, const void* r
   if (C > RSL_CFAR_MAX_C) return fail(h, RSL_ERR_UNSUPPORTED, fn + ": C above RSL_CFAR_MAX_C");
   if (rank && !(*rank > 0 && *rank <= 1)) return fail(h, RSL_ERR_INVALID, fn + ": rank must lie in (0, 1]");
   if (F == 0) return RSL_OK;
-  if (!rds || !det.mask || !det.row_count) return fail(h, RSL_ERR_INVALID, fn + ": null pointer");
+  if (!maps || !det.mask || !det.row_count) return fail(h, RSL_ERR_INVALID, fn + ": null pointer");
   Scope sc(h, RSL_K_DETECT);
-  const float2* z = (const float2*)rds;
+  const float2* z = (const float2*)maps;
+  const float* p = (const float*)maps;
+  const float af = (float)alpha;
   if (rank)
-    return hip_check(h, rsl::launch_detect_oscfar(h->stream, z, F, A, S, C, win, *rank, (float)alpha, det),
+    return hip_check(h,
+                     power ? rsl::launch_detect_oscfar(h->stream, p, F, S, C, win, *rank, af, det)
+                           : rsl::launch_detect_oscfar(h->stream, z, F, A, S, C, win, *rank, af, det),
                      "detect_oscfar");
-  return hip_check(h, rsl::launch_detect_cfar(h->stream, z, F, A, S, C, win, (float)alpha, det), "detect_cfar");
+  return hip_check(h,
+                   power ? rsl::launch_detect_cfar(h->stream, p, F, S, C, win, af, det)
+                         : rsl::launch_detect_cfar(h->stream, z, F, A, S, C, win, af, det),
+                   "detect_cfar");
 }
 
 int rsl_detect_cfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d, int train_r,
                     int train_d, double alpha, double thr_power, int i_lo, int i_hi, void* mask, void* row_count,
                     void* db_map, void* peak_pow) {
-  return detect_cfar_family(h, "rsl_detect_cfar", rds, F, A, S, C, {guard_r, guard_d, train_r, train_d}, nullptr,
-                            alpha, detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow));
+  return detect_cfar_family(h, "rsl_detect_cfar", rds, false, F, A, S, C, {guard_r, guard_d, train_r, train_d},
+                            nullptr, alpha, detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow));
 }
 
 int rsl_detect_oscfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d,
                       int train_r, int train_d, double rank, double alpha, double thr_power, int i_lo, int i_hi,
                       void* mask, void* row_count, void* db_map, void* peak_pow) {
   // the factor is checked as the float the kernel multiplies by
-  return detect_cfar_family(h, "rsl_detect_oscfar", rds, F, A, S, C, {guard_r, guard_d, train_r, train_d}, &rank,
-                            (float)alpha, detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow));
+  return detect_cfar_family(h, "rsl_detect_oscfar", rds, false, F, A, S, C, {guard_r, guard_d, train_r, train_d},
+                            &rank, (float)alpha,
+                            detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow));
+}
+
+int rsl_power_integrate(rsl_handle h, const void* rds, int F, int A, int S, int C, void* power) {
+  if (!h) return RSL_ERR_INVALID;
+  if (F < 0 || A <= 0 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_power_integrate: bad shape");
+  if (A > 32) return fail(h, RSL_ERR_INVALID, "rsl_power_integrate: more than 32 antennas");
+  if (F == 0) return RSL_OK;
+  if (!rds || !power) return fail(h, RSL_ERR_INVALID, "rsl_power_integrate: null pointer");
+  Scope sc(h, RSL_K_DETECT);
+  return hip_check(h, rsl::launch_power_integrate(h->stream, (const float2*)rds, F, A, S, C, (float*)power),
+                   "power_integrate");
+}
+
+int rsl_detect_power(rsl_handle h, const void* power, int F, int S, int C, int rule, int guard_r, int guard_d,
+                     int train_r, int train_d, double rank, double alpha, double thr_power, int i_lo, int i_hi,
+                     void* mask, void* row_count, void* db_map, void* peak_pow) {
+  if (!h) return RSL_ERR_INVALID;
+  const rsl::DetectArgs det = detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow);
+  const rsl::CfarWindow win = {guard_r, guard_d, train_r, train_d};
+  switch (rule) {
+    case RSL_RULE_THRESHOLD: {  // rsl_detect's checks; window, rank and alpha are not looked at
+      if (F < 0 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_detect_power: bad shape");
+      if (F == 0) return RSL_OK;
+      if (!power || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect_power: null pointer");
+      if ((size_t)(18 * (size_t)C * 4) > 64 * 1024)
+        return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect_power: C too large");
+      Scope sc(h, RSL_K_DETECT);
+      return hip_check(h, rsl::launch_detect(h->stream, (const float*)power, F, S, C, det), "detect");
+    }
+    case RSL_RULE_CA:
+      return detect_cfar_family(h, "rsl_detect_power", power, true, F, 1, S, C, win, nullptr, alpha, det);
+    case RSL_RULE_OS:
+      return detect_cfar_family(h, "rsl_detect_power", power, true, F, 1, S, C, win, &rank, (float)alpha, det);
+    default:
+      return fail(h, RSL_ERR_INVALID, "rsl_detect_power: unknown rule");
+  }
 }
 
 int rsl_peak_offsets(rsl_handle h, const void* mask, const void* row_count, int F, int A, int S, int C,

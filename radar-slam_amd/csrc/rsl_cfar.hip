@@ -42,7 +42,9 @@ static_assert(cfar_lds_bytes(RSL_CFAR_MAX_C, CfarWindow{0, 0, RSL_CFAR_MAX_HALF,
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ rds, int S, int C, int W,
+// T: the map's element, float2 (c64 RDS, p = |z|^2) or float (a power map, rsl_detect_power): cell_power.
+template <class T>
+__global__ __launch_bounds__(256) void k_detect_cfar(const T* __restrict__ rds, int S, int C, int W,
                                                      CfarWindow win, float alpha, float thr_f, int i_lo, int i_hi,
                                                      int R, int RB,
                                                      unsigned long long* __restrict__ mask,
@@ -61,7 +63,7 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
   const int i0 = sp.i0, Re = sp.Re;
   const int UL = Re + 2 * hh;  // rows the strip loads: u = 0 .. UL-1 is range row ibase + u
   const int ibase = i0 - hh;
-  const float2* base = rds + fa * S * C;
+  const T* base = rds + fa * S * C;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
   int done = hh;  // next row (u) to decide
@@ -122,7 +124,7 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
         const unsigned long long mx = MX[(size_t)(u % NR) * W + w];
         const bool in = j < C;
         float p = 0.f;
-        if (in && (dbmap || (gate && mx))) p = cabs2(base[(size_t)i * C + j]);
+        if (in && (dbmap || (gate && mx))) p = cell_power(base[(size_t)i * C + j]);
         bool pk = false;
         if (gate && mx && in) {  // gate, mx: wave-uniform
           float s = 0.f;
@@ -144,7 +146,12 @@ __global__ __launch_bounds__(256) void k_detect_cfar(const float2* __restrict__ 
 
 hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, CfarWindow win,
                               float alpha, const DetectArgs& d) {
-  return launch_cfar_strips(st, k_detect_cfar, cfar_lds_bytes, rds, F, A, S, C, win, d, alpha);
+  return launch_cfar_strips(st, k_detect_cfar<float2>, cfar_lds_bytes, rds, F, A, S, C, win, d, alpha);
+}
+
+hipError_t launch_detect_cfar(hipStream_t st, const float* power, int F, int S, int C, CfarWindow win, float alpha,
+                              const DetectArgs& d) {
+  return launch_cfar_strips(st, k_detect_cfar<float>, cfar_lds_bytes, power, F, 1, S, C, win, d, alpha);
 }
 
 }  // namespace rsl

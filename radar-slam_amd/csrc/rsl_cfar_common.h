@@ -46,15 +46,17 @@ RSL_DEV CfarStrip cfar_strip(int S, int R) {
 inline int cfar_strip_rows(int F, int A, int S) { return (long long)F * A * ((S + 127) / 128) < 1024 ? 32 : 128; }
 
 // One wave's share of a step's rows: the fp32 powers of the strip rows u = u0, u0 + 4, u0 + 8, ... < u1 (u0 = the
-// step's first row + the wave's index; strip row u is range row ibase + u of the map `base`, c64 [S][C]) into their
+// step's first row + the wave's index; strip row u is range row ibase + u of the map `base`, [S][C] of c64 values or
+// of fp32 powers: cell_power) into their
 // rows of the LDS ring PW [NP][PS], PS = C + 2 hd: ring row u % NP, whose first and last hd cells repeat the other end
 // of the row (Doppler wraps); a row outside the map holds `outside`.  Four rows at a time, their loads issued together
 // (a row outside the map, or past u1, re-reads a row of the map and drops the value): one load in flight per wave
 // leaves the kernel waiting on memory latency.
-RSL_DEV void power_rows_halo(float* PW, int NP, int PS, const float2* __restrict__ base, int ibase, int u0, int u1,
-                             int S, int C, int hd, float outside) {
+template <class T>
+RSL_DEV void power_rows_halo(float* PW, int NP, int PS, const T* __restrict__ base, int ibase, int u0, int u1, int S,
+                             int C, int hd, float outside) {
   for (int ub = u0; ub < u1; ub += 16) {
-    const float2* src[4];
+    const T* src[4];
     float* dst[4];
     bool valid[4];
 #pragma unroll
@@ -65,14 +67,14 @@ RSL_DEV void power_rows_halo(float* PW, int NP, int PS, const float2* __restrict
       dst[m] = u < u1 ? PW + (size_t)(u % NP) * PS : nullptr;
     }
     for (int j = threadIdx.x & 63; j < C; j += 64) {
-      float2 z[4];
+      T z[4];
 #pragma unroll
       for (int m = 0; m < 4; ++m) z[m] = src[m][j];
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         float* pr = dst[m];
         if (!pr) continue;
-        const float p = valid[m] ? cabs2(z[m]) : outside;
+        const float p = valid[m] ? cell_power(z[m]) : outside;
         pr[hd + j] = p;
         if (j < hd) pr[hd + C + j] = p;         // right halo: columns 0 .. hd-1
         if (j >= C - hd) pr[j - (C - hd)] = p;  // left halo: columns C-hd .. C-1
@@ -81,11 +83,12 @@ RSL_DEV void power_rows_halo(float* PW, int NP, int PS, const float2* __restrict
   }
 }
 
-// The launcher of the family.  `kernel` takes (rds, S, C, W, window, extra..., thr_f, i_lo, i_hi, R, RB, mask,
-// row_count, dbmap, pk_pow) and lds_bytes(C, window, RB) bytes of dynamic LDS, one workgroup of 256 per strip.
-template <typename... KArgs, typename... Extra>
+// The launcher of the family.  `kernel` takes (map, S, C, W, window, extra..., thr_f, i_lo, i_hi, R, RB, mask,
+// row_count, dbmap, pk_pow) and lds_bytes(C, window, RB) bytes of dynamic LDS, one workgroup of 256 per strip.  The
+// F * A maps are c64 RDS maps (T = float2) or fp32 power maps (T = float).
+template <class T, typename... KArgs, typename... Extra>
 hipError_t launch_cfar_strips(hipStream_t st, void (*kernel)(KArgs...), size_t (*lds_bytes)(int, CfarWindow, int),
-                              const float2* rds, int F, int A, int S, int C, CfarWindow win, const DetectArgs& d,
+                              const T* rds, int F, int A, int S, int C, CfarWindow win, const DetectArgs& d,
                               Extra... extra) {
   if (F <= 0 || A <= 0 || S <= 0 || C <= 0) return hipSuccess;
   const int W = (C + 63) / 64;

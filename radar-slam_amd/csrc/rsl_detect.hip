@@ -24,7 +24,9 @@ float threshold_as_float(double thr) {
   return t;
 }
 
-__global__ __launch_bounds__(256) void k_detect(const float2* __restrict__ rds, int S, int C, int W, float thr_f,
+// T: the map's element, float2 (c64 RDS, p = |z|^2) or float (a power map, rsl_detect_power): cell_power.
+template <class T>
+__global__ __launch_bounds__(256) void k_detect(const T* __restrict__ rds, int S, int C, int W, float thr_f,
                                                 int i_lo, int i_hi, unsigned long long* __restrict__ mask,
                                                 int* __restrict__ row_count, float* __restrict__ dbmap,
                                                 float* __restrict__ pk_pow) {
@@ -34,11 +36,11 @@ __global__ __launch_bounds__(256) void k_detect(const float2* __restrict__ rds, 
   const long fa = blockIdx.x / nib;
   const int i0 = ib * kDetRows;
   const int nrows = min(kDetRows, S - i0);
-  const float2* base = rds + (size_t)fa * S * C;
+  const T* base = rds + (size_t)fa * S * C;
   for (int idx = threadIdx.x; idx < (nrows + 2) * C; idx += 256) {
     const int r = idx / C, j = idx - r * C;
     const int i = i0 - 1 + r;
-    pw[idx] = (i >= 0 && i < S) ? cabs2(base[(size_t)i * C + j]) : -1.f;  // outside the map: never read
+    pw[idx] = (i >= 0 && i < S) ? cell_power(base[(size_t)i * C + j]) : -1.f;  // outside the map: never read
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -560,14 +562,23 @@ hipError_t launch_emit2(hipStream_t st, const unsigned long long* mask, const un
   });
 }
 
-hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S, int C, const DetectArgs& d) {
+template <class T>
+static hipError_t launch_detect_maps(hipStream_t st, const T* maps, int F, int A, int S, int C, const DetectArgs& d) {
   if (F <= 0 || A <= 0 || S <= 0 || C <= 0) return hipSuccess;
   const int W = (C + 63) / 64;
   const long nblk = (long)F * A * ((S + kDetRows - 1) / kDetRows);
   const size_t lds = sizeof(float) * (kDetRows + 2) * (size_t)C;
-  hipLaunchKernelGGL(k_detect, dim3((unsigned)nblk), dim3(256), lds, st, rds, S, C, W, threshold_as_float(d.thr_p),
-                     d.i_lo, d.i_hi, d.mask, d.row_count, d.dbmap, d.pk_pow);
+  hipLaunchKernelGGL(k_detect<T>, dim3((unsigned)nblk), dim3(256), lds, st, maps, S, C, W,
+                     threshold_as_float(d.thr_p), d.i_lo, d.i_hi, d.mask, d.row_count, d.dbmap, d.pk_pow);
   return hipGetLastError();
+}
+
+hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S, int C, const DetectArgs& d) {
+  return launch_detect_maps(st, rds, F, A, S, C, d);
+}
+
+hipError_t launch_detect(hipStream_t st, const float* power, int F, int S, int C, const DetectArgs& d) {
+  return launch_detect_maps(st, power, F, 1, S, C, d);
 }
 
 hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const int* row_count, int F, int A, int S,

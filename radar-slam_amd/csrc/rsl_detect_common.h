@@ -13,6 +13,11 @@
 
 namespace rsl {
 
+// The fp32 power p of a map element: |z|^2 of a c64 RDS value, or the value itself where the map already holds powers
+// (rsl_detect_power: the antenna-summed map of rsl_power_integrate).  The only place a detector's element type shows.
+RSL_DEV float cell_power(float2 z) { return cabs2(z); }
+RSL_DEV float cell_power(float p) { return p; }
+
 // The largest of the 3x3 window around column j of row `mid` (the cell itself included), rows of C powers in LDS.
 // 'reflect' edges: a neighbour outside the map repeats a cell of the window.  So the row above (has_up false) or below
 // (has_dn false) is read as `mid` again, which keeps the row loads unconditional, and the column left of 0 or right of

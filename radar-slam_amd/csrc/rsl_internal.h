@@ -73,6 +73,16 @@ hipError_t launch_detect_cfar(hipStream_t st, const float2* rds, int F, int A, i
 // training cells (k(i) = min(n(i), max(1, ceil(rank n(i))))) in place of their mean.
 hipError_t launch_detect_oscfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, CfarWindow win,
                                 double rank, float alpha, const DetectArgs& det);
+// rsl_nci.hip: non-coherent integration, rds c64 [F, A, S, C] -> power f32 [F, S, C], the fp32 sum over the antennas
+// in antenna order.
+hipError_t launch_power_integrate(hipStream_t st, const float2* rds, int F, int A, int S, int C, float* power);
+// The three detectors on F fp32 power maps [F, S, C] in place of the F * A c64 maps (rsl_detect_power): the same
+// kernels with the element type float (cell_power, rsl_detect_common.h), outputs as with A = 1.
+hipError_t launch_detect(hipStream_t st, const float* power, int F, int S, int C, const DetectArgs& det);
+hipError_t launch_detect_cfar(hipStream_t st, const float* power, int F, int S, int C, CfarWindow win, float alpha,
+                              const DetectArgs& det);
+hipError_t launch_detect_oscfar(hipStream_t st, const float* power, int F, int S, int C, CfarWindow win, double rank,
+                                float alpha, const DetectArgs& det);
 // Per-frame offsets of peak entries (antenna-major) and union cells (range-major).
 hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const int* row_count, int F, int A, int S,
                           int C, int* entry_row_off, int* cell_row_off, int* cell_row_cnt, long long* entry_base,

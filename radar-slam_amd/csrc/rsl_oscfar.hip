@@ -54,7 +54,9 @@ RSL_DEV float ring_at(const float* PW, unsigned byte_off) {
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void k_detect_oscfar(const float2* __restrict__ rds, int S, int C, int W,
+// T: the map's element, float2 (c64 RDS, p = |z|^2) or float (a power map, rsl_detect_power): cell_power.
+template <class T>
+__global__ __launch_bounds__(256) void k_detect_oscfar(const T* __restrict__ rds, int S, int C, int W,
                                                        CfarWindow win, double rank, float alpha, float thr_f,
                                                        int i_lo, int i_hi, int R, int RB,
                                                        unsigned long long* __restrict__ mask,
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(256) void k_detect_oscfar(const float2* __restrict_
   const int Re = sp.Re;
   const int UL = Re + 2 * hh;  // rows the strip loads: u = 0 .. UL-1 is range row ibase + u
   const int ibase = sp.i0 - hh;
-  const float2* base = rds + fa * S * C;
+  const T* base = rds + fa * S * C;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const unsigned ringb = 4u * NP * PS;
 
@@ -184,7 +186,12 @@ __global__ __launch_bounds__(256) void k_detect_oscfar(const float2* __restrict_
 
 hipError_t launch_detect_oscfar(hipStream_t st, const float2* rds, int F, int A, int S, int C, CfarWindow win,
                                 double rank, float alpha, const DetectArgs& d) {
-  return launch_cfar_strips(st, k_detect_oscfar, oscfar_lds_bytes, rds, F, A, S, C, win, d, rank, alpha);
+  return launch_cfar_strips(st, k_detect_oscfar<float2>, oscfar_lds_bytes, rds, F, A, S, C, win, d, rank, alpha);
+}
+
+hipError_t launch_detect_oscfar(hipStream_t st, const float* power, int F, int S, int C, CfarWindow win, double rank,
+                                float alpha, const DetectArgs& d) {
+  return launch_cfar_strips(st, k_detect_oscfar<float>, oscfar_lds_bytes, power, F, 1, S, C, win, d, rank, alpha);
 }
 
 }  // namespace rsl

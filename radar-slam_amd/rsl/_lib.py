@@ -19,6 +19,8 @@ DOA_TOEPLITZ = 0x100
 DOA_SPEC_GMAJOR = 0x200
 DOA_SPEC_BLOCKED = 0x400
 STEER_TOEPLITZ = 1
+RULE_THRESHOLD, RULE_CA, RULE_OS = 0, 1, 2  # RSL_RULE_*: the detection rule of rsl_detect_power
+RULE_IDS = {'threshold': RULE_THRESHOLD, 'ca': RULE_CA, 'os': RULE_OS}
 SS_MAX_L = 8  # RSL_SS_MAX_L: the longest sub-array of rsl_doa_smoothed
 LOSS_HUBER, LOSS_TUKEY = 1, 2
 LOSS_IDS = {'huber': LOSS_HUBER, 'tukey': LOSS_TUKEY}
@@ -48,6 +50,9 @@ SIGNATURES = {
                                 c_int, c_int, _P, _P, _P, _P]),
     'rsl_detect_oscfar': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double,
                                   c_double, c_int, c_int, _P, _P, _P, _P]),
+    'rsl_power_integrate': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    'rsl_detect_power': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double,
+                                 c_double, c_int, c_int, _P, _P, _P, _P]),
     'rsl_peak_offsets': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     'rsl_peak_emit': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_longlong,
                               c_longlong, _P, _P, _P, _P, _P, _P]),

@@ -7,6 +7,10 @@ device (``entry_base[F]``, ``cell_base[F]``).  Per-antenna detections of one (ra
 one spatial signature (angle_estimation.py:83), so DoA/ESPRIT run once per unique cell and entries map
 to cells (``e_cell``); the velocity LS weights each cell by its number of antenna detections, which
 reproduces the reference's sums over all targets exactly.
+
+``ChainConfig(detect_on='sum')`` detects once per frame on the antenna-summed power map instead (non-coherent
+integration, include/rsl.h rsl_power_integrate / rsl_detect_power): every cell is then one entry of antenna 0 with
+weight 1, and the DoA stage runs unchanged on the full RDS.
 """
 from __future__ import annotations
 
@@ -60,6 +64,12 @@ class ChainConfig:
                                                # (rsl_detect_oscfar), cfar_alpha / cfar_pfa then refer to the
                                                # order statistic (tables.os_cfar_alpha)
     cfar_rank: float = 0.75                    # 'os': the ceil(cfar_rank * cells)-th smallest training cell, (0, 1]
+    detect_on: str = 'antenna'                 # 'antenna': the detector runs once per antenna on that antenna's
+                                               # |rds|^2 (the reference's way); 'sum': once per frame on the
+                                               # antenna-summed power (non-coherent integration: rsl_power_integrate
+                                               # + rsl_detect_power): every cell is one entry of antenna 0, cfar_pfa
+                                               # is the rate per cell (alpha designed for a sum of num_antennas looks)
+                                               # and threshold_db applies to the summed power
     velocity_loss: str = 'ls'                  # 'ls': rsl_velocity (plain box-constrained LS); 'huber' | 'tukey':
                                                # rsl_velocity_robust (IRLS from the LS start, include/rsl.h)
     velocity_scale: Optional[float] = None     # residual scale sigma (the sensor's phase-noise sigma, radians); None:
@@ -100,6 +110,10 @@ class ChainConfig:
             raise ValueError(f"velocity_loss must be 'ls', 'huber' or 'tukey', not {self.velocity_loss!r}")
         if self.detector not in ('threshold', 'cfar'):
             raise ValueError(f"detector must be 'threshold' or 'cfar', not {self.detector!r}")
+        if self.detect_on not in ('antenna', 'sum'):
+            raise ValueError(f"detect_on must be 'antenna' or 'sum', not {self.detect_on!r}")
+        if self.detect_on == 'sum' and not 1 <= int(self.num_antennas) <= 32:
+            raise ValueError(f"detect_on='sum' needs 1 to 32 antennas, not {self.num_antennas}")
         if self.cfar_method not in tables.CFAR_METHODS:
             raise ValueError(f"cfar_method must be 'ca' or 'os', not {self.cfar_method!r}")
         if not 0.0 < float(self.cfar_rank) <= 1.0:
@@ -146,7 +160,8 @@ class RadarChain:
         self.cfar_alpha = None
         if cfg.detector == 'cfar':
             self.cfar_alpha = float(cfg.cfar_alpha) if cfg.cfar_alpha is not None else tables.cfar_design_alpha(
-                cfg.cfar_method, cfg.cfar_pfa, cfg.cfar_guard, cfg.cfar_train, cfg.cfar_rank)
+                cfg.cfar_method, cfg.cfar_pfa, cfg.cfar_guard, cfg.cfar_train, cfg.cfar_rank,
+                looks=cfg.num_antennas if cfg.detect_on == 'sum' else 1)
         d = cfg.antenna_spacing or cfg.lambda_c / 2
         self.grid = tables.azimuth_grid(cfg.search_range, cfg.search_resolution)
         steer_c128 = tables.steering_matrix(self.grid, np.arange(A) * d, cfg.lambda_c)
@@ -156,7 +171,9 @@ class RadarChain:
         lam_v = cfg.velocity_lambda or cfg.lambda_c
         self.k = 4 * np.pi * cfg.dt / lam_v
         self.method = _lib.METHOD_MUSIC if cfg.method == 'music' else _lib.METHOD_BEAMFORMING
-        self.entry_cap = int(math.ceil(cfg.entry_frac * F * A * S * C)) + 64
+        self.sum = cfg.detect_on == 'sum'
+        DA = 1 if self.sum else A  # antenna maps the detector decides on per frame
+        self.entry_cap = int(math.ceil(cfg.entry_frac * F * DA * S * C)) + 64
         self.cell_cap = (int(math.ceil(cfg.cell_frac * F * S * C)) + 64 + 3) & ~3  # a multiple of 4 (16-B rows)
         e = self._guarded_empty if guard else ctx.empty
         W = (C + 63) // 64
@@ -165,7 +182,16 @@ class RadarChain:
         self.mask = e((F, A, S, W), torch.int64)
         self.row_count = e((F, A, S), torch.int32)
         self.peak_pow = e((F, A, S, C), torch.float32)  # row-compact peak powers (detect -> emit)
-        self.offs = dict(entry_row_off=e((F * A * S,), torch.int32), cell_row_off=e((F * S,), torch.int32),
+        self.power = None
+        if self.sum:
+            # the fused front end still writes its per-antenna outputs; what it wrote is not read, and the detector of
+            # the summed map puts its own (one map per frame) at the start of the same buffers
+            self.power = e((F, S, C), torch.float32)  # the antenna-summed map (the integrated range-Doppler map)
+            self._front = dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow)
+            self.mask = self.mask.view(-1)[:F * S * W].view(F, 1, S, W)
+            self.row_count = self.row_count.view(-1)[:F * S].view(F, 1, S)
+            self.peak_pow = self.peak_pow.view(-1)[:F * S * C].view(F, 1, S, C)
+        self.offs = dict(entry_row_off=e((F * DA * S,), torch.int32), cell_row_off=e((F * S,), torch.int32),
                          scratch=e((F * S,), torch.int32), entry_base=e((F + 1,), torch.int64),
                          cell_base=e((F + 1,), torch.int64), frame_counts=e((2 * F,), torch.int64),
                          union_mask=e((F, S, W), torch.int64))
@@ -238,11 +264,19 @@ class RadarChain:
         if self.F == 0:  # empty batch: only the (zeroed) bases
             ctx.offsets(self.mask, self.row_count, self.C, bufs=self.offs)
             return
+        front = self._front if self.sum else dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow)
         group = ctx.rds_detect(cube, self.table, self.thr_p, self.i_lo, self.i_hi, rds=self.rds, work=self.work,
-                               mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow,
-                               dc_removal=cfg.dc_removal)
+                               dc_removal=cfg.dc_removal, **front)
         self._group = group
-        if cfg.detector == 'cfar':  # the CFAR detector rewrites the fused detector's mask, counts and peak powers
+        if self.sum:  # one decision per cell, on the antenna-summed power
+            out = dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow)
+            ctx.integrate_power(self.rds, out=self.power)
+            ctx.detect_power(self.power, 'threshold' if cfg.detector == 'threshold' else cfg.cfar_method,
+                             cfg.cfar_guard, cfg.cfar_train, cfg.cfar_rank,
+                             self.cfar_alpha if self.cfar_alpha is not None else 1.0, self.thr_p, self.i_lo,
+                             self.i_hi, out=out)
+            self._group = 1
+        elif cfg.detector == 'cfar':  # the CFAR detector rewrites the fused detector's mask, counts and peak powers
             out = dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow)
             ctx.detect_cfar(self.rds, cfg.cfar_guard, cfg.cfar_train, self.cfar_alpha, self.thr_p, self.i_lo,
                             self.i_hi, out=out, method=cfg.cfar_method, rank=cfg.cfar_rank)

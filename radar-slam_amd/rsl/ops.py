@@ -126,6 +126,68 @@ def detect_peaks_cfar(rds, *, guard=(2, 2), train=(8, 8), pfa=1e-4, alpha=None, 
                                                                        want_db=want_db, method=method, rank=rank))
 
 
+# -- non-coherent integration: detection on the antenna-summed power map --------------------------------
+def _dev_rds4(c: Context, rds):
+    d = as_dev_c64(c, rds)
+    if d.dim() == 3:
+        d = d.unsqueeze(0)
+    return d.contiguous()
+
+
+def integrate_power(rds, ctx: Optional[Context] = None, keep_on_device=False):
+    """rds [A, S, C] or [F, A, S, C] -> the antenna-summed power map [S, C] or [F, S, C] (rsl_power_integrate: fp32
+    sum of |rds|^2 over the antennas in antenna order; float64 host array, or the float32 device tensor)."""
+    c = _ctx(ctx)
+    single = (rds.ndim == 3)
+    p = c.integrate_power(_dev_rds4(c, rds))
+    if not keep_on_device:
+        p = to_host(p, np.float64)
+    return p[0] if single else p
+
+
+def detect_peaks_integrated(rds, *, detector='cfar', method='ca', rank=0.75, guard=(2, 2), train=(8, 8), pfa=1e-4,
+                            alpha=None, threshold_db=-math.inf, i_lo=0, i_hi=1 << 30, want_db=True,
+                            ctx: Optional[Context] = None):
+    """rds [A, S, C] -> the dictionary of detect_peaks, detected once on the antenna-summed power map instead of once
+    per antenna (rsl_power_integrate + rsl_detect_power).  detector 'cfar': method 'ca' / 'os' as detect_peaks_cfar,
+    alpha from pfa for a sum of A looks (tables.cfar_design_alpha(..., looks=A)) unless given, threshold_db a floor on
+    the summed power (-inf: none); detector 'threshold': the fixed threshold_db on the summed power.  Every peak is
+    one entry: antenna is all zeros, power_db is that of the summed power and power_spectrum_db is [1, S, C]."""
+    if detector not in ('threshold', 'cfar'):
+        raise ValueError(f"detector must be 'threshold' or 'cfar', not {detector!r}")
+    if method not in tables.CFAR_METHODS:
+        raise ValueError(f"method must be 'ca' or 'os', not {method!r}")
+    c = _ctx(ctx)
+    d = _dev_rds4(c, rds)
+    F, A, S, C = d.shape
+    rule = 'threshold' if detector == 'threshold' else method
+    if alpha is None:
+        alpha = tables.cfar_design_alpha(method, pfa, guard, train, rank, looks=A) if detector == 'cfar' else 1.0
+    power = c.integrate_power(d)
+    pk = c.empty((F, 1, S, C), c.torch.float32)
+    W = (C + 63) // 64
+    on_dev = (W & (W - 1)) == 0  # else emit would recompute power_db from the RDS: gather it from the dB map instead
+    mask, rc, db = c.detect_power(power, rule, guard, train, rank, alpha, tables.power_threshold(threshold_db), i_lo,
+                                  i_hi, want_db=want_db or not on_dev, out=dict(peak_pow=pk))
+    offs = c.offsets(mask, rc, C)
+    ne = int(offs['entry_base'][F].item())
+    nc = int(offs['cell_base'][F].item())
+    lists = c.emit(d, mask, offs, ne, nc, want_pdb=on_dev, peak_pow=pk)
+    ant, rbin, dbin = unpack_coord(to_host(lists['e_coord'][:ne]))
+    if on_dev:
+        pdb = to_host(lists['e_pdb'][:ne], np.float64)
+    else:
+        fr = np.searchsorted(to_host(offs['entry_base']), np.arange(ne), side='right') - 1
+        pdb = to_host(db, np.float64)[fr, 0, rbin, dbin]
+    res = dict(antenna=ant.astype(np.int64), range_bin=rbin.astype(np.int64), doppler_bin=dbin.astype(np.int64),
+               power_db=pdb, entry_base=to_host(offs['entry_base']), cells=nc)
+    if want_db:
+        res['power_spectrum_db'] = to_host(db, np.float64)
+        if F == 1:
+            res['power_spectrum_db'] = res['power_spectrum_db'][0]
+    return res
+
+
 # -- signatures as a pseudo-RDS [N, A, 1, 1] -------------------------------------------------------------
 def _sig_cells(c: Context, sigs: np.ndarray):
     torch = c.torch

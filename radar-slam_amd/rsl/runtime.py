@@ -241,6 +241,42 @@ class Context:
         """detect_cfar with method 'os'."""
         return self.detect_cfar(rds, guard, train, alpha, thr_power, i_lo, i_hi, want_db, out, method='os', rank=rank)
 
+    # -- non-coherent integration -----------------------------------------------------------------
+    def integrate_power(self, rds, out=None):
+        """rds complex64 [F, A, S, C] -> the antenna-summed power map float32 [F, S, C] (rsl_power_integrate: the
+        fp32 sum of the per-antenna powers in antenna order; A <= 32)."""
+        torch = self.torch
+        if rds.dim() != 4 or rds.dtype != torch.complex64:
+            raise ValueError('integrate_power: rds must be complex64 [F, A, S, C]')
+        F, A, S, C = rds.shape
+        if out is None:
+            out = self.empty((F, S, C), torch.float32)
+        self._bind()
+        self.check(self.lib.rsl_power_integrate(self.h, _ptr(rds), F, A, S, C, _ptr(out)), 'rsl_power_integrate')
+        return out
+
+    def detect_power(self, power, rule, guard, train, rank: float, alpha: float, thr_power: float, i_lo: int,
+                     i_hi: int, want_db: bool = False, out=None):
+        """One of the three detection rules on a power map float32 [F, S, C] (rsl_detect_power).  rule: 'threshold'
+        (guard, train, rank and alpha are ignored), 'ca' or 'os', or the _lib.RULE_* id.  Returns (mask [F, 1, S, W],
+        row_count [F, 1, S], dB map [F, 1, S, C] or None): a unit antenna axis, so that offsets and emit take them as
+        they are.  out: optional preallocated mask / row_count / peak_pow (row-compact, group 1)."""
+        torch = self.torch
+        if power.dim() != 3 or power.dtype != torch.float32:
+            raise ValueError('detect_power: power must be float32 [F, S, C]')
+        if isinstance(rule, str):
+            if rule not in _lib.RULE_IDS:
+                raise ValueError(f"rule must be 'threshold', 'ca' or 'os', not {rule!r}")
+            rule = _lib.RULE_IDS[rule]
+        F, S, C = power.shape
+        mask, rc, db, pk = self._detect_out(power.unsqueeze(1), want_db, out)
+        self._bind()
+        self.check(self.lib.rsl_detect_power(self.h, _ptr(power), F, S, C, int(rule), int(guard[0]), int(guard[1]),
+                                             int(train[0]), int(train[1]), float(rank), float(alpha),
+                                             float(thr_power), int(i_lo), int(i_hi), _ptr(mask), _ptr(rc), _ptr(db),
+                                             _ptr(pk)), 'rsl_detect_power')
+        return mask, rc, db
+
     def offsets(self, mask, row_count, C: int, bufs=None):
         torch = self.torch
         F, A, S, W = mask.shape
@@ -260,9 +296,16 @@ class Context:
     def emit(self, rds, mask, offs, entry_cap: int, cell_cap: int, want_pdb: bool = True, bufs=None,
              peak_pow=None, peak_pow_group: int = 1):
         """Compact peak entries and unique cells.  With ``peak_pow`` (from detect, row grouping 1; or rds_detect,
-        the grouping it returned) and the offsets' union mask the RDS is not re-read."""
+        the grouping it returned) and the offsets' union mask the RDS is not re-read.  The antenna count is the
+        mask's: masks of an antenna-summed map (detect_power, one antenna) go with the full RDS."""
         torch = self.torch
-        F, A, S, C = rds.shape
+        F, _, S, C = rds.shape
+        A = int(mask.shape[1])
+        W = int(mask.shape[3])
+        if want_pdb and A != rds.shape[1] and (peak_pow is None or offs.get('union_mask') is None or W & (W - 1)):
+            # rsl_peak_emit would recompute power_db from the RDS, which is not the map these masks were taken on
+            raise ValueError('emit: masks of another antenna count than the RDS need peak_pow, the union mask and a '
+                             'power-of-two count of mask words per row (or want_pdb=False)')
 
         def get(name, n, dt):
             return self._buf(bufs, name, (max(n, 1),), dt)

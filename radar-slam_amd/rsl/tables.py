@@ -124,11 +124,143 @@ def os_cfar_alpha(pfa: float, n_train: int, k: int) -> float:
 CFAR_METHODS = ('ca', 'os')  # cell averaging (rsl_detect_cfar), ordered statistic (rsl_detect_oscfar)
 
 
-def cfar_design_alpha(method: str, pfa: float, guard, train, rank: float = 0.75) -> float:
+# -- non-coherent integration: the cell under test and every training cell are sums of L looks ------------------
+# In exponential (unit-mean) noise such a sum is Gamma(L, 1)-distributed: density x^(L-1) e^-x / (L-1)!, survival
+# function Q_L(t) = e^-t sum_{m<L} t^m / m!.
+
+def _bisect_decreasing(rate, pfa: float) -> float:
+    """The alpha > 0 with rate(alpha) = pfa, rate strictly decreasing from 1, to fp64 precision."""
+    lo, hi = 0.0, 1.0
+    while rate(hi) > pfa:
+        lo, hi = hi, 2.0 * hi
+    while True:
+        mid = 0.5 * (lo + hi)
+        if not lo < mid < hi:
+            return mid
+        if rate(mid) > pfa:
+            lo = mid
+        else:
+            hi = mid
+
+
+def _check_looks(what: str, looks) -> int:
+    if int(looks) != looks or not 1 <= int(looks) <= 32:
+        raise ValueError(f'{what}: looks must be an integer in [1, 32], not {looks!r}')
+    return int(looks)
+
+
+def cfar_pfa_nci(alpha: float, n_train: int, looks: int) -> float:
+    """False-alarm rate of CA-CFAR with factor alpha on the mean of n training cells when every cell is the sum of
+    `looks` looks: with T = alpha / n,  Pfa = sum_{k<L} C(nL + k - 1, k) T^k / (1 + T)^(nL + k)  (the training sum is
+    Gamma(nL); looks = 1: (1 + alpha / n)^-n, cfar_alpha's closed form).  Terms by their ratio, no large factorials."""
+    n, L = int(n_train), _check_looks('cfar_pfa_nci', looks)
+    if n < 1 or not alpha >= 0.0:
+        raise ValueError('cfar_pfa_nci: n_train must be >= 1 and alpha >= 0')
+    T = float(alpha) / n
+    term = math.exp(-n * L * math.log1p(T))
+    total = term
+    r = T / (1.0 + T)
+    for k in range(1, L):
+        term *= (n * L + k - 1) / k * r
+        total += term
+    return total
+
+
+def cfar_alpha_nci(pfa: float, n_train: int, looks: int) -> float:
+    """CA-CFAR factor on the training mean of maps that sum `looks` looks, for false-alarm rate pfa: cfar_pfa_nci
+    (strictly decreasing in alpha) inverted by bisection."""
+    n, L = int(n_train), _check_looks('cfar_alpha_nci', looks)
+    if n < 1 or not (0.0 < pfa < 1.0):
+        raise ValueError('cfar_alpha_nci: pfa must lie in (0, 1) and n_train be >= 1')
+    return _bisect_decreasing(lambda a: cfar_pfa_nci(a, n, L), pfa)
+
+
+def _gamma_sf(t, L: int):
+    """Q_L(t) = e^-t sum_{m<L} t^m / m! for an array t >= 0."""
+    t = np.asarray(t, dtype=np.float64)
+    s = np.ones_like(t)
+    term = np.ones_like(t)
+    for m in range(1, L):
+        term = term * t / m
+        s += term
+    return np.exp(-t) * s
+
+
+def _gamma_cdf(x, L: int):
+    """1 - Q_L(x); below x = 1 by its own series e^-x sum_{m>=L} x^m / m! (1 - Q cancels there)."""
+    x = np.asarray(x, dtype=np.float64)
+    xs = np.minimum(x, 1.0)
+    term = xs ** L / math.factorial(L)
+    s = term.copy()
+    for m in range(L + 1, L + 40):
+        term = term * xs / m
+        s += term
+    return np.where(x < 1.0, np.exp(-xs) * s, 1.0 - _gamma_sf(x, L))
+
+
+_GL_X, _GL_W = np.polynomial.legendre.leggauss(16)
+
+
+def _os_nci_nodes(n: int, k: int, L: int):
+    """Quadrature nodes x and weights w (density of x_(k) included) of  E[g(x_(k))] ~ sum w g(x), x_(k) the k-th
+    smallest of n Gamma(L, 1) variables, density k C(n, k) F^(k-1) (1 - F)^(n-k) f.  Composite 16-point Gauss-Legendre
+    in s = log x (the order statistic's relative width is bounded below over every n, k, L admitted, its absolute
+    width is not), panels of 0.002, only those that hold more than e^-60 of the largest panel's density."""
+    logc = math.log(k) + math.lgamma(n + 1) - math.lgamma(k + 1) - math.lgamma(n - k + 1)
+
+    def logdens_s(s):  # log of the density of s = log x_(k)
+        x = np.exp(s)
+        with np.errstate(divide='ignore'):
+            lf = np.log(_gamma_cdf(x, L)) if k > 1 else 0.0
+            lq = np.log(_gamma_sf(x, L)) if n > k else 0.0
+        return logc + (k - 1) * lf + (n - k) * lq + (L - 1) * s - x - math.lgamma(L) + s
+
+    h = 0.002
+    s_lo = (math.log(1e-30) + math.lgamma(L + 1) - math.log(n)) / L  # n F(x) < 1e-30 below
+    s_hi = math.log(L + 80.0 + 8.0 * math.sqrt(L) + math.log(n))      # n Q_L(x) < 1e-30 above
+    edges = np.arange(s_lo, s_hi + h, h)
+    mid = edges[:-1] + 0.5 * h
+    with np.errstate(invalid='ignore'):
+        ld = logdens_s(mid)
+    ld = np.where(np.isnan(ld), -np.inf, ld)
+    keep = ld > ld.max() - 60.0
+    keep = keep | np.roll(keep, 1) | np.roll(keep, -1)
+    s = (mid[keep, None] + 0.5 * h * _GL_X[None, :]).ravel()
+    w = np.exp(logdens_s(s)) * np.tile(0.5 * h * _GL_W, int(keep.sum()))
+    return np.exp(s), w
+
+
+def os_cfar_pfa_nci(alpha: float, n_train: int, k: int, looks: int) -> float:
+    """False-alarm rate of OS-CFAR with factor alpha on the k-th smallest of n training cells when every cell is the
+    sum of `looks` looks:  Pfa = E[Q_L(alpha x_(k))]  by one-dimensional quadrature (looks = 1: os_cfar_pfa's
+    product)."""
+    n, k, L = int(n_train), int(k), _check_looks('os_cfar_pfa_nci', looks)
+    if not 1 <= k <= n or not alpha >= 0.0:
+        raise ValueError('os_cfar_pfa_nci: k must lie in [1, n_train] and alpha be >= 0')
+    x, w = _os_nci_nodes(n, k, L)
+    return float(np.dot(w, _gamma_sf(float(alpha) * x, L)))
+
+
+def os_cfar_alpha_nci(pfa: float, n_train: int, k: int, looks: int) -> float:
+    """OS-CFAR factor on the k-th smallest training cell of maps that sum `looks` looks, for false-alarm rate pfa:
+    os_cfar_pfa_nci (strictly decreasing in alpha) inverted by bisection on one set of quadrature nodes."""
+    n, k, L = int(n_train), int(k), _check_looks('os_cfar_alpha_nci', looks)
+    if not (0.0 < pfa < 1.0) or not 1 <= k <= n:
+        raise ValueError('os_cfar_alpha_nci: pfa must lie in (0, 1) and k in [1, n_train]')
+    x, w = _os_nci_nodes(n, k, L)
+    return _bisect_decreasing(lambda a: float(np.dot(w, _gamma_sf(a * x, L))), pfa)
+
+
+def cfar_design_alpha(method: str, pfa: float, guard, train, rank: float = 0.75, looks: int = 1) -> float:
     """The factor of a CFAR design, from its false-alarm rate and the full-window training-cell count: 'ca' on the
-    training mean (cfar_alpha), 'os' on the order statistic of rank ceil(rank * cells) (os_cfar_alpha)."""
+    training mean (cfar_alpha), 'os' on the order statistic of rank ceil(rank * cells) (os_cfar_alpha).  looks > 1:
+    the design for maps that sum that many looks (non-coherent integration: cfar_alpha_nci, os_cfar_alpha_nci)."""
     n = cfar_training_cells(guard, train)
-    return os_cfar_alpha(pfa, n, os_cfar_rank(n, rank)) if method == 'os' else cfar_alpha(pfa, n)
+    if looks == 1:
+        return os_cfar_alpha(pfa, n, os_cfar_rank(n, rank)) if method == 'os' else cfar_alpha(pfa, n)
+    if method == 'os':
+        return os_cfar_alpha_nci(pfa, n, os_cfar_rank(n, rank), looks)
+    return cfar_alpha_nci(pfa, n, looks)
 
 
 def azimuth_grid(search_range=(-90, 90), search_resolution=0.5):

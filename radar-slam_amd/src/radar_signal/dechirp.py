@@ -143,6 +143,30 @@ class SignalPreprocessor:
         return {'peaks': peaks, 'range_bins_m': range_bins_m, 'doppler_bins_hz': doppler_bins_hz,
                 'power_spectrum_db': r['power_spectrum_db']}
 
+    def extract_range_doppler_peaks_integrated(self, rds: np.ndarray, detector: str = 'cfar', guard=(2, 2),
+                                               train=(8, 8), pfa: float = 1e-4, threshold_db: Optional[float] = None,
+                                               min_range: float = 1.0, max_range: float = 200.0, method: str = 'ca',
+                                               rank: float = 0.75) -> Dict:
+        """extract_range_doppler_peaks_cfar on the antenna-summed power map (non-coherent integration; not in the
+        reference): one decision per (range, doppler) cell instead of one per antenna, alpha from pfa for a sum of A
+        looks.  detector 'threshold' applies threshold_db (None: -20 dB) to the summed power instead of a CFAR level.
+        Same dict; every peak carries 'antenna': 0, power_db is that of the summed power and power_spectrum_db is
+        [1, S, C], so db[p['antenna'], p['range_bin'], p['doppler_bin']] keeps working."""
+        A, S, C = rds.shape
+        range_bins_m = tables.range_axis(self.bandwidth, S)
+        doppler_bins_hz = np.linspace(-self.sampling_rate / 2, self.sampling_rate / 2, C)
+        i_lo, i_hi = tables.range_gate(self.bandwidth, S, min_range, max_range)
+        if threshold_db is None:
+            threshold_db = -20.0 if detector == 'threshold' else -np.inf
+        r = ops.detect_peaks_integrated(rds, detector=detector, method=method, rank=rank, guard=guard, train=train,
+                                        pfa=pfa, threshold_db=threshold_db, i_lo=i_lo, i_hi=i_hi, want_db=True)
+        ant, ib, jb, pdb = r['antenna'], r['range_bin'], r['doppler_bin'], r['power_db']
+        peaks = [{'antenna': int(a), 'range_bin': i, 'doppler_bin': j, 'range_m': range_bins_m[i],
+                  'doppler_hz': doppler_bins_hz[j], 'power_db': p}
+                 for a, i, j, p in zip(ant.tolist(), ib, jb, pdb)]
+        return {'peaks': peaks, 'range_bins_m': range_bins_m, 'doppler_bins_hz': doppler_bins_hz,
+                'power_spectrum_db': r['power_spectrum_db']}
+
     def visualize_rds(self, rds: np.ndarray, antenna_idx: int = 0, save_path: Optional[str] = None) -> None:
         import matplotlib.pyplot as plt
         power_db = 10 * np.log10(np.abs(rds[antenna_idx, :, :]) ** 2 + 1e-12)
