@@ -443,27 +443,26 @@ int rsl_peak_emit(rsl_handle h, const void* rds, const void* mask, const void* u
     return fail(h, RSL_ERR_INVALID, "rsl_peak_emit: null pointer");
   if ((entry_cap > 0 && (!e_coord || !e_cell)) || (cell_cap > 0 && (!c_frame || !c_rc || !c_amask)))
     return fail(h, RSL_ERR_INVALID, "rsl_peak_emit: null output");
-  const int W = (C + 63) / 64;
   if (peak_pow && (peak_pow_group < 1 || S % peak_pow_group != 0))
     return fail(h, RSL_ERR_INVALID, "rsl_peak_emit: peak_pow_group must divide S");
   Scope sc(h, RSL_K_EMIT);
-  if (union_mask && (peak_pow || !e_pdb) && (W & (W - 1)) == 0 && W <= 64)
+  if (rsl::emit_compact_supported(C, union_mask, peak_pow, e_pdb))
     return hip_check(h,
-                     rsl::launch_emit2(h->stream, (const unsigned long long*)mask,
-                                       (const unsigned long long*)union_mask, (const float*)peak_pow,
-                                       peak_pow_group, F, A, S, C,
-                                       (const int*)entry_row_off, (const int*)cell_row_off,
-                                       (const long long*)entry_base, (const long long*)cell_base, entry_cap, cell_cap,
-                                       (unsigned*)e_coord, (int*)e_cell, (float*)e_pdb,
-                                       (int*)c_frame, (int*)c_rc, (unsigned*)c_amask),
+                     rsl::launch_emit_compact(h->stream, (const unsigned long long*)mask,
+                                              (const unsigned long long*)union_mask, (const float*)peak_pow,
+                                              peak_pow_group, F, A, S, C, (const int*)entry_row_off,
+                                              (const int*)cell_row_off, (const long long*)entry_base,
+                                              (const long long*)cell_base, entry_cap, cell_cap, (unsigned*)e_coord,
+                                              (int*)e_cell, (float*)e_pdb, (int*)c_frame, (int*)c_rc,
+                                              (unsigned*)c_amask),
                      "emit2");
   if (!rds) return fail(h, RSL_ERR_INVALID, "rsl_peak_emit: rds needed without union_mask / peak_pow");
   return hip_check(h,
-                   rsl::launch_emit(h->stream, (const float2*)rds, (const unsigned long long*)mask, F, A, S, C,
-                                    (const int*)entry_row_off, (const int*)cell_row_off, (const long long*)entry_base,
-                                    (const long long*)cell_base, entry_cap, cell_cap, (unsigned*)e_coord,
-                                    (int*)e_cell, (float*)e_pdb, (int*)c_frame, (int*)c_rc,
-                                    (unsigned*)c_amask),
+                   rsl::launch_emit_rows(h->stream, (const float2*)rds, (const unsigned long long*)mask, F, A, S, C,
+                                         (const int*)entry_row_off, (const int*)cell_row_off,
+                                         (const long long*)entry_base, (const long long*)cell_base, entry_cap,
+                                         cell_cap, (unsigned*)e_coord, (int*)e_cell, (float*)e_pdb, (int*)c_frame,
+                                         (int*)c_rc, (unsigned*)c_amask),
                    "emit");
 }
 

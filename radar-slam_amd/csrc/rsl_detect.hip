@@ -9,6 +9,13 @@
 // Per-antenna 64-bit ballots give one mask word per 64 Doppler cells; a per-frame scan then turns
 // row counts into entry offsets (antenna-major) and union-cell offsets (range-major), and the emit
 // kernel writes both lists in reference order without any sort.
+// Two emit paths (emit_compact_supported, rsl_internal.h, chooses):
+//   compact (k_emit_cells + k_emit_entries, launch_emit_compact): from the masks, the union mask and the peak powers,
+//     power_db = 10 log10f of the stored fp32 peak power; where W = ceil(C / 64) is a power of two <= 64, the union
+//     mask is given, and peak_pow is given or no power_db is wanted.  The chain runs this one.
+//   general (k_emit, launch_emit_rows): one wave per range row, power_db rounded from a double-precision log10 of the
+//     RDS power; every other case: W not a power of two or above 64, no union mask, or power_db wanted without
+//     peak_pow.  The last is the drop-in extract_range_doppler_peaks, whose power_db bits depend on it.
 #include "rsl_common.h"
 #include "rsl_detect_common.h"
 #include "rsl_internal.h"
@@ -282,113 +289,83 @@ __global__ __launch_bounds__(256) void k_emit(const float2* __restrict__ rds, co
   }
 }
 
-// Stream compaction of the peak / cell bit masks: 256 consecutive mask words per block produce one contiguous run of
-// entries (or cells).  Phase 1: per-word popcounts, a block scan, and one packed (word, bit) code per item in
+// Stream compaction of the peak bit masks into the entry list: 256 consecutive mask words per block produce one
+// contiguous run of entries.  Phase 1: per-word popcounts, a block scan, and one packed (word, bit) code per item in
 // LDS.  Phase 2: item k of the block is written by lane k % 256, so every store instruction is coalesced
 // (consecutive lanes -> consecutive addresses); scattered 4-byte stores from a per-word set-bit loop would cost
-// one memory request per lane.  Entries follow dechirp.py:257 (np.where order: antenna -> range -> doppler);
-// cells are range-major unions over antennas.  power_db comes from the row-compact peak powers of k_detect
-// (no RDS re-read), 10 log10 in fp32 (the powers are fp32), stored as float64 like power_spectrum_db.  A block with more than kEmitCap items
-// runs phases 1-2 in rounds of kEmitCap (a per-word store loop would scatter 4-byte stores: measured 2.9x HBM write
-// amplification on the 54%-dense cell unions of cfg2).
+// one memory request per lane.  Entries follow dechirp.py:257 (np.where order: antenna -> range -> doppler).
+// power_db comes from the detector's compacted peak powers (pk_group rows per group, 1 = row-compact; no RDS
+// re-read), 10 log10 in fp32 (the powers are fp32).  A block with more than kEmitCap items runs phases 1-2 in rounds of
+// kEmitCap.
 constexpr int kEmitCap = 2048;
 constexpr int kEmitU = 4;  // phase-2 items per lane per trip
 
-// WPE: minimum waves per SIMD the register allocation must allow (0: unconstrained; A/B knob RSL_EMIT_WPE).
+// Registers capped for 8 waves per SIMD (44 VGPRs, no spill; 14 KiB of LDS).  The cells are k_emit_cells' work: this
+// kernel holds no antenna masks, neither in LDS nor in registers.
 // (Non-temporal entry stores were measured slower: 0.53 vs 0.48 ms per 1000 cfg2 frames.)
-// CELLS = false: an entries-only launch (the cells go to k_emit_cells): no antenna-mask buffer in LDS (14 instead of 22
-// KiB) and no cell path in the registers.
-template <int W, int MAXA, int WPE = 0, bool CELLS = true>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? WPE : 1))) void k_emit_block(const unsigned long long* __restrict__ mask,
-                                                    const unsigned long long* __restrict__ umask,
-                                                    const float* __restrict__ pk_pow, int pk_group, long long F,
-                                                    int A, int S, int C, const int* __restrict__ entry_row_off,
-                                                    const int* __restrict__ cell_row_off,
-                                                    const long long* __restrict__ entry_base,
-                                                    const long long* __restrict__ cell_base, long long entry_cap,
-                                                    long long cell_cap, long long nblk_e,
-                                                    unsigned* __restrict__ e_coord, int* __restrict__ e_cell,
-                                                    float* __restrict__ e_pdb,
-                                                    int* __restrict__ c_frame, int* __restrict__ c_rc,
-                                                    unsigned* __restrict__ c_amask) {
+template <int W>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_emit_entries(
+    const unsigned long long* __restrict__ mask, const unsigned long long* __restrict__ umask,
+    const float* __restrict__ pk_pow, int pk_group, long long F, int A, int S, int C,
+    const int* __restrict__ entry_row_off, const int* __restrict__ cell_row_off,
+    const long long* __restrict__ entry_base, const long long* __restrict__ cell_base, long long entry_cap,
+    unsigned* __restrict__ e_coord, int* __restrict__ e_cell, float* __restrict__ e_pdb) {
   static_assert(64 % W == 0, "a mask row must lie within one wave");
-  __shared__ unsigned pk[kEmitCap];                  // item code: (word << 6) | bit
-  __shared__ unsigned pam[CELLS ? kEmitCap : 1];  // cells: antenna mask of the item
+  __shared__ unsigned pk[kEmitCap];  // item code: (word << 6) | bit
   __shared__ int wsum[4];
   __shared__ int s_cw[256], s_fi[256];
-  __shared__ long long s_pkb[256];  // entries: peak_pow index of the word's item 0 minus its block rank
+  __shared__ long long s_pkb[256];  // peak_pow index of the word's item 0 minus its block rank
   __shared__ unsigned long long s_u[256];
   __shared__ long long s_first;
   const int t = threadIdx.x, lane = t & 63;
-  const bool entries = !CELLS || blockIdx.x < nblk_e;
-  const long long nent = F * A * S * W, ncw = F * S * W;
-  const long long gw0 = (entries ? (long long)blockIdx.x : (long long)blockIdx.x - nblk_e) * 256;  // row-aligned
-  const long long nw = entries ? nent : ncw;
+  const long long nw = F * A * S * W;
+  const long long gw0 = (long long)blockIdx.x * 256;  // row-aligned
   const bool valid = gw0 + t < nw;
   const long long gw = valid ? gw0 + t : gw0;  // past-the-end words alias the block's first word (then m = 0)
-  // word -> (row, w); entries: row = (f*A + a)*S + i, cells: row = f*S + i  (divisions once per word)
+  // word -> (row, w), row = (f*A + a)*S + i  (divisions once per word)
   const long long row = gw / W;
   const int w = (int)(gw - row * W);
-  const long long q = row / S;  // entries: f*A + a ; cells: f
+  const long long q = row / S;  // f*A + a
   const int i = (int)(row - q * S);
-  const long long f = entries ? q / A : q;
-  const int a = entries ? (int)(q - f * A) : 0;
+  const long long f = q / A;
+  const int a = (int)(q - f * A);
   // every global load of the word is issued here, independent of its value (one memory round trip)
-  unsigned long long m = entries ? mask[gw] : umask[gw];
+  unsigned long long m = mask[gw];
   long long fst = 0;  // thread 0: the block's first item index (the block starts a row: no earlier words)
-  if (t == 0) fst = entries ? entry_base[f] + entry_row_off[row] : cell_base[f] + cell_row_off[row];
-  unsigned long long u = 0;  // entries: the union word of (f, i, w)
-  long long cwb = 0;
+  if (t == 0) fst = entry_base[f] + entry_row_off[row];
+  int gof = 0;  // peaks of the earlier rows of the row's peak_pow group
+  const int ig = i - i % pk_group;
+  if (ig != i) gof = entry_row_off[row] - entry_row_off[row - (i - ig)];
+  const unsigned long long* urow = umask + ((size_t)f * S + i) * W;
+  const unsigned long long u = urow[w];  // the union word of (f, i, w)
+  const long long cwb = cell_base[f] + cell_row_off[f * S + i];
   int cwo = 0;
-  int gof = 0;  // entries: peaks of the earlier rows of the row's peak_pow group
-  if (entries) {
-    const int ig = i - i % pk_group;
-    if (ig != i) gof = entry_row_off[row] - entry_row_off[row - (i - ig)];
-    const unsigned long long* urow = umask + ((size_t)f * S + i) * W;
-    u = urow[w];
-    cwb = cell_base[f] + cell_row_off[f * S + i];
 #pragma unroll
-    for (int ww = 0; ww < W; ++ww)
-      if (ww < w) cwo += __popcll(urow[ww]);
-  }
-  unsigned long long ma[CELLS ? MAXA : 1];  // cells: the antennas' peak words of (f, i, w)
-  if (CELLS && !entries) {
-#pragma unroll
-    for (int aa = 0; aa < MAXA; ++aa) ma[aa] = aa < A ? mask[(((size_t)f * A + aa) * S + i) * W + w] : 0ull;
-  }
+  for (int ww = 0; ww < W; ++ww)
+    if (ww < w) cwo += __popcll(urow[ww]);
   if (!valid) m = 0;
   const int cnt = __popcll(m);
   int total;
   const int loc = block_exscan<int, 256>(cnt, wsum, &total);
-  // entries: peaks of the earlier words of this row (the row's words are lanes lane-w .. lane of this wave)
+  // peaks of the earlier words of this row (the row's words are lanes lane-w .. lane of this wave)
   const int r0 = loc - __shfl(loc, lane - w);
   if (t == 0) s_first = fst;
   s_cw[t] = (int)(cwb + cwo);
   s_u[t] = u;
-  s_fi[t] = entries ? ((a << 16) | i) : (int)f;
+  s_fi[t] = (a << 16) | i;
   // the row's group starts at row - i % pk_group; item k of the block reads peak_pow[s_pkb + base + k] (divisions once
   // per word instead of 64-bit divisions per item)
-  if (entries) s_pkb[t] = (row - i % pk_group) * (long long)C + (r0 + gof) - loc;
-  // rounds of kEmitCap items (one round unless the block is dense, e.g. the cell union at high peak density)
+  s_pkb[t] = (row - i % pk_group) * (long long)C + (r0 + gof) - loc;
+  // rounds of kEmitCap items (one round unless the block is dense)
   for (int base = 0; base < total; base += kEmitCap) {
-    // phase 1: packed (word, bit) codes (+ the cell's antenna mask) of this round's items, in LDS
+    // phase 1: packed (word, bit) codes of this round's items, in LDS
     if (loc < base + kEmitCap && loc + cnt > base) {
       unsigned long long mm = m;
       int o = loc;
       while (mm && o < base + kEmitCap) {
         const int b = __ffsll((long long)mm) - 1;
         mm &= mm - 1;
-        if (o >= base) {
-          pk[o - base] = ((unsigned)t << 6) | (unsigned)b;
-          if constexpr (CELLS) {
-            if (!entries) {
-              unsigned am = 0;
-#pragma unroll
-              for (int aa = 0; aa < MAXA; ++aa) am |= (unsigned)((ma[aa] >> b) & 1ull) << aa;
-              pam[o - base] = am;
-            }
-          }
-        }
+        if (o >= base) pk[o - base] = ((unsigned)t << 6) | (unsigned)b;
         ++o;
       }
     }
@@ -398,66 +375,50 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? W
     // phase 2: coalesced stores, lane k % 256 writes item k; kEmitU items per trip with their peak-power
     // gathers issued first (a rolled loop waits on each gather in turn)
     for (int k0 = t; k0 < nk; k0 += 256 * kEmitU) {
-      if (entries) {
-        float pw[kEmitU];
+      float pw[kEmitU];
 #pragma unroll
-        for (int uu = 0; uu < kEmitU; ++uu) {
-          const int k = k0 + 256 * uu;
-          pw[uu] = 0.f;
-          if (k < nk && e_pdb) {
-            pw[uu] = pk_pow[s_pkb[pk[k] >> 6] + base + k];
-          }
+      for (int uu = 0; uu < kEmitU; ++uu) {
+        const int k = k0 + 256 * uu;
+        pw[uu] = 0.f;
+        if (k < nk && e_pdb) {
+          pw[uu] = pk_pow[s_pkb[pk[k] >> 6] + base + k];
         }
+      }
 #pragma unroll
-        for (int uu = 0; uu < kEmitU; ++uu) {
-          const int k = k0 + 256 * uu;
-          const long long e = first + k;
-          if (k < nk && e < entry_cap) {
-            const unsigned code = pk[k];
-            const int tt = (int)(code >> 6), b = (int)(code & 63);
-            const int ww = (int)((gw0 + tt) % W);
-            const int ai = s_fi[tt];
-            e_coord[e] = ((unsigned)(ai >> 16) << 26) | ((unsigned)(ai & 0xffff) << 13) | (unsigned)(ww * 64 + b);
-            e_cell[e] = s_cw[tt] + __popcll(s_u[tt] & ((1ull << b) - 1ull));
-            if (e_pdb) e_pdb[e] = 10.0f * log10f(pw[uu] + 1e-12f);  // dechirp.py:235-236
-          }
-        }
-      } else if constexpr (CELLS) {
-#pragma unroll
-        for (int uu = 0; uu < kEmitU; ++uu) {
-          const int k = k0 + 256 * uu;
-          const long long e = first + k;
-          if (k < nk && e < cell_cap) {
-            const unsigned code = pk[k];
-            const int tt = (int)(code >> 6), b = (int)(code & 63);
-            const long long g2 = gw0 + tt;
-            const long long rw = g2 / W;
-            const int ww = (int)(g2 - rw * W);
-            c_frame[e] = s_fi[tt];
-            c_rc[e] = (int)(rw - (long long)s_fi[tt] * S) * C + ww * 64 + b;
-            c_amask[e] = pam[k];
-          }
+      for (int uu = 0; uu < kEmitU; ++uu) {
+        const int k = k0 + 256 * uu;
+        const long long e = first + k;
+        if (k < nk && e < entry_cap) {
+          const unsigned code = pk[k];
+          const int tt = (int)(code >> 6), b = (int)(code & 63);
+          const int ww = (int)((gw0 + tt) % W);
+          const int ai = s_fi[tt];
+          e_coord[e] = ((unsigned)(ai >> 16) << 26) | ((unsigned)(ai & 0xffff) << 13) | (unsigned)(ww * 64 + b);
+          e_cell[e] = s_cw[tt] + __popcll(s_u[tt] & ((1ull << b) - 1ull));
+          if (e_pdb) e_pdb[e] = 10.0f * log10f(pw[uu] + 1e-12f);  // dechirp.py:235-236
         }
       }
     }
-    __syncthreads();  // pk / pam reused by the next round
+    __syncthreads();  // pk reused by the next round
   }
 }
 
-// Cell-list compaction (union masks, ~54 % dense at cfg2): 4 threads per mask word (16-bit slices), 64 words per
-// block, so every block's items (at most 4096) are expanded in one round and no thread walks more than 16 set bits
-// (k_emit_block's word-per-thread cells path walked ~35 bits per word, up to 5 rounds of 2048 per block).
-// Blocks are row- and frame-aligned ((S * W) % 64 == 0): one contiguous run of cells from cell_base[f] + row offset.
+// Cell-list compaction (union masks, ~54 % dense at cfg2; cells are range-major unions over antennas): 4 threads per
+// mask word (16-bit slices), 64 words per block, so every block's items (at most 4096) are expanded in one round and no
+// thread walks more than 16 set bits.  Each frame has its own nbf = ceil(S * W / 64) blocks, the last one partly filled
+// where 64 does not divide S * W: a block lies in one frame and starts a row (64 % W == 0), so it writes one contiguous
+// run of cells from cell_base[f] + the row's offset, and every index below is a 32-bit word index within the frame.
 constexpr int kCellWords = 64;
 constexpr int kCellCap = kCellWords * 64;
 
 template <int W, int MAXA>
 __global__ __launch_bounds__(256) void k_emit_cells(const unsigned long long* __restrict__ mask,
-                                                    const unsigned long long* __restrict__ umask, long long F, int A,
+                                                    const unsigned long long* __restrict__ umask, int nbf, int A,
                                                     int S, int C, const int* __restrict__ cell_row_off,
                                                     const long long* __restrict__ cell_base, long long cell_cap,
                                                     int* __restrict__ c_frame, int* __restrict__ c_rc,
                                                     unsigned* __restrict__ c_amask) {
+  static_assert(kCellWords % W == 0, "a block must start a row");
   // item code (thread << 4) | bit within the thread's 16-bit slice (12 bits); for MAXA <= 16 the cell's antenna mask
   // is packed above it (16 KiB of LDS instead of 32: 5 workgroups per CU instead of 4)
   constexpr bool PACK = MAXA <= 16;
@@ -466,20 +427,17 @@ __global__ __launch_bounds__(256) void k_emit_cells(const unsigned long long* __
   __shared__ int wsum[4];
   __shared__ long long s_first;
   const int t = threadIdx.x;
-  const long long ncw = F * S * W;
-  const long long gw0 = (long long)blockIdx.x * kCellWords;
+  const int f = (int)(blockIdx.x / (unsigned)nbf);
+  const int lw0 = (int)(blockIdx.x - (unsigned)f * (unsigned)nbf) * kCellWords;  // the block's first word in the frame
   const int wl = t >> 2, sl = t & 3;
-  const bool valid = gw0 + wl < ncw;
-  const long long gw = valid ? gw0 + wl : gw0;
-  const long long row = gw / W;  // f * S + i
-  const int w = (int)(gw - row * W);
-  const long long f = row / S;
-  const int i = (int)(row - f * S);
-  unsigned long long m = valid ? umask[gw] : 0ull;
+  const bool valid = lw0 + wl < S * W;
+  const int lw = valid ? lw0 + wl : lw0;  // past-the-end words load the block's first word and contribute no bits
+  const int i = lw / W, w = lw % W;
+  unsigned long long m = valid ? umask[(size_t)f * S * W + lw] : 0ull;
   unsigned long long ma[MAXA];
 #pragma unroll
   for (int aa = 0; aa < MAXA; ++aa) ma[aa] = aa < A ? mask[(((size_t)f * A + aa) * S + i) * W + w] : 0ull;
-  if (t == 0) s_first = cell_base[f] + cell_row_off[row];
+  if (t == 0) s_first = cell_base[f] + cell_row_off[(size_t)f * S + i];
   const unsigned sm16 = (unsigned)(m >> (16 * sl)) & 0xffffu;
   unsigned sa[MAXA];  // this thread's 16-bit slice of every antenna's word: 32-bit bit extracts per cell below
 #pragma unroll
@@ -511,53 +469,39 @@ __global__ __launch_bounds__(256) void k_emit_cells(const unsigned long long* __
     if (e < cell_cap) {
       const unsigned code = pk[k];
       const int tt = (int)((code >> 4) & 0xffu);
-      const long long g2 = gw0 + (tt >> 2);
-      const long long rw = g2 / W;
-      const int ww = (int)(g2 - rw * W);
-      // the block lies in one frame (launch condition (S * W) % 64 == 0): every item's frame is this thread's f, so
-      // no 64-bit division by S per item
-      c_frame[e] = (int)f;
-      c_rc[e] = (int)(rw - f * S) * C + ww * 64 + 16 * (tt & 3) + (int)(code & 15);
+      const int lw2 = lw0 + (tt >> 2);
+      c_frame[e] = f;
+      c_rc[e] = (lw2 / W) * C + (lw2 % W) * 64 + 16 * (tt & 3) + (int)(code & 15);
       c_amask[e] = PACK ? code >> 12 : pam[k];
     }
   }
 }
 
-hipError_t launch_emit2(hipStream_t st, const unsigned long long* mask, const unsigned long long* umask,
-                        const float* pk_pow, int pk_group, int F, int A, int S, int C, const int* entry_row_off,
-                        const int* cell_row_off, const long long* entry_base, const long long* cell_base,
-                        long long entry_cap, long long cell_cap, unsigned* e_coord, int* e_cell, float* e_pdb,
-                        int* c_frame, int* c_rc, unsigned* c_amask) {
+bool emit_compact_supported(int C, bool union_mask, bool peak_pow, bool want_pdb) {
+  const int W = (C + 63) / 64;
+  return union_mask && (peak_pow || !want_pdb) && (W & (W - 1)) == 0 && W <= 64;
+}
+
+hipError_t launch_emit_compact(hipStream_t st, const unsigned long long* mask, const unsigned long long* umask,
+                               const float* pk_pow, int pk_group, int F, int A, int S, int C,
+                               const int* entry_row_off, const int* cell_row_off, const long long* entry_base,
+                               const long long* cell_base, long long entry_cap, long long cell_cap,
+                               unsigned* e_coord, int* e_cell, float* e_pdb, int* c_frame, int* c_rc,
+                               unsigned* c_amask) {
   if (F <= 0) return hipSuccess;
   if (A > 32) return hipErrorInvalidValue;
   const int W = (C + 63) / 64;
-  const long long nbe = ((long long)F * A * S * W + 255) / 256;
-  // cells: k_emit_cells when its frame-aligned blocks tile the cell words, else the word-per-thread path
-  const bool cells4 = ((long long)S * W) % kCellWords == 0;
-  const long long nbc = cells4 ? 0 : ((long long)F * S * W + 255) / 256;
-  const unsigned nb = (unsigned)(nbe + nbc);
-  if (cells4) {
-    const unsigned nbc4 = (unsigned)(((long long)F * S * W) / kCellWords);
-    const hipError_t e = with_int<1, 2, 4, 8, 16, 32, 64>(W, [&](auto w) {
-      constexpr int WW = decltype(w)::value;
-      hipLaunchKernelGGL((A <= 8 ? k_emit_cells<WW, 8> : A <= 16 ? k_emit_cells<WW, 16> : k_emit_cells<WW, 32>),
-                         dim3(nbc4), dim3(256), 0, st, mask, umask, (long long)F, A, S, C, cell_row_off, cell_base,
-                         cell_cap, c_frame, c_rc, c_amask);
-      return hipGetLastError();
-    });
-    if (e != hipSuccess) return e;
-  }
-  // registers capped for 7 waves per SIMD (72 VGPRs, no spill; 7 workgroups per CU as the LDS allows, instead of 6):
-  // emit 0.45-0.47 vs 0.46-0.48 ms per 1000 cfg2 frames (tools/cpb.sh); the entries-only instance (cells by
-  // k_emit_cells) holds 14 KiB of LDS and is capped for 8 waves per SIMD
-  constexpr int EWPE = 8;
+  const int nbf = (S * W + kCellWords - 1) / kCellWords;
+  const unsigned nbe = (unsigned)(((long long)F * A * S * W + 255) / 256);
   return with_int<1, 2, 4, 8, 16, 32, 64>(W, [&](auto w) {
     constexpr int WW = decltype(w)::value;
-    hipLaunchKernelGGL((cells4 ? k_emit_block<WW, 8, EWPE, false> /* entries only: MAXA unused */
-                               : (A <= 8 ? k_emit_block<WW, 8, 7> : k_emit_block<WW, 32>)),
-                       dim3(nb), dim3(256), 0, st, mask, umask, pk_pow, pk_group, (long long)F, A, S, C,
-                       entry_row_off, cell_row_off, entry_base, cell_base, entry_cap, cell_cap, nbe, e_coord, e_cell,
-                       e_pdb, c_frame, c_rc, c_amask);
+    hipLaunchKernelGGL((A <= 8 ? k_emit_cells<WW, 8> : A <= 16 ? k_emit_cells<WW, 16> : k_emit_cells<WW, 32>),
+                       dim3((unsigned)F * nbf), dim3(256), 0, st, mask, umask, nbf, A, S, C, cell_row_off, cell_base,
+                       cell_cap, c_frame, c_rc, c_amask);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_emit_entries<WW>, dim3(nbe), dim3(256), 0, st, mask, umask, pk_pow, pk_group, (long long)F, A,
+                       S, C, entry_row_off, cell_row_off, entry_base, cell_base, entry_cap, e_coord, e_cell, e_pdb);
     return hipGetLastError();
   });
 }
@@ -595,10 +539,10 @@ hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const 
   return hipGetLastError();
 }
 
-hipError_t launch_emit(hipStream_t st, const float2* rds, const unsigned long long* mask, int F, int A, int S, int C,
-                       const int* entry_row_off, const int* cell_row_off, const long long* entry_base,
-                       const long long* cell_base, long long entry_cap, long long cell_cap, unsigned* e_coord,
-                       int* e_cell, float* e_pdb, int* c_frame, int* c_rc, unsigned* c_amask) {
+hipError_t launch_emit_rows(hipStream_t st, const float2* rds, const unsigned long long* mask, int F, int A, int S,
+                            int C, const int* entry_row_off, const int* cell_row_off, const long long* entry_base,
+                            const long long* cell_base, long long entry_cap, long long cell_cap, unsigned* e_coord,
+                            int* e_cell, float* e_pdb, int* c_frame, int* c_rc, unsigned* c_amask) {
   if (F <= 0) return hipSuccess;
   const int W = (C + 63) / 64;
   const long rows = (long)F * S;

@@ -87,19 +87,23 @@ hipError_t launch_detect_oscfar(hipStream_t st, const float* power, int F, int S
 hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const int* row_count, int F, int A, int S,
                           int C, int* entry_row_off, int* cell_row_off, int* cell_row_cnt, long long* entry_base,
                           long long* cell_base, long long* frame_counts, unsigned long long* umask);
-// Emit compacted entries and cells in reference order.
-hipError_t launch_emit(hipStream_t st, const float2* rds, const unsigned long long* mask, int F, int A, int S, int C,
-                       const int* entry_row_off, const int* cell_row_off, const long long* entry_base,
-                       const long long* cell_base, long long entry_cap, long long cell_cap, unsigned* e_coord,
-                       int* e_cell, float* e_pdb, int* c_frame, int* c_rc, unsigned* c_amask);
-
-// Emit from group-compact peak powers (pk_group rows per group, 1 = row-compact) and union masks (no RDS read);
-// W = ceil(C/64) must be a power of two <= 64.
-hipError_t launch_emit2(hipStream_t st, const unsigned long long* mask, const unsigned long long* umask,
-                        const float* pk_pow, int pk_group, int F, int A, int S, int C, const int* entry_row_off,
-                        const int* cell_row_off, const long long* entry_base, const long long* cell_base,
-                        long long entry_cap, long long cell_cap, unsigned* e_coord, int* e_cell, float* e_pdb,
-                        int* c_frame, int* c_rc, unsigned* c_amask);
+// Emit compacted entries and cells in reference order, by one of two paths (rsl_detect.hip's header says what each
+// computes).  The compact path serves a call with the union mask, with peak powers unless no power_db is wanted, and
+// with a power-of-two count W = ceil(C / 64) <= 64 of mask words per row; the general path serves every other call.
+bool emit_compact_supported(int C, bool union_mask, bool peak_pow, bool want_pdb);
+// General path: one wave per range row, power_db from the RDS.
+hipError_t launch_emit_rows(hipStream_t st, const float2* rds, const unsigned long long* mask, int F, int A, int S,
+                            int C, const int* entry_row_off, const int* cell_row_off, const long long* entry_base,
+                            const long long* cell_base, long long entry_cap, long long cell_cap, unsigned* e_coord,
+                            int* e_cell, float* e_pdb, int* c_frame, int* c_rc, unsigned* c_amask);
+// Compact path, only where emit_compact_supported: block compactions of the masks and the union masks, power_db from
+// the group-compact peak powers (pk_group rows per group, 1 = row-compact); no RDS read.
+hipError_t launch_emit_compact(hipStream_t st, const unsigned long long* mask, const unsigned long long* umask,
+                               const float* pk_pow, int pk_group, int F, int A, int S, int C,
+                               const int* entry_row_off, const int* cell_row_off, const long long* entry_base,
+                               const long long* cell_base, long long entry_cap, long long cell_cap,
+                               unsigned* e_coord, int* e_cell, float* e_pdb, int* c_frame, int* c_rc,
+                               unsigned* c_amask);
 // K4..K7, the direction-of-arrival stage.  CellList (the cells of a call) and steer_layout (the sections of the
 // steering table) are in rsl_doa_common.h.
 // K5: steering scan on MFMA (f32 16x16x4), argmax; optional spectrum (spec_ld 0: cell-major [n][G], > 0: grid-major

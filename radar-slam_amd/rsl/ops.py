@@ -13,7 +13,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, tables
-from .runtime import Context, get_context, unpack_coord
+from .runtime import Context, emit_compact_supported, get_context, unpack_coord
 
 
 def _ctx(ctx: Optional[Context]) -> Context:
@@ -80,28 +80,43 @@ def range_doppler(frames, table: np.ndarray, *, chirp0=0, num_chirps=None, dc_re
 
 
 # -- a8 -------------------------------------------------------------------------------------------------
-def _detect_peaks(rds, ctx: Optional[Context], want_db, detector):
-    """The peak dictionary of detect_peaks from ``detector(c, d)`` -> (mask, row_count, dB map) on the device RDS d."""
-    c = _ctx(ctx)
+def _dev_rds4(c: Context, rds):
+    """rds [A, S, C] or [F, A, S, C] -> the contiguous complex64 device tensor [F, A, S, C] (F = 1 for three axes)."""
     d = as_dev_c64(c, rds)
     if d.dim() == 3:
         d = d.unsqueeze(0)
-    d = d.contiguous()
-    F, A, S, C = d.shape
-    mask, rc, db = detector(c, d)
+    return d.contiguous()
+
+
+def _peak_result(c: Context, d, mask, rc, db, want_db, peak_pow=None, pdb_from_db=False):
+    """The peak dictionary of detect_peaks from a detector's outputs (mask, row_count, dB map) on the device RDS d:
+    offsets, emit and the host unpack.  power_db is the emit's; with pdb_from_db it is gathered from the dB map."""
+    F, C = d.shape[0], d.shape[3]
     offs = c.offsets(mask, rc, C)
     ne = int(offs['entry_base'][F].item())
     nc = int(offs['cell_base'][F].item())
-    lists = c.emit(d, mask, offs, ne, nc, want_pdb=True)
+    lists = c.emit(d, mask, offs, ne, nc, want_pdb=not pdb_from_db, peak_pow=peak_pow)
     ant, rbin, dbin = unpack_coord(to_host(lists['e_coord'][:ne]))
+    if pdb_from_db:
+        fr = np.searchsorted(to_host(offs['entry_base']), np.arange(ne), side='right') - 1
+        pdb = to_host(db, np.float64)[fr, 0, rbin, dbin]
+    else:
+        pdb = to_host(lists['e_pdb'][:ne], np.float64)
     res = dict(antenna=ant.astype(np.int64), range_bin=rbin.astype(np.int64), doppler_bin=dbin.astype(np.int64),
-               power_db=to_host(lists['e_pdb'][:ne], np.float64),
-               entry_base=to_host(offs['entry_base']), cells=nc)
+               power_db=pdb, entry_base=to_host(offs['entry_base']), cells=nc)
     if want_db:
         res['power_spectrum_db'] = to_host(db, np.float64)
         if F == 1:
             res['power_spectrum_db'] = res['power_spectrum_db'][0]
     return res
+
+
+def _detect_peaks(rds, ctx: Optional[Context], want_db, detector):
+    """The peak dictionary of detect_peaks from ``detector(c, d)`` -> (mask, row_count, dB map) on the device RDS d."""
+    c = _ctx(ctx)
+    d = _dev_rds4(c, rds)
+    mask, rc, db = detector(c, d)
+    return _peak_result(c, d, mask, rc, db, want_db)
 
 
 def detect_peaks(rds, *, threshold_db=-20.0, i_lo=0, i_hi=1 << 30, want_db=True, ctx: Optional[Context] = None):
@@ -127,13 +142,6 @@ def detect_peaks_cfar(rds, *, guard=(2, 2), train=(8, 8), pfa=1e-4, alpha=None, 
 
 
 # -- non-coherent integration: detection on the antenna-summed power map --------------------------------
-def _dev_rds4(c: Context, rds):
-    d = as_dev_c64(c, rds)
-    if d.dim() == 3:
-        d = d.unsqueeze(0)
-    return d.contiguous()
-
-
 def integrate_power(rds, ctx: Optional[Context] = None, keep_on_device=False):
     """rds [A, S, C] or [F, A, S, C] -> the antenna-summed power map [S, C] or [F, S, C] (rsl_power_integrate: fp32
     sum of |rds|^2 over the antennas in antenna order; float64 host array, or the float32 device tensor)."""
@@ -165,27 +173,11 @@ def detect_peaks_integrated(rds, *, detector='cfar', method='ca', rank=0.75, gua
         alpha = tables.cfar_design_alpha(method, pfa, guard, train, rank, looks=A) if detector == 'cfar' else 1.0
     power = c.integrate_power(d)
     pk = c.empty((F, 1, S, C), c.torch.float32)
-    W = (C + 63) // 64
-    on_dev = (W & (W - 1)) == 0  # else emit would recompute power_db from the RDS: gather it from the dB map instead
+    # without the compact path emit would recompute power_db from the RDS: gather it from the dB map instead
+    on_dev = emit_compact_supported(C, True, True, True)
     mask, rc, db = c.detect_power(power, rule, guard, train, rank, alpha, tables.power_threshold(threshold_db), i_lo,
                                   i_hi, want_db=want_db or not on_dev, out=dict(peak_pow=pk))
-    offs = c.offsets(mask, rc, C)
-    ne = int(offs['entry_base'][F].item())
-    nc = int(offs['cell_base'][F].item())
-    lists = c.emit(d, mask, offs, ne, nc, want_pdb=on_dev, peak_pow=pk)
-    ant, rbin, dbin = unpack_coord(to_host(lists['e_coord'][:ne]))
-    if on_dev:
-        pdb = to_host(lists['e_pdb'][:ne], np.float64)
-    else:
-        fr = np.searchsorted(to_host(offs['entry_base']), np.arange(ne), side='right') - 1
-        pdb = to_host(db, np.float64)[fr, 0, rbin, dbin]
-    res = dict(antenna=ant.astype(np.int64), range_bin=rbin.astype(np.int64), doppler_bin=dbin.astype(np.int64),
-               power_db=pdb, entry_base=to_host(offs['entry_base']), cells=nc)
-    if want_db:
-        res['power_spectrum_db'] = to_host(db, np.float64)
-        if F == 1:
-            res['power_spectrum_db'] = res['power_spectrum_db'][0]
-    return res
+    return _peak_result(c, d, mask, rc, db, want_db, peak_pow=pk, pdb_from_db=not on_dev)
 
 
 # -- signatures as a pseudo-RDS [N, A, 1, 1] -------------------------------------------------------------
@@ -200,10 +192,7 @@ def _sig_cells(c: Context, sigs: np.ndarray):
 
 
 def _rds_cells(c: Context, rds, rbins, dbins):
-    d = as_dev_c64(c, rds)
-    if d.dim() == 3:
-        d = d.unsqueeze(0)
-    d = d.contiguous()
+    d = _dev_rds4(c, rds)
     _, A, S, C = d.shape
     rb = np.asarray(rbins, dtype=np.int64)
     db = np.asarray(dbins, dtype=np.int64)

@@ -25,6 +25,13 @@ def unpack_coord(coord: np.ndarray):
     return ((u >> 26).astype(np.int32), ((u >> 13) & 0x1fff).astype(np.int32), (u & 0x1fff).astype(np.int32))
 
 
+def emit_compact_supported(C: int, union_mask: bool, peak_pow: bool, want_pdb: bool) -> bool:
+    """Whether rsl_peak_emit takes its compact path (power_db from the peak powers) and not the general one, which
+    recomputes power_db from the RDS: the rule of emit_compact_supported in csrc/rsl_internal.h."""
+    W = (C + 63) // 64
+    return bool(union_mask and (peak_pow or not want_pdb) and not W & (W - 1) and W <= 64)
+
+
 _HIP = None
 
 
@@ -301,8 +308,8 @@ class Context:
         torch = self.torch
         F, _, S, C = rds.shape
         A = int(mask.shape[1])
-        W = int(mask.shape[3])
-        if want_pdb and A != rds.shape[1] and (peak_pow is None or offs.get('union_mask') is None or W & (W - 1)):
+        if want_pdb and A != rds.shape[1] and not emit_compact_supported(C, offs.get('union_mask') is not None,
+                                                                         peak_pow is not None, True):
             # rsl_peak_emit would recompute power_db from the RDS, which is not the map these masks were taken on
             raise ValueError('emit: masks of another antenna count than the RDS need peak_pow, the union mask and a '
                              'power-of-two count of mask words per row (or want_pdb=False)')

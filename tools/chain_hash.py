@@ -20,62 +20,74 @@ from rsl import tables  # noqa: E402
 from rsl.runtime import spectrum_rows  # noqa: E402
 from bench import make_cubes  # noqa: E402
 
-A, C, TC = {'cfg1': (8, 64, 25.6e-6), 'cfg2': (8, 128, 51.2e-6), 'cfg5': (16, 256, 102.4e-6), 'gen32': (4, 32, 12.8e-6),
-            'gen64': (2, 64, 6.4e-6), 'unf48': (6, 48, 9.6e-6)}[os.environ.get('CFG', 'cfg2')]
-F = int(os.environ.get('F', '200'))
-ctx = rsl.get_context(0)
-cfg = rsl.ChainConfig(num_antennas=A, num_chirps=C, chirp_duration=TC)
-ch = rsl.RadarChain(cfg, F, ctx)
-cube = make_cubes(ctx, 1, F, A, C, TC, 0)[0]
-ch.run(cube)
-torch.cuda.synchronize()
-ne, nc = ch.totals()
-out = {}
+# (antennas, chirps, chirp duration) by CFG name
+CONFIGS = {'cfg1': (8, 64, 25.6e-6), 'cfg2': (8, 128, 51.2e-6), 'cfg5': (16, 256, 102.4e-6), 'gen32': (4, 32, 12.8e-6),
+           'gen64': (2, 64, 6.4e-6), 'unf48': (6, 48, 9.6e-6)}
 
 
-def sha(t):
-    return hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:12]
-
-
-for name, t in (('rds', ch.rds), ('mask', ch.mask), ('row_count', ch.row_count), ('entry_base', ch.offs['entry_base']),
-                ('peak_pow', ch.peak_pow.view(-1)[:ne]), ('e_pdb', ch.lists['e_pdb'][:ne]),
-                ('c_rc', ch.lists['c_rc'][:nc]), ('gidx', ch.gidx[:nc]), ('esprit', ch.ext['esprit'][:nc]),
-                ('phase', ch.ext['phase'][:nc]), ('vel', ch.vel)):
-    out[name] = sha(t)
-
-# The detectors the chain does not run, on the chain's RDS: mask, row counts and the row-compact peak powers' prefix.
-W = (C + 63) // 64
-for name, run in (('det', lambda o: ctx.detect(ch.rds, ch.thr_p, ch.i_lo, ch.i_hi, out=o)),
-                  ('cfar', lambda o: ctx.detect_cfar(ch.rds, (2, 2), (8, 8), 12.0, ch.thr_p, ch.i_lo, ch.i_hi, out=o)),
-                  ('oscfar', lambda o: ctx.detect_oscfar(ch.rds, (2, 2), (8, 8), 0.75, 6.0, ch.thr_p, ch.i_lo, ch.i_hi,
-                                                         out=o))):
-    o = dict(mask=torch.zeros((F, A, ch.S, W), dtype=torch.int64, device=ctx.device),
-             row_count=torch.zeros((F, A, ch.S), dtype=torch.int32, device=ctx.device),
-             peak_pow=torch.zeros((F, A, ch.S, C), dtype=torch.float32, device=ctx.device))
-    run(o)
+def main():
+    A, C, TC = CONFIGS[os.environ.get('CFG', 'cfg2')]
+    F = int(os.environ.get('F', '200'))
+    ctx = rsl.get_context(0)
+    cfg = rsl.ChainConfig(num_antennas=A, num_chirps=C, chirp_duration=TC)
+    ch = rsl.RadarChain(cfg, F, ctx)
+    cube = make_cubes(ctx, 1, F, A, C, TC, 0)[0]
+    ch.run(cube)
     torch.cuda.synchronize()
-    out[name + '_mask'], out[name + '_rows'], out[name + '_pk'] = sha(o['mask']), sha(o['row_count']), sha(o['peak_pow'])
-    out[name + '_n'] = int(o['row_count'].sum().item())
-    del o
+    ne, nc = ch.totals()
+    out = {}
 
-# The DoA paths the chain does not run, on (a prefix of) the chain's own cell list: the f32 scans (argmax with gmax; the
-# three spectrum layouts), the Toeplitz cell-blocked spectrum, and the spatially smoothed MUSIC.
-n = min(nc, int(os.environ.get('NDOA', '100003')))
-L = ch.lists
-args = (ch.rds, L['c_frame'], L['c_rc'], ch.steer, ch.method)
-idx, gmax, _ = ctx.doa(*args, n=n, fast=False, want_gmax=True)
-out['f32_idx'], out['f32_gmax'] = sha(idx[:n]), sha(gmax[:n])
-for name, kw in (('f32_spec_cm', {}), ('f32_spec_gm', {'spec_gmajor': True}), ('f32_spec_bl', {'spec_blocked': True}),
-                 ('toep_spec_bl', {'spec_blocked': True, 'fast': True})):
-    idx, _, spec = ctx.doa(*args, n=n, want_spec=True, **{'fast': False, **kw})
-    out[name] = sha(spectrum_rows(spec, n) if 'spec_blocked' in kw else spec)
-    out[name + '_idx'] = sha(idx[:n])
-    del spec
-d = cfg.antenna_spacing or cfg.lambda_c / 2
-steer = tables.steering_matrix(ch.grid, np.arange(A) * d, cfg.lambda_c)
-if A >= 3:  # the smoothed estimator needs three antennas
-    sub_len = tables.default_sub_len(A)
-    sub = ctx.steering_sub(steer, sub_len)
-    nsrc, idx, den, _, _ = ctx.doa_smoothed(ch.rds, L['c_frame'], L['c_rc'], sub, n=n, nmax=min(3, sub_len - 1))
-    out['ss_nsrc'], out['ss_idx'], out['ss_den'] = sha(nsrc[:n]), sha(idx[:n]), sha(den[:n])
-print(json.dumps(out), flush=True)
+    def sha(t):
+        return hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:12]
+
+    for name, t in (('rds', ch.rds), ('mask', ch.mask), ('row_count', ch.row_count),
+                    ('entry_base', ch.offs['entry_base']), ('peak_pow', ch.peak_pow.view(-1)[:ne]),
+                    ('e_pdb', ch.lists['e_pdb'][:ne]),
+                    ('c_rc', ch.lists['c_rc'][:nc]), ('gidx', ch.gidx[:nc]), ('esprit', ch.ext['esprit'][:nc]),
+                    ('phase', ch.ext['phase'][:nc]), ('vel', ch.vel)):
+        out[name] = sha(t)
+
+    # The detectors the chain does not run, on the chain's RDS: mask, row counts and the row-compact peak powers'
+    # prefix.
+    W = (C + 63) // 64
+    for name, run in (('det', lambda o: ctx.detect(ch.rds, ch.thr_p, ch.i_lo, ch.i_hi, out=o)),
+                      ('cfar', lambda o: ctx.detect_cfar(ch.rds, (2, 2), (8, 8), 12.0, ch.thr_p, ch.i_lo, ch.i_hi,
+                                                         out=o)),
+                      ('oscfar', lambda o: ctx.detect_oscfar(ch.rds, (2, 2), (8, 8), 0.75, 6.0, ch.thr_p, ch.i_lo,
+                                                             ch.i_hi, out=o))):
+        o = dict(mask=torch.zeros((F, A, ch.S, W), dtype=torch.int64, device=ctx.device),
+                 row_count=torch.zeros((F, A, ch.S), dtype=torch.int32, device=ctx.device),
+                 peak_pow=torch.zeros((F, A, ch.S, C), dtype=torch.float32, device=ctx.device))
+        run(o)
+        torch.cuda.synchronize()
+        out[name + '_mask'], out[name + '_rows'] = sha(o['mask']), sha(o['row_count'])
+        out[name + '_pk'] = sha(o['peak_pow'])
+        out[name + '_n'] = int(o['row_count'].sum().item())
+        del o
+
+    # The DoA paths the chain does not run, on (a prefix of) the chain's own cell list: the f32 scans (argmax with gmax;
+    # the three spectrum layouts), the Toeplitz cell-blocked spectrum, and the spatially smoothed MUSIC.
+    n = min(nc, int(os.environ.get('NDOA', '100003')))
+    L = ch.lists
+    args = (ch.rds, L['c_frame'], L['c_rc'], ch.steer, ch.method)
+    idx, gmax, _ = ctx.doa(*args, n=n, fast=False, want_gmax=True)
+    out['f32_idx'], out['f32_gmax'] = sha(idx[:n]), sha(gmax[:n])
+    for name, kw in (('f32_spec_cm', {}), ('f32_spec_gm', {'spec_gmajor': True}),
+                     ('f32_spec_bl', {'spec_blocked': True}),
+                     ('toep_spec_bl', {'spec_blocked': True, 'fast': True})):
+        idx, _, spec = ctx.doa(*args, n=n, want_spec=True, **{'fast': False, **kw})
+        out[name] = sha(spectrum_rows(spec, n) if 'spec_blocked' in kw else spec)
+        out[name + '_idx'] = sha(idx[:n])
+        del spec
+    d = cfg.antenna_spacing or cfg.lambda_c / 2
+    steer = tables.steering_matrix(ch.grid, np.arange(A) * d, cfg.lambda_c)
+    if A >= 3:  # the smoothed estimator needs three antennas
+        sub_len = tables.default_sub_len(A)
+        sub = ctx.steering_sub(steer, sub_len)
+        nsrc, idx, den, _, _ = ctx.doa_smoothed(ch.rds, L['c_frame'], L['c_rc'], sub, n=n, nmax=min(3, sub_len - 1))
+        out['ss_nsrc'], out['ss_idx'], out['ss_den'] = sha(nsrc[:n]), sha(idx[:n]), sha(den[:n])
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == '__main__':
+    main()

@@ -1,7 +1,8 @@
-"""k_offsets + k_frame_scan and the compaction (k_emit_cells + k_emit_block) standalone on one cfg2 batch
-(development or product library via RSL_LIBRARY): min over 3 rounds of the mean of 20 launches, and a checksum of
-every output (equal checksums across two libraries = identical offsets and lists).
-GPU box:  RSL_LIBRARY=... python tools/offsets_time.py"""
+"""k_offsets + k_frame_scan and the compaction (k_emit_cells + k_emit_entries) standalone on one chain batch (cfg2, or a
+configuration of tools/chain_hash.py by name: unf48 has S * W = 96, partly filled cell blocks; development or product
+library via RSL_LIBRARY): min over 3 rounds of the mean of 20 launches, and a checksum of every output (equal
+checksums across two libraries = identical offsets and lists).
+GPU box:  [CFG=cfg2|...] [F=frames] RSL_LIBRARY=... python tools/offsets_time.py"""
 import hashlib
 import json
 import os
@@ -13,12 +14,14 @@ import torch  # noqa: E402
 
 import rsl  # noqa: E402
 from bench import make_cubes  # noqa: E402
+from chain_hash import CONFIGS  # noqa: E402
 
+A, C, TC = CONFIGS[os.environ.get('CFG', 'cfg2')]
 F = int(os.environ.get('F', '2000'))
 ctx = rsl.get_context(0)
-cfg = rsl.ChainConfig(num_antennas=8, num_chirps=128, chirp_duration=51.2e-6)
+cfg = rsl.ChainConfig(num_antennas=A, num_chirps=C, chirp_duration=TC)
 ch = rsl.RadarChain(cfg, F, ctx)
-cube = make_cubes(ctx, 1, F, 8, 128, 51.2e-6, 0)[0]
+cube = make_cubes(ctx, 1, F, A, C, TC, 0)[0]
 ch.run(cube)
 torch.cuda.synchronize()
 ne, nc = ch.totals()

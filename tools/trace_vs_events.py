@@ -1,7 +1,7 @@
 """Live per-kernel time from the two sources of ONE profiled bench run: the rocprofv3 kernel trace
 (begin / end of every dispatch) and the bench's own hipEvent spans (`live_timeline.spans_ms` in its JSON line, one
 [start, end] per launch of each timing scope).  The trace's dispatches are grouped into the bench's scopes (range_fft =
-K1, doppler_fft = K2, offsets = k_offsets + k_frame_scan, emit = k_emit_cells + k_emit_block, doa_scan = k_doa_toep +
+K1, doppler_fft = K2, offsets = k_offsets + k_frame_scan, emit = k_emit_cells + k_emit_entries, doa_scan = k_doa_toep +
 k_doa_fixup, velocity = k_velocity), the timed steps are aligned on the first timed K1, and every scope launch is
 compared: trace [first kernel begin, last kernel end] against the event span.
 usage: python tools/trace_vs_events.py TRACE_kernel_trace.csv BENCH_LOG"""
@@ -10,10 +10,10 @@ import json
 import sys
 
 SCOPES = {'k_range_fft': 'range_fft', 'k_doppler_detect': 'doppler_fft', 'k_offsets': 'offsets', 'k_frame_scan': 'offsets',
-          'k_emit_cells': 'emit', 'k_emit_block': 'emit', 'k_doa_toep': 'doa_scan', 'k_doa_fixup': 'doa_scan',
+          'k_emit_cells': 'emit', 'k_emit_entries': 'emit', 'k_doa_toep': 'doa_scan', 'k_doa_fixup': 'doa_scan',
           'k_velocity': 'velocity'}
 FIRST = {'offsets': 'k_offsets', 'emit': 'k_emit_cells', 'doa_scan': 'k_doa_toep'}
-LAST = {'offsets': 'k_frame_scan', 'emit': 'k_emit_block', 'doa_scan': 'k_doa_fixup'}
+LAST = {'offsets': 'k_frame_scan', 'emit': 'k_emit_entries', 'doa_scan': 'k_doa_fixup'}
 
 
 def short(name):
