@@ -100,7 +100,8 @@ int rsl_rds(rsl_handle h, const void* cube, int F, int A, int C_total, int chirp
  *     range gate i_lo <= range_bin <= i_hi (from linspace(0, rr*S, S) on the host);
  *     mask u64 [F, A, S, W], W = ceil(C/64) (bit j%64 of word j/64 = peak at doppler j);
  *     row_count i32 [F, A, S];  db_map f32 [F, A, S, C] (nullable) = 10 log10(|rds|^2 + 1e-12);
- *     peak_pow f32 [F, A, S, C] (nullable): row-compact |rds|^2 of the peaks, slot = rank within the row. */
+ *     peak_pow f32 [F, A, S, C] (nullable): row-compact |rds|^2 of the peaks, slot = rank within the row.
+ *     RSL_ERR_UNSUPPORTED: C > 4096 (every length rsl_rds produces is supported). */
 int rsl_detect(rsl_handle h, const void* rds, int F, int A, int S, int C, double thr_power, int i_lo, int i_hi,
                void* mask, void* row_count, void* db_map, void* peak_pow);
 

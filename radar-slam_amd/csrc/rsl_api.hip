@@ -315,7 +315,7 @@ int rsl_detect(rsl_handle h, const void* rds, int F, int A, int S, int C, double
   if (F < 0 || A <= 0 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_detect: bad shape");
   if (F == 0) return RSL_OK;
   if (!rds || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect: null pointer");
-  if ((size_t)(18 * (size_t)C * 4) > 64 * 1024) return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect: C too large");
+  if (!rsl::detect_rows(C)) return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect: C too large");
   Scope sc(h, RSL_K_DETECT);
   const rsl::DetectArgs det = detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow);
   return hip_check(h, rsl::launch_detect(h->stream, (const float2*)rds, F, A, S, C, det), "detect");
@@ -393,8 +393,7 @@ int rsl_detect_power(rsl_handle h, const void* power, int F, int S, int C, int r
       if (F < 0 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_detect_power: bad shape");
       if (F == 0) return RSL_OK;
       if (!power || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect_power: null pointer");
-      if ((size_t)(18 * (size_t)C * 4) > 64 * 1024)
-        return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect_power: C too large");
+      if (!rsl::detect_rows(C)) return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect_power: C too large");
       Scope sc(h, RSL_K_DETECT);
       return hip_check(h, rsl::launch_detect(h->stream, (const float*)power, F, S, C, det), "detect");
     }

@@ -22,7 +22,7 @@
 
 namespace rsl {
 
-constexpr int kDetRows = 16;  // shifted range rows per workgroup
+constexpr int kDetRows = 16;  // shifted range rows per workgroup (fewer at large C: detect_rows)
 
 // The largest float t <= thr: for a float p, (double)p > thr  <=>  p > t.
 float threshold_as_float(double thr) {
@@ -32,17 +32,18 @@ float threshold_as_float(double thr) {
 }
 
 // T: the map's element, float2 (c64 RDS, p = |z|^2) or float (a power map, rsl_detect_power): cell_power.
+// rows: the workgroup's shifted range rows (detect_rows); the decisions do not depend on it.
 template <class T>
-__global__ __launch_bounds__(256) void k_detect(const T* __restrict__ rds, int S, int C, int W, float thr_f,
+__global__ __launch_bounds__(256) void k_detect(const T* __restrict__ rds, int S, int C, int W, int rows, float thr_f,
                                                 int i_lo, int i_hi, unsigned long long* __restrict__ mask,
                                                 int* __restrict__ row_count, float* __restrict__ dbmap,
                                                 float* __restrict__ pk_pow) {
-  extern __shared__ float pw[];  // (kDetRows + 2) x C power values
-  const int nib = (S + kDetRows - 1) / kDetRows;
+  extern __shared__ float pw[];  // (rows + 2) x C power values
+  const int nib = (S + rows - 1) / rows;
   const int ib = blockIdx.x % nib;
   const long fa = blockIdx.x / nib;
-  const int i0 = ib * kDetRows;
-  const int nrows = min(kDetRows, S - i0);
+  const int i0 = ib * rows;
+  const int nrows = min(rows, S - i0);
   const T* base = rds + (size_t)fa * S * C;
   for (int idx = threadIdx.x; idx < (nrows + 2) * C; idx += 256) {
     const int r = idx / C, j = idx - r * C;
@@ -506,13 +507,23 @@ hipError_t launch_emit_compact(hipStream_t st, const unsigned long long* mask, c
   });
 }
 
+// Rows per k_detect workgroup: kDetRows where its (rows + 2) x C power tile fits 64 KiB of LDS (C <= 910), else the
+// largest of 8 / 4 / 2 that does (C <= 4096, every length the FFTs produce); 0 where none does.
+int detect_rows(int C) {
+  for (int r = kDetRows; r >= 2; r /= 2)
+    if (sizeof(float) * (r + 2) * (size_t)C <= 64 * 1024) return r;
+  return 0;
+}
+
 template <class T>
 static hipError_t launch_detect_maps(hipStream_t st, const T* maps, int F, int A, int S, int C, const DetectArgs& d) {
   if (F <= 0 || A <= 0 || S <= 0 || C <= 0) return hipSuccess;
   const int W = (C + 63) / 64;
-  const long nblk = (long)F * A * ((S + kDetRows - 1) / kDetRows);
-  const size_t lds = sizeof(float) * (kDetRows + 2) * (size_t)C;
-  hipLaunchKernelGGL(k_detect<T>, dim3((unsigned)nblk), dim3(256), lds, st, maps, S, C, W,
+  const int rows = detect_rows(C);
+  if (!rows) return hipErrorInvalidValue;
+  const long nblk = (long)F * A * ((S + rows - 1) / rows);
+  const size_t lds = sizeof(float) * (rows + 2) * (size_t)C;
+  hipLaunchKernelGGL(k_detect<T>, dim3((unsigned)nblk), dim3(256), lds, st, maps, S, C, W, rows,
                      threshold_as_float(d.thr_p), d.i_lo, d.i_hi, d.mask, d.row_count, d.dbmap, d.pk_pow);
   return hipGetLastError();
 }

@@ -60,7 +60,9 @@ hipError_t launch_doppler_detect(hipStream_t st, const float2* work, int F, int 
 // packed (both launches): `work` holds packed rows (rsl_packed.h: 6 B per value in 24 KiB tiles, each bin's int8
 // exponent inside its 48-B unit) -- only where work_packed_supported(C, S).
 bool work_packed_supported(int C, int S);
-// K3: 3x3 local max (reflect), threshold, range gate -> per-antenna bit masks + row counts.
+// K3: 3x3 local max (reflect), threshold, range gate -> per-antenna bit masks + row counts.  detect_rows(C): the range
+// rows per workgroup at C Doppler cells, 0 where C is too large for the kernel's LDS tile (C > 4096).
+int detect_rows(int C);
 hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S, int C, const DetectArgs& det);
 // K3 alternatives, the CFAR family (CfarWindow and the launcher both share: rsl_cfar_common.h).  Every window within
 // RSL_CFAR_MAX_HALF fits the CU's LDS at every C <= RSL_CFAR_MAX_C: each kernel file asserts it at compile time.

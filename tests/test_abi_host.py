@@ -66,6 +66,20 @@ def test_fft_support_table():
         assert lib.rsl_fft_supported(n) == 0
 
 
+def test_fft_support_table_exhaustive():
+    """1 exactly for the 17 planned lengths (the list tests/test_gpu_fft_sizes.py runs one case each for), 2 for every
+    other length up to 4096, 0 outside."""
+    import rsl
+    import rds_ref
+    lib = rsl.load()
+    assert len(set(rds_ref.PLANNED)) == 17
+    assert sorted(rds_ref.PLANNED) == [8, 16, 25, 32, 50, 64, 100, 128, 200, 256, 400, 512, 800, 1024, 1600, 2048, 4096]
+    for n in range(1, 4097):
+        assert lib.rsl_fft_supported(n) == (1 if n in rds_ref.PLANNED else 2), n
+    for n in (0, -1, 4097):
+        assert lib.rsl_fft_supported(n) == 0, n
+
+
 def test_null_handle_errors():
     import rsl
     lib = rsl.load()

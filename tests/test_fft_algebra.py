@@ -69,6 +69,66 @@ def doppler(Xr, ncls, rows):
     return out
 
 
+PLANNED = (8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 25, 50, 100, 200, 400, 800, 1600)  # RSL_FFT_SIZES
+
+
+def make_plan(N):
+    """rsl_common.h make_plan: the stage radices in order, None for a length with another prime factor.  Powers of two
+    from 128 take radix-16 stages first (one where lg N % 3 == 1, two at 256), then the order 8, 4, 2, 5, 3, 7."""
+    r, m = [], N
+    lg = 0
+    while (1 << lg) < N:
+        lg += 1
+    if (1 << lg) == N and N >= 128:
+        n16 = 1 if lg % 3 == 1 else (2 if N == 256 else 0)
+        r += [16] * n16
+        m //= 16 ** n16
+    for R in (8, 4, 2, 5, 3, 7):
+        while m > 1 and m % R == 0:
+            r.append(R)
+            m //= R
+    return r if m == 1 else None
+
+
+def stockham_stage(x, N, R, NS):
+    """One stage as fft_stage writes it: butterfly j < NB = N / R reads x[j + r NB], multiplies by tw[r k STEP] with
+    k = j % NS and STEP = N / (NS R), takes the R-point DFT and writes (j / NS) NS R + k + r NS."""
+    NB, STEP = N // R, N // (NS * R)
+    tw = W(np.arange(N), N)
+    out = np.full(N, np.nan, complex)
+    for j in range(NB):
+        k = j % NS
+        r = np.arange(R)
+        assert (r * k * STEP < N).all()  # inside the N-entry twiddle table
+        v = np.fft.fft(x[j + r * NB] * tw[r * k * STEP])
+        out[(j // NS) * NS * R + k + r * NS] = v
+    return out
+
+
+def test_stockham_plans():
+    assert make_plan(2048) == [8, 8, 8, 4]
+    assert make_plan(1600) == [8, 8, 5, 5]
+    assert make_plan(25) == [5, 5]
+    assert make_plan(4096) == [8, 8, 8, 8] and make_plan(1024) == [16, 8, 8] and make_plan(256) == [16, 16]
+    assert make_plan(59) is None and make_plan(4093) is None
+    for N in PLANNED:
+        assert int(np.prod(make_plan(N))) == N
+
+
+@pytest.mark.parametrize('N', PLANNED)
+def test_stockham_stages(N):
+    """The stage index algebra under each planned length's plan gives the N-point DFT in natural order, so a GPU
+    failure at one length points at layout or launch, not at the plan."""
+    rs = np.random.RandomState(N)
+    x = rs.randn(N) + 1j * rs.randn(N)
+    y, ns = x, 1
+    for R in make_plan(N):
+        y = stockham_stage(y, N, R, ns)
+        ns *= R
+    assert ns == N
+    np.testing.assert_allclose(y, np.fft.fft(x), atol=1e-9 * np.abs(y).max())
+
+
 @pytest.mark.parametrize('shape', [(128, 512), (256, 1024), (64, 256)])
 def test_register_form_decomposition(shape):
     C, S = shape

@@ -9,14 +9,19 @@ thr_power n), so the rule reduces to k_detect's: 3x3 'reflect' local maximum, ra
 test_cfar_rule_reduces_to_threshold_rule confirms that reduction on the CPU, cfar_ref.reference against the plain
 rule on a random map.
 
-The cube is complex noise of variance 0.02 per sample, so the mean RDS power is S * C * 0.02; with that as the threshold
-nearly every 3x3 local maximum passes (the largest of nine exponential powers exceeds their mean 98 % of the time), so
-roughly 11 % of the cells are peaks, edge rows and tile borders included.
+The cube is complex noise of variance 0.02 per sample and the window table is random and complex (rds_ref.make_table:
+an all-ones table hides a wrong table index), so the mean RDS power is S * C * 0.02 * mean |table|^2; with that as the
+threshold nearly every 3x3 local maximum passes (the largest of nine exponential powers exceeds their mean 98 % of the
+time), so roughly 11 % of the cells are peaks, edge rows and tile borders included.  The RDS the detectors agree on is
+itself compared with the fp64 numpy reference (rds_ref.reference, parity.RDS_ATOL_REL).
 """
 import numpy as np
 import pytest
 
 import cfar_ref as R
+import parity as P
+import rds_ref
+from rds_ref import LISTS, lists_of
 
 SHAPES = [  # (F, A, C, S): each the smallest that reaches its body
     (2, 2, 32, 128),    # fused, general tile body
@@ -28,7 +33,6 @@ SHAPES = [  # (F, A, C, S): each the smallest that reaches its body
 ]
 SEED = 20
 CFAR_OFF = dict(guard=(0, 0), train=(1, 1), alpha=1e-20)
-LISTS = ('e_coord', 'e_cell', 'e_pdb', 'c_frame', 'c_rc', 'c_amask')
 
 
 def test_cfar_rule_reduces_to_threshold_rule():
@@ -54,15 +58,37 @@ def make_cube(ctx, F, A, C, S):
     return torch.complex(re, im).to(ctx.device)
 
 
-def lists_of(ctx, rds, det, C):
-    """offsets + emit on one detector's outputs -> (ne, nc, the six lists cut to their counts, as bytes)."""
-    F = rds.shape[0]
-    offs = ctx.offsets(det['mask'], det['row_count'], C)
-    ne, nc = int(offs['entry_base'][F].item()), int(offs['cell_base'][F].item())
-    out = ctx.emit(rds, det['mask'], offs, ne, nc, want_pdb=True, peak_pow=det['peak_pow'],
-                   peak_pow_group=det['group'])
-    cut = {k: out[k][:(ne if k.startswith('e_') else nc)].cpu().numpy().tobytes() for k in LISTS}
-    return ne, nc, cut
+@pytest.mark.gpu
+@pytest.mark.parametrize('C', [910, 911, 1639, 2731, 4096])
+def test_detect_wide_maps(ctx, C):
+    """rsl_detect at every rows-per-workgroup value of k_detect (16 up to C = 910, then 8, 4 and 2 up to C = 4096, the
+    last with exactly 64 KiB of LDS), against the plain rule in numpy.  The map is real, so its fp32 power x * x is the
+    same number in numpy as in the kernel and the comparison is exact; S = 19 leaves a partial last tile at each value."""
+    torch = ctx.torch
+    F, A, S = 1, 2, 19
+    rng = np.random.default_rng([SEED, C])
+    x = rng.standard_normal((F, A, S, C), dtype=np.float32)
+    p = x * x
+    thr = float(np.median(p))
+    rds = ctx.to_dev(x.astype(np.complex64))
+    nb = R.neighbour_max(p.astype(np.float64))
+    for i_lo, i_hi in ((0, S - 1), (2, S - 3)):
+        g = np.zeros(S, bool)
+        g[i_lo:i_hi + 1] = True
+        want = (p.astype(np.float64) > thr) & (p >= nb) & g[:, None]
+        out = dict(peak_pow=torch.full((F, A, S, C), float('nan'), dtype=torch.float32, device=ctx.device))
+        mask, rc, _ = ctx.detect(rds, thr, i_lo, i_hi, out=out)
+        torch.cuda.synchronize()
+        got = R.mask_bool(mask.cpu().numpy(), C)
+        assert want.any() and (got == want).all(), int((got ^ want).sum())
+        assert (rc.cpu().numpy() == want.sum(axis=-1)).all()
+        pk = out['peak_pow'].cpu().numpy()
+        for a in range(A):
+            for i in range(S):
+                n = int(want[0, a, i].sum())
+                assert (pk[0, a, i, :n] == p[0, a, i][want[0, a, i]]).all() and np.isnan(pk[0, a, i, n:]).all()
+    with pytest.raises(ValueError, match='C too large'):
+        ctx.detect(ctx.empty((1, 1, 2, 4097), torch.complex64), thr, 0, 1)
 
 
 @pytest.mark.gpu
@@ -73,9 +99,10 @@ def test_detectors_agree(ctx, shape, gate):
     F, A, C, S = shape
     i_lo, i_hi = (0, S - 1) if gate == 'full' else (3, S - 5)
     W = (C + 63) // 64
-    thr = S * C * 0.02
+    tab = rds_ref.make_table(S, SEED)
+    thr = rds_ref.mean_power(tab, S, C)
     cube = make_cube(ctx, F, A, C, S)
-    table = torch.ones((S,), dtype=torch.complex64, device=ctx.device)
+    table = ctx.to_dev(tab)
 
     def buffers():
         return dict(mask=ctx.empty((F, A, S, W), torch.int64), row_count=ctx.empty((F, A, S), torch.int32),
@@ -97,6 +124,9 @@ def test_detectors_agree(ctx, shape, gate):
     torch.cuda.synchronize()
 
     host = lambda t: t.cpu().numpy()
+    err = P.rds_error(host(rds), rds_ref.reference(host(cube), tab, 0, C, True))
+    print(f'\n{shape}: rds error {err:.3e}')
+    assert err <= P.RDS_ATOL_REL, err
     m0, r0, d0 = host(fused['mask']), host(fused['row_count']), host(fused['db'])
     frac = r0.sum() / (F * A * (i_hi - i_lo + 1) * C)
     print(f'\n{shape} gate {(i_lo, i_hi)}: group {fused["group"]}, peaks {int(r0.sum())} ({100 * frac:.2f} % of the gated '
