@@ -747,30 +747,39 @@ int rsl_associate_nearest(rsl_handle h, const void* range_m, const void* az_rad,
                    "associate_nearest");
 }
 
+// The checks rsl_wrapped_solve and rsl_wrapped_search (fn) share, in their order: the arguments (own_bad: the entry
+// point's own conditions), the pointers (own_null: one of the entry point's own is null), the box, then the scratch
+// size (need: the entry point's *_scratch_bytes).
+static int wrapped_check(rsl_handle h, const std::string& fn, const rsl::WrapArgs& a, bool own_bad, bool own_null,
+                         const void* scratch, long long scratch_bytes, long long need, const void* out) {
+  if (!h) return RSL_ERR_INVALID;
+  if (a.n < 1 || (a.nv != 3 && a.nv != 6) || (a.mode != 0 && a.mode != 1) || own_bad || a.nextra < 0 || a.iters < 0)
+    return fail(h, RSL_ERR_INVALID, fn + ": bad argument");
+  if (!a.pos || !a.ang || !a.y || !a.lo || !a.hi || own_null || !scratch || !out || (a.nextra > 0 && !a.extra))
+    return fail(h, RSL_ERR_INVALID, fn + ": null pointer");
+  for (int c = 0; c < 6; ++c)
+    if (!(a.lo[c] <= a.hi[c])) return fail(h, RSL_ERR_INVALID, fn + ": bad bounds");
+  if (scratch_bytes < need) return fail(h, RSL_ERR_INVALID, fn + ": scratch too small");
+  return RSL_OK;
+}
+
 long long rsl_wrapped_scratch_bytes(long long n, int grid_n, int nextra) {
   if (n < 0 || grid_n < 0 || nextra < 0) return -1;
-  return 8LL * (6 * n + 36 + 8 * ((long long)grid_n * grid_n + nextra));
+  return 8LL * rsl::WrappedSolveScratch(nullptr, n, (long long)grid_n * grid_n + nextra).total;
 }
 
 int rsl_wrapped_solve(rsl_handle h, const void* pos, const void* ang, long long n, const void* y, double k, int mode,
                       double w, double vmax, double wmax, const void* prev, const double* lo6, const double* hi6,
                       int nv, int grid_n, const void* extra, int nextra, int iters, void* scratch,
                       long long scratch_bytes, void* out) {
-  if (!h) return RSL_ERR_INVALID;
-  if (n < 1 || (nv != 3 && nv != 6) || (mode != 0 && mode != 1) || grid_n < 0 || nextra < 0 || iters < 0 ||
-      grid_n * (long long)grid_n + nextra < 1)
-    return fail(h, RSL_ERR_INVALID, "rsl_wrapped_solve: bad argument");
-  if (!pos || !ang || !y || !lo6 || !hi6 || !scratch || !out || (nextra > 0 && !extra))
-    return fail(h, RSL_ERR_INVALID, "rsl_wrapped_solve: null pointer");
-  for (int a = 0; a < 6; ++a)
-    if (!(lo6[a] <= hi6[a])) return fail(h, RSL_ERR_INVALID, "rsl_wrapped_solve: bad bounds");
-  if (scratch_bytes < rsl_wrapped_scratch_bytes(n, grid_n, nextra))
-    return fail(h, RSL_ERR_INVALID, "rsl_wrapped_solve: scratch too small");
+  const rsl::WrapArgs a = {(const double*)pos, (const double*)ang, n, (const double*)y, k, mode, w, vmax, wmax,
+                           (const double*)prev, lo6, hi6, nv, (const double*)extra, nextra, iters};
+  const bool own_bad = grid_n < 0 || grid_n * (long long)grid_n + nextra < 1;
+  if (const int rc = wrapped_check(h, "rsl_wrapped_solve", a, own_bad, false, scratch, scratch_bytes,
+                                   rsl_wrapped_scratch_bytes(n, grid_n, nextra), out))
+    return rc;
   Scope sc(h, RSL_K_VELOCITY);
-  return hip_check(h,
-                   rsl::launch_wrapped_solve(h->stream, (const double*)pos, (const double*)ang, n, (const double*)y,
-                                             k, mode, w, vmax, wmax, (const double*)prev, lo6, hi6, nv, grid_n,
-                                             (const double*)extra, nextra, iters, (double*)scratch, (double*)out),
+  return hip_check(h, rsl::launch_wrapped_solve(h->stream, a, grid_n, (double*)scratch, (double*)out),
                    "wrapped_solve");
 }
 
@@ -792,32 +801,23 @@ long long rsl_wrapped_search_scratch_bytes(long long n, const double* lo6, const
   if (n < 0 || !lo6 || !hi6 || nbest < 1 || nextra < 0) return -1;
   long long gx, gy;
   search_grid(lo6, hi6, spacing, &gx, &gy);
-  return 8LL * rsl::wrapped_search_scratch_doubles(n, gx * gy, nbest, nextra);
+  return 8LL * rsl::WrappedSearchScratch(nullptr, n, gx * gy, (long long)nbest + nextra).total;
 }
 
 int rsl_wrapped_search(rsl_handle h, const void* pos, const void* ang, long long n, const void* y, double k, int mode,
                        double w, double vmax, double wmax, const void* prev, const double* lo6, const double* hi6,
                        int nv, const double* base6, double spacing, int nbest, const void* extra, int nextra, int iters,
                        void* scratch, long long scratch_bytes, void* out) {
-  if (!h) return RSL_ERR_INVALID;
-  if (n < 1 || (nv != 3 && nv != 6) || (mode != 0 && mode != 1) || !(spacing > 0) || nbest < 1 || nbest > 1024 ||
-      nextra < 0 || iters < 0)
-    return fail(h, RSL_ERR_INVALID, "rsl_wrapped_search: bad argument");
-  if (!pos || !ang || !y || !lo6 || !hi6 || !base6 || !scratch || !out || (nextra > 0 && !extra))
-    return fail(h, RSL_ERR_INVALID, "rsl_wrapped_search: null pointer");
-  for (int a = 0; a < 6; ++a)
-    if (!(lo6[a] <= hi6[a])) return fail(h, RSL_ERR_INVALID, "rsl_wrapped_search: bad bounds");
-  if (scratch_bytes < rsl_wrapped_search_scratch_bytes(n, lo6, hi6, spacing, nbest, nextra))
-    return fail(h, RSL_ERR_INVALID, "rsl_wrapped_search: scratch too small");
+  const rsl::WrapArgs a = {(const double*)pos, (const double*)ang, n, (const double*)y, k, mode, w, vmax, wmax,
+                           (const double*)prev, lo6, hi6, nv, (const double*)extra, nextra, iters};
+  const bool own_bad = !(spacing > 0) || nbest < 1 || nbest > 1024;
+  if (const int rc = wrapped_check(h, "rsl_wrapped_search", a, own_bad, !base6, scratch, scratch_bytes,
+                                   rsl_wrapped_search_scratch_bytes(n, lo6, hi6, spacing, nbest, nextra), out))
+    return rc;
   long long gx, gy;
   search_grid(lo6, hi6, spacing, &gx, &gy);
-  hipSetDevice(h->device);
   Scope sc(h, RSL_K_VELOCITY);
-  return hip_check(h,
-                   rsl::launch_wrapped_search(h->stream, (const double*)pos, (const double*)ang, n, (const double*)y,
-                                              k, mode, w, vmax, wmax, (const double*)prev, lo6, hi6, nv, base6, gx,
-                                              gy, nbest, (const double*)extra, nextra, iters, (double*)scratch,
-                                              (double*)out),
+  return hip_check(h, rsl::launch_wrapped_search(h->stream, a, base6, gx, gy, nbest, (double*)scratch, (double*)out),
                    "wrapped_search");
 }
 

@@ -155,15 +155,62 @@ hipError_t launch_associate_nearest(hipStream_t st, const double* range_m, const
                                     double* dist, double* phase);
 hipError_t launch_associate(hipStream_t st, const double* cur, int nc, const double* prev, int np, double thr,
                             unsigned* used_scratch, int* match, double* dist);
-long wrapped_search_scratch_doubles(long n, long nstart1, int nbest, int nextra);
-hipError_t launch_wrapped_search(hipStream_t st, const double* pos, const double* ang, long n, const double* y,
-                                 double k, int mode, double w, double vmax, double wmax, const double* prev,
-                                 const double* lo, const double* hi, int nv, const double* base6, long gx, long gy,
-                                 int nbest, const double* extra, int nextra, int iters, double* scratch, double* out);
-hipError_t launch_wrapped_solve(hipStream_t st, const double* pos, const double* ang, long n, const double* y,
-                                double k, int mode, double w, double vmax, double wmax, const double* prev,
-                                const double* lo, const double* hi, int nv, int gn, const double* extra, int nextra,
-                                int iters, double* scratch, double* out);
+// The arguments rsl_wrapped_solve and rsl_wrapped_search share (include/rsl.h).
+struct WrapArgs {
+  const double *pos, *ang;
+  long n;
+  const double* y;
+  double k;
+  int mode;
+  double w, vmax, wmax;
+  const double *prev, *lo, *hi;
+  int nv;
+  const double* extra;
+  int nextra, iters;
+};
+// The scratch buffers of the two wrapped launchers, in doubles.  Each section's size is stated once, in the order of
+// the layout: the launcher carves its pointers with the struct, rsl_wrapped_scratch_bytes and
+// rsl_wrapped_search_scratch_bytes take `total` of one built on a null buffer (whose pointers stay null).
+struct ScratchCarver {
+  double* buf;
+  long used;
+  double* take(long doubles) {
+    double* p = buf ? buf + used : nullptr;
+    used += doubles;
+    return p;
+  }
+};
+struct WrappedSolveScratch {
+  double *J, *Hd, *res;  // J [6n] | Hd [36] | per-start results [8 nstart], nstart = grid_n^2 + nextra
+  long total;
+  WrappedSolveScratch(double* buf, long n, long nstart) {
+    ScratchCarver c{buf, 0};
+    J = c.take(6 * n);
+    Hd = c.take(36);
+    res = c.take(8 * nstart);
+    total = c.used;
+  }
+};
+struct WrappedSearchScratch {
+  // J [6n] | Hd [36] | stage-1 terms T [3n] | base [6] | block results [4 nblk], one block per 256 stage-1 starts |
+  // stage-2 starts [6 nstart] | per-start results [8 nstart], nstart = nbest + nextra
+  double *J, *Hd, *T, *base, *blk, *starts, *res;
+  long nblk, total;
+  WrappedSearchScratch(double* buf, long n, long nstart1, long nstart) : nblk((nstart1 + 255) / 256) {
+    ScratchCarver c{buf, 0};
+    J = c.take(6 * n);
+    Hd = c.take(36);
+    T = c.take(3 * n);
+    base = c.take(6);
+    blk = c.take(4 * nblk);
+    starts = c.take(6 * nstart);
+    res = c.take(8 * nstart);
+    total = c.used;
+  }
+};
+hipError_t launch_wrapped_search(hipStream_t st, const WrapArgs& a, const double* base6, long gx, long gy, int nbest,
+                                 double* scratch, double* out);
+hipError_t launch_wrapped_solve(hipStream_t st, const WrapArgs& a, int gn, double* scratch, double* out);
 
 // Trajectory scans (rsl_traj.hip).
 hipError_t launch_traj_scan(hipStream_t st, const double* vel, int vstride, int nv, const double* om, int ostride,

@@ -20,6 +20,7 @@
 // Parity contract: cost <= the reference's DE cost (the argmin itself is not unique).
 #include "rsl_common.h"
 #include "rsl_internal.h"
+#include "rsl_phase_common.h"
 
 namespace rsl {
 
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(256) void k_associate(const double* __restrict__ cu
                                                    unsigned* __restrict__ used, int* __restrict__ match,
                                                    double* __restrict__ dist) {
   __shared__ double sd[256];
-  __shared__ int si[256];
+  __shared__ long si[256];
   const int t = threadIdx.x;
   for (int j = t; j < (np + 31) / 32; j += 256) used[j] = 0u;
   __syncthreads();
@@ -48,22 +49,9 @@ __global__ __launch_bounds__(256) void k_associate(const double* __restrict__ cu
         bj = j;
       }
     }
-    sd[t] = bd;
-    si[t] = bj;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-      if (t < off) {
-        const double od = sd[t + off];
-        const int oj = si[t + off];
-        if (oj >= 0 && (si[t] < 0 || od < sd[t] || (od == sd[t] && oj < si[t]))) {
-          sd[t] = od;
-          si[t] = oj;
-        }
-      }
-      __syncthreads();
-    }
+    block_argmin<256>(bd, bj, sd, si);
     if (t == 0) {
-      const int j = si[0];
+      const int j = (int)si[0];
       match[i] = j;
       dist[i] = j >= 0 ? sd[0] : INFINITY;
       if (j >= 0) used[j >> 5] |= 1u << (j & 31);
@@ -167,7 +155,9 @@ RSL_DEV void reg_grad_hess(const WrapProblem& P, const double* x, double* g, dou
   H[2][2] += 20.0 * P.w;
 }
 
-RSL_DEV double data_cost(const WrapProblem& P, const double* x, double* g /* nullable: -2k sum J r */) {
+// sum_i wrap(y_i - k J_i . x)^2; with GRAD also its gradient g[6] = -2k sum J r (g is not read otherwise).
+template <bool GRAD>
+RSL_DEV double data_cost(const WrapProblem& P, const double* x, double* g) {
   double c = 0.0;
   double gg[6] = {0, 0, 0, 0, 0, 0};
   for (long i = 0; i < P.n; ++i) {
@@ -177,14 +167,37 @@ RSL_DEV double data_cost(const WrapProblem& P, const double* x, double* g /* nul
     for (int a = 0; a < 6; ++a) pred += Ji[a] * x[a];
     const double r = wrap_pi(P.y[i] - P.k * pred);
     c += r * r;
-    if (g) {
+    if (GRAD) {
 #pragma unroll
       for (int a = 0; a < 6; ++a) gg[a] += Ji[a] * r;
     }
   }
-  if (g)
+  if (GRAD)
     for (int a = 0; a < 6; ++a) g[a] = -2.0 * P.k * gg[a];
   return c;
+}
+
+// One backtracking step of a projected descent over the first NX coordinates: x + step d clamped to the box, step
+// 1, 1/2, ... (six trials), and the first trial whose cost(xn) is below f replaces x and f.  True while the descent
+// should go on: a trial was taken and it gained more than 1e-13 (1 + f).
+template <int NX, class Cost>
+RSL_DEV bool backtrack(const WrapProblem& P, double* x, const double* d, double& f, Cost cost) {
+  double step = 1.0, fn = f, xn[NX];
+  bool ok = false;
+  for (int ls = 0; ls < 6; ++ls) {
+    for (int a = 0; a < NX; ++a) xn[a] = fmin(fmax(x[a] + step * d[a], P.lo[a]), P.hi[a]);
+    fn = cost(xn);
+    if (fn < f) {
+      ok = true;
+      break;
+    }
+    step *= 0.5;
+  }
+  if (!ok) return false;
+  const double df = f - fn;
+  for (int a = 0; a < NX; ++a) x[a] = xn[a];
+  f = fn;
+  return !(df <= 1e-13 * (1.0 + f));
 }
 
 // Solve H d = -g on the first nv coordinates (Cholesky with a tiny diagonal floor), d[nv..5] = 0.
@@ -236,8 +249,9 @@ __global__ __launch_bounds__(256) void k_wrapped_ms(WrapProblem P, const double*
     if (a >= P.nv) x[a] = 0.0;
     x[a] = fmin(fmax(x[a], P.lo[a]), P.hi[a]);
   }
-  double g[6], H[6][6], d[6], xn[6];
-  double f = data_cost(P, x, g) + reg_cost(P, x);
+  double g[6], H[6][6], d[6];
+  double f = data_cost<true>(P, x, g) + reg_cost(P, x);
+  const auto cost = [&](const double* xn) { return data_cost<false>(P, xn, nullptr) + reg_cost(P, xn); };
   for (int it = 0; it < iters; ++it) {
     double gr[6];
     reg_grad_hess(P, x, gr, H);
@@ -246,23 +260,8 @@ __global__ __launch_bounds__(256) void k_wrapped_ms(WrapProblem P, const double*
       for (int b = 0; b < 6; ++b) H[a][b] += Hd[a * 6 + b];
     }
     newton_step(H, g, P.nv, d);
-    double step = 1.0, fn = f;
-    bool ok = false;
-    for (int ls = 0; ls < 6; ++ls) {
-      for (int a = 0; a < 6; ++a) xn[a] = fmin(fmax(x[a] + step * d[a], P.lo[a]), P.hi[a]);
-      fn = data_cost(P, xn, nullptr) + reg_cost(P, xn);
-      if (fn < f) {
-        ok = true;
-        break;
-      }
-      step *= 0.5;
-    }
-    if (!ok) break;
-    const double df = f - fn;
-    for (int a = 0; a < 6; ++a) x[a] = xn[a];
-    f = fn;
-    if (df <= 1e-13 * (1.0 + f)) break;
-    data_cost(P, x, g);  // gradient at the new point
+    if (!backtrack<6>(P, x, d, f, cost)) break;
+    data_cost<true>(P, x, g);  // gradient at the new point
   }
   double* o = out + s * 8;
   for (int a = 0; a < 6; ++a) o[a] = x[a];
@@ -285,20 +284,7 @@ __global__ __launch_bounds__(1024) void k_wrapped_best(const double* __restrict_
       bi = s;
     }
   }
-  sc[t] = bc;
-  si[t] = bi;
-  __syncthreads();
-  for (int off = 512; off > 0; off >>= 1) {
-    if (t < off) {
-      const double oc = sc[t + off];
-      const long oi = si[t + off];
-      if (oi >= 0 && (si[t] < 0 || oc < sc[t] || (oc == sc[t] && oi < si[t]))) {
-        sc[t] = oc;
-        si[t] = oi;
-      }
-    }
-    __syncthreads();
-  }
+  block_argmin<1024>(bc, bi, sc, si);
   if (t == 0) {
     const long b = si[0];
     for (int a = 0; a < 8; ++a) best[a] = b >= 0 ? res[b * 8 + a] : 0.0;
@@ -333,22 +319,11 @@ __global__ __launch_bounds__(256) void k_wrapped_hess(const double* __restrict__
   }
 }
 
-// Jacobian rows J_i = [d_i, p_i x d_i], d = (cos el cos az, cos el sin az, sin el)  (velocity_solver.py:94-109).
+// Jacobian rows J [n][6] (jacobian_row).
 __global__ __launch_bounds__(256) void k_wrapped_jac(const double* __restrict__ pos, const double* __restrict__ ang,
                                                      long n, double* __restrict__ J) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const double az = ang[2 * i], el = ang[2 * i + 1];
-  const double ce = cos(el);
-  const double d0 = ce * cos(az), d1 = ce * sin(az), d2 = sin(el);
-  const double px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
-  double* o = J + 6 * i;
-  o[0] = d0;
-  o[1] = d1;
-  o[2] = d2;
-  o[3] = py * d2 - pz * d1;  // (w x p).d = w.(p x d)
-  o[4] = pz * d0 - px * d2;
-  o[5] = px * d1 - py * d0;
+  if (i < n) jacobian_row(pos + 3 * i, ang + 2 * i, J + 6 * i);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -389,27 +364,22 @@ struct Grid2 {
   double x0, y0, hx, hy;  // start (ix, iy) = (x0 + (ix + 0.5) hx, y0 + (iy + 0.5) hy)
 };
 
-RSL_DEV double data_cost2(const double* __restrict__ T, long n, double k, double vx, double vy, double* g) {
+// The data cost on the stage-1 terms T at (v_x, v_y) = (v[0], v[1]); with GRAD also its gradient g[2].
+template <bool GRAD>
+RSL_DEV double data_cost2(const double* __restrict__ T, long n, double k, const double* v, double* g) {
   double c = 0.0, g0 = 0.0, g1 = 0.0;
   for (long i = 0; i < n; ++i) {
     const double j0 = T[3 * i], j1 = T[3 * i + 1];
-    const double r = wrap_pi(T[3 * i + 2] - k * (j0 * vx + j1 * vy));
+    const double r = wrap_pi(T[3 * i + 2] - k * (j0 * v[0] + j1 * v[1]));
     c += r * r;
-    g0 += j0 * r;
-    g1 += j1 * r;
+    if (GRAD) {
+      g0 += j0 * r;
+      g1 += j1 * r;
+    }
   }
-  if (g) {
+  if (GRAD) {
     g[0] = -2.0 * k * g0;
     g[1] = -2.0 * k * g1;
-  }
-  return c;
-}
-
-RSL_DEV double data_cost2_f(const double* __restrict__ T, long n, double k, double vx, double vy) {
-  double c = 0.0;
-  for (long i = 0; i < n; ++i) {
-    const double r = wrap_pi(T[3 * i + 2] - k * (T[3 * i] * vx + T[3 * i + 1] * vy));
-    c += r * r;
   }
   return c;
 }
@@ -430,8 +400,12 @@ __global__ __launch_bounds__(256) void k_wrapped_grid2(WrapProblem P, const doub
     x[0] = fmin(fmax(Gd.x0 + ((double)ix + 0.5) * Gd.hx, P.lo[0]), P.hi[0]);
     x[1] = fmin(fmax(Gd.y0 + ((double)iy + 0.5) * Gd.hy, P.lo[1]), P.hi[1]);
     double g[2];
-    f = data_cost2(T, P.n, P.k, x[0], x[1], g) + reg_cost(P, x);
+    f = data_cost2<true>(T, P.n, P.k, x, g) + reg_cost(P, x);
     const double h00 = Hd[0], h01 = Hd[1], h11 = Hd[7];
+    const auto cost = [&](const double* xn) {  // at (xn[0], xn[1], x[2..5])
+      const double xt[6] = {xn[0], xn[1], x[2], x[3], x[4], x[5]};
+      return data_cost2<false>(T, P.n, P.k, xn, nullptr) + reg_cost(P, xt);
+    };
     for (int it = 0; it < iters; ++it) {
       double gr[6], H[6][6];
       reg_grad_hess(P, x, gr, H);
@@ -439,56 +413,20 @@ __global__ __launch_bounds__(256) void k_wrapped_grid2(WrapProblem P, const doub
       const double g0 = g[0] + gr[0], g1 = g[1] + gr[1];
       double det = a * c - b * b;
       if (!(det > 1e-300)) det = 1e-300;
-      const double d0 = -(c * g0 - b * g1) / det, d1 = -(a * g1 - b * g0) / det;
-      double step = 1.0, fn = f, xn0 = x[0], xn1 = x[1];
-      bool ok = false;
-      for (int ls = 0; ls < 6; ++ls) {
-        xn0 = fmin(fmax(x[0] + step * d0, P.lo[0]), P.hi[0]);
-        xn1 = fmin(fmax(x[1] + step * d1, P.lo[1]), P.hi[1]);
-        const double xs0 = x[0], xs1 = x[1];
-        x[0] = xn0;
-        x[1] = xn1;
-        fn = data_cost2_f(T, P.n, P.k, xn0, xn1) + reg_cost(P, x);
-        x[0] = xs0;
-        x[1] = xs1;
-        if (fn < f) {
-          ok = true;
-          break;
-        }
-        step *= 0.5;
-      }
-      if (!ok) break;
-      const double df = f - fn;
-      x[0] = xn0;
-      x[1] = xn1;
-      f = fn;
-      if (df <= 1e-13 * (1.0 + f)) break;
-      data_cost2(T, P.n, P.k, x[0], x[1], g);
+      const double d[2] = {-(c * g0 - b * g1) / det, -(a * g1 - b * g0) / det};
+      if (!backtrack<2>(P, x, d, f, cost)) break;
+      data_cost2<true>(T, P.n, P.k, x, g);
     }
   }
-  sc[t] = f;
   sx[t] = x[0];
   sy[t] = x[1];
-  si[t] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) {
-      const double oc = sc[t + off];
-      const long oi = si[t + off];
-      if (oc < sc[t] || (oc == sc[t] && oi < si[t])) {
-        sc[t] = oc;
-        sx[t] = sx[t + off];
-        sy[t] = sy[t + off];
-        si[t] = oi;
-      }
-    }
-    __syncthreads();
-  }
+  block_argmin<256>(f, s < nstart ? s : -1, sc, si);  // a start past the grid is no candidate; thread 0's is on it
   if (t == 0) {
+    const long win = si[0] - (long)blockIdx.x * 256;  // the winning thread
     double* o = blk + 4 * (long)blockIdx.x;
     o[0] = sc[0];
-    o[1] = sx[0];
-    o[2] = sy[0];
+    o[1] = sx[win];
+    o[2] = sy[win];
     o[3] = (double)si[0];
   }
 }
@@ -502,32 +440,18 @@ __global__ __launch_bounds__(1024) void k_wrapped_topk(double* __restrict__ blk,
   const int t = threadIdx.x;
   for (int q = 0; q < nbest; ++q) {
     double bc = INFINITY;
-    long bi = -1;
+    long bi = -1;  // the candidate's start index: the tie key, and 256 b + the winning thread of its block b
     for (long b = t; b < nblk; b += 1024) {
       const double c = blk[4 * b];
       const long idx = (long)blk[4 * b + 3];
-      if (c < bc || (c == bc && bi >= 0 && idx < (long)blk[4 * bi + 3])) {
+      if (c < bc || (c == bc && bi >= 0 && idx < bi)) {
         bc = c;
-        bi = b;
+        bi = idx;
       }
     }
-    sc[t] = bc;
-    si[t] = bi;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-      if (t < off) {
-        const double oc = sc[t + off];
-        const long ob = si[t + off];
-        if (ob >= 0 && (si[t] < 0 || oc < sc[t] ||
-                        (oc == sc[t] && (long)blk[4 * ob + 3] < (long)blk[4 * si[t] + 3]))) {
-          sc[t] = oc;
-          si[t] = ob;
-        }
-      }
-      __syncthreads();
-    }
+    block_argmin<1024>(bc, bi, sc, si);
     if (t == 0) {
-      const long b = si[0];
+      const long b = si[0] >= 0 ? si[0] / 256 : -1;
       double* o = starts + 6 * q;
       o[0] = b >= 0 ? blk[4 * b + 1] : base[0];
       o[1] = b >= 0 ? blk[4 * b + 2] : base[1];
@@ -538,97 +462,54 @@ __global__ __launch_bounds__(1024) void k_wrapped_topk(double* __restrict__ blk,
   }
 }
 
-// scratch doubles of launch_wrapped_search: J [6n] | Hd [36] | T [3n] | base [6] | block results [4 nblk] |
-// starts [6 (nbest + nextra)] | per-start results [8 (nbest + nextra)]
-long wrapped_search_scratch_doubles(long n, long nstart1, int nbest, int nextra) {
-  const long nblk = (nstart1 + 255) / 256;
-  return 6 * n + 36 + 3 * n + 6 + 4 * nblk + 14L * (nbest + nextra);
+// The problem of one call, with its Jacobian J [6n] and data Hessian Hd [36] launched into the scratch sections given.
+static WrapProblem wrap_problem(hipStream_t st, const WrapArgs& a, double* J, double* Hd) {
+  hipLaunchKernelGGL(k_wrapped_jac, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, st, a.pos, a.ang, a.n, J);
+  hipLaunchKernelGGL(k_wrapped_hess, dim3(1), dim3(256), 0, st, J, a.n, a.k, Hd);
+  WrapProblem P = {J, a.y, a.n, a.k, a.mode, a.w, a.vmax, a.wmax, a.prev, {}, {}, a.nv};
+  for (int c = 0; c < 6; ++c) {
+    P.lo[c] = a.lo[c];
+    P.hi[c] = a.hi[c];
+  }
+  return P;
 }
 
-hipError_t launch_wrapped_search(hipStream_t st, const double* pos, const double* ang, long n, const double* y,
-                                 double k, int mode, double w, double vmax, double wmax, const double* prev,
-                                 const double* lo, const double* hi, int nv, const double* base6, long gx, long gy,
-                                 int nbest, const double* extra, int nextra, int iters, double* scratch, double* out) {
-  double* J = scratch;
-  double* Hd = J + 6 * n;
-  double* T = Hd + 36;
-  double* base = T + 3 * n;
-  double* blk = base + 6;
-  const long nstart1 = gx * gy;
-  const long nblk = (nstart1 + 255) / 256;
-  double* starts = blk + 4 * nblk;
-  double* res = starts + 6L * (nbest + nextra);
+// The nv-D descent from nstart = gn^2 + nextra starts into res [8 nstart], and the best of them into out [8].
+static hipError_t wrapped_descend(hipStream_t st, const WrapProblem& P, const double* Hd, int gn, const double* extra,
+                                  long nextra, int iters, double* res, double* out) {
+  const long nstart = (long)gn * gn + nextra;
+  hipLaunchKernelGGL(k_wrapped_ms, dim3((unsigned)((nstart + 255) / 256)), dim3(256), 0, st, P, Hd, gn, extra,
+                     (int)nextra, iters, res);
+  hipLaunchKernelGGL(k_wrapped_best, dim3(1), dim3(1024), 0, st, res, nstart, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_wrapped_search(hipStream_t st, const WrapArgs& a, const double* base6, long gx, long gy, int nbest,
+                                 double* scratch, double* out) {
+  const long n = a.n, nstart = (long)nbest + a.nextra;
+  const WrappedSearchScratch S(scratch, n, gx * gy, nstart);
   Six b6;
-  for (int a = 0; a < 6; ++a) b6.v[a] = fmin(fmax(base6[a], lo[a]), hi[a]);
-  hipLaunchKernelGGL(k_fill6, dim3(1), dim3(64), 0, st, base, b6);  // by value: no pageable host copy
-  if (nextra > 0) {
-    const hipError_t e = hipMemcpyAsync(starts + 6L * nbest, extra, 6 * sizeof(double) * nextra, hipMemcpyDeviceToDevice, st);
+  for (int c = 0; c < 6; ++c) b6.v[c] = fmin(fmax(base6[c], a.lo[c]), a.hi[c]);
+  hipLaunchKernelGGL(k_fill6, dim3(1), dim3(64), 0, st, S.base, b6);  // by value: no pageable host copy
+  if (a.nextra > 0) {
+    const hipError_t e = hipMemcpyAsync(S.starts + 6L * nbest, a.extra, 6 * sizeof(double) * a.nextra,
+                                        hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k_wrapped_jac, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pos, ang, n, J);
-  hipLaunchKernelGGL(k_wrapped_hess, dim3(1), dim3(256), 0, st, J, n, k, Hd);
-  hipLaunchKernelGGL(k_wrapped_prep2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, J, y, n, k, base, T);
-  WrapProblem P;
-  P.J = J;
-  P.y = y;
-  P.n = n;
-  P.k = k;
-  P.mode = mode;
-  P.w = w;
-  P.vmax = vmax;
-  P.wmax = wmax;
-  P.prev = prev;
-  for (int a = 0; a < 6; ++a) {
-    P.lo[a] = lo[a];
-    P.hi[a] = hi[a];
-  }
-  P.nv = nv;
-  Grid2 Gd;
-  Gd.gx = gx;
-  Gd.gy = gy;
-  Gd.x0 = lo[0];
-  Gd.y0 = lo[1];
-  Gd.hx = (hi[0] - lo[0]) / (double)gx;
-  Gd.hy = (hi[1] - lo[1]) / (double)gy;
-  hipLaunchKernelGGL(k_wrapped_grid2, dim3((unsigned)nblk), dim3(256), 0, st, P, T, Hd, base, Gd, iters, blk);
-  hipLaunchKernelGGL(k_wrapped_topk, dim3(1), dim3(1024), 0, st, blk, nblk, nbest, base, starts);
-  const long nstart = (long)nbest + nextra;
-  hipLaunchKernelGGL(k_wrapped_ms, dim3((unsigned)((nstart + 255) / 256)), dim3(256), 0, st, P, Hd, 0, starts,
-                     (int)nstart, iters, res);
-  hipLaunchKernelGGL(k_wrapped_best, dim3(1), dim3(1024), 0, st, res, nstart, out);
-  return hipGetLastError();
+  const WrapProblem P = wrap_problem(st, a, S.J, S.Hd);
+  hipLaunchKernelGGL(k_wrapped_prep2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S.J, a.y, n, a.k, S.base,
+                     S.T);
+  const Grid2 Gd = {gx, gy, a.lo[0], a.lo[1], (a.hi[0] - a.lo[0]) / (double)gx, (a.hi[1] - a.lo[1]) / (double)gy};
+  hipLaunchKernelGGL(k_wrapped_grid2, dim3((unsigned)S.nblk), dim3(256), 0, st, P, S.T, S.Hd, S.base, Gd, a.iters,
+                     S.blk);
+  hipLaunchKernelGGL(k_wrapped_topk, dim3(1), dim3(1024), 0, st, S.blk, S.nblk, nbest, S.base, S.starts);
+  return wrapped_descend(st, P, S.Hd, 0, S.starts, nstart, a.iters, S.res, out);
 }
 
-hipError_t launch_wrapped_solve(hipStream_t st, const double* pos, const double* ang, long n, const double* y,
-                                double k, int mode, double w, double vmax, double wmax, const double* prev,
-                                const double* lo, const double* hi, int nv, int gn, const double* extra, int nextra,
-                                int iters, double* scratch, double* out) {
-  // scratch: J [6n] | Hd [36] | per-start results [8 * (gn^2 + nextra)]
-  double* J = scratch;
-  double* Hd = J + 6 * n;
-  double* res = Hd + 36;
-  hipLaunchKernelGGL(k_wrapped_jac, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pos, ang, n, J);
-  hipLaunchKernelGGL(k_wrapped_hess, dim3(1), dim3(256), 0, st, J, n, k, Hd);
-  WrapProblem P;
-  P.J = J;
-  P.y = y;
-  P.n = n;
-  P.k = k;
-  P.mode = mode;
-  P.w = w;
-  P.vmax = vmax;
-  P.wmax = wmax;
-  P.prev = prev;
-  for (int a = 0; a < 6; ++a) {
-    P.lo[a] = lo[a];
-    P.hi[a] = hi[a];
-  }
-  P.nv = nv;
-  const long nstart = (long)gn * gn + nextra;
-  hipLaunchKernelGGL(k_wrapped_ms, dim3((unsigned)((nstart + 255) / 256)), dim3(256), 0, st, P, Hd, gn, extra, nextra,
-                     iters, res);
-  hipLaunchKernelGGL(k_wrapped_best, dim3(1), dim3(1024), 0, st, res, nstart, out);
-  return hipGetLastError();
+hipError_t launch_wrapped_solve(hipStream_t st, const WrapArgs& a, int gn, double* scratch, double* out) {
+  const WrappedSolveScratch S(scratch, a.n, (long)gn * gn + a.nextra);
+  const WrapProblem P = wrap_problem(st, a, S.J, S.Hd);
+  return wrapped_descend(st, P, S.Hd, gn, a.extra, a.nextra, a.iters, S.res, out);
 }
 
 }  // namespace rsl

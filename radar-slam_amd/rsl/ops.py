@@ -8,12 +8,13 @@ then used in place without a copy.
 from __future__ import annotations
 
 import math
+from ctypes import c_double
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib, tables
-from .runtime import Context, emit_compact_supported, get_context, unpack_coord
+from .runtime import Context, _ptr, emit_compact_supported, get_context, unpack_coord
 
 
 def _ctx(ctx: Optional[Context]) -> Context:
@@ -55,11 +56,6 @@ def preprocess_rows(rows, table: np.ndarray, dc: bool, ctx: Optional[Context] = 
     c.check(c.lib.rsl_preprocess_rows(c.h, _ptr(d_in), d_in.shape[0], S, _ptr(d_tab), int(dc), _ptr(out)),
             'rsl_preprocess_rows')
     return to_host(out, np.complex128).reshape(shape)
-
-
-def _ptr(t):
-    from ctypes import c_void_p
-    return None if t is None else c_void_p(t.data_ptr())
 
 
 def range_doppler(frames, table: np.ndarray, *, chirp0=0, num_chirps=None, dc_removal=True,
@@ -339,13 +335,21 @@ def confidence(sigs, az_deg: Sequence[float], antenna_positions, lambda_c, ctx: 
     return to_host(conf[:N])
 
 
-def phase_model(pos, ang, x6, k, y=None, wrap=False, ridge=0.0, ctx: Optional[Context] = None):
-    c = _ctx(ctx)
+def _pos_ang(c: Context, pos, ang, pad=False):
+    """(n, device pos f64 [3 n], device ang f64 [2 n]) of n targets' host positions [n, 3] and angles [n, 2]; with pad
+    an empty set still gets valid pointers."""
     pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 3))
     ang = np.ascontiguousarray(np.asarray(ang, np.float64).reshape(-1, 2))
     n = pos.shape[0]
+    if pad and not n:
+        pos, ang = np.zeros(3), np.zeros(2)
+    return n, c.to_dev(pos.reshape(-1)), c.to_dev(ang.reshape(-1))
+
+
+def phase_model(pos, ang, x6, k, y=None, wrap=False, ridge=0.0, ctx: Optional[Context] = None):
+    c = _ctx(ctx)
+    n, dp, da = _pos_ang(c, pos, ang, pad=True)
     torch = c.torch
-    dp, da = c.to_dev(pos.reshape(-1) if n else np.zeros(3)), c.to_dev(ang.reshape(-1) if n else np.zeros(2))
     dx = c.to_dev(np.asarray(x6, np.float64).reshape(6))
     dy = c.to_dev(np.asarray(y, np.float64)) if y is not None and n else None
     pred = c.empty((max(n, 1),), torch.float64)
@@ -364,12 +368,10 @@ def phase_model(pos, ang, x6, k, y=None, wrap=False, ridge=0.0, ctx: Optional[Co
 def bvls(pos, ang, y, k, lo, hi, ridge=0.0, ctx: Optional[Context] = None):
     """Exact box-constrained linear LS of the 3- or 6-DoF phase model; returns (x, cost)."""
     c = _ctx(ctx)
-    pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 3))
-    ang = np.ascontiguousarray(np.asarray(ang, np.float64).reshape(-1, 2))
-    n = pos.shape[0]
+    n, dp, da = _pos_ang(c, pos, ang)
     nv = len(lo)
     torch = c.torch
-    dp, da, dy = c.to_dev(pos.reshape(-1)), c.to_dev(ang.reshape(-1)), c.to_dev(np.asarray(y, np.float64))
+    dy = c.to_dev(np.asarray(y, np.float64))
     dlo, dhi = c.to_dev(np.asarray(lo, np.float64)), c.to_dev(np.asarray(hi, np.float64))
     out = c.empty((nv + 1,), torch.float64)
     c._bind()
@@ -431,33 +433,38 @@ def associate(cur_xy, prev_xy, thr: float, ctx: Optional[Context] = None):
     return to_host(match).astype(np.int64), to_host(dist)
 
 
+def _wrapped_call(c: Context, name, pos, ang, y, k, mode, w, vmax, wmax, prev, lo, hi, nv, own, extra, iters,
+                  scratch_bytes):
+    """One call of rsl_wrapped_solve / rsl_wrapped_search (name) on host operands: own are the entry point's arguments
+    between nv and extra, scratch_bytes(n, lo6, hi6, nextra) its scratch size.  Returns (x6, cost)."""
+    torch = c.torch
+    n, dp, da = _pos_ang(c, pos, ang)
+    ex = None if extra is None else np.ascontiguousarray(np.asarray(extra, np.float64).reshape(-1, 6))
+    nextra = 0 if ex is None else ex.shape[0]
+    lo6 = (c_double * 6)(*[float(v) for v in lo])
+    hi6 = (c_double * 6)(*[float(v) for v in hi])
+    nbytes = int(scratch_bytes(n, lo6, hi6, nextra))
+    scratch = c.empty(((nbytes + 7) // 8,), torch.float64)
+    dy = c.to_dev(np.asarray(y, np.float64))
+    dprev = c.to_dev(np.asarray(prev, np.float64).reshape(6)) if prev is not None else None
+    dex = c.to_dev(ex.reshape(-1)) if nextra else None
+    out = c.empty((8,), torch.float64)
+    c._bind()
+    c.check(getattr(c.lib, name)(c.h, _ptr(dp), _ptr(da), n, _ptr(dy), float(k), int(mode), float(w), float(vmax),
+                                 float(wmax), _ptr(dprev), lo6, hi6, int(nv), *own, _ptr(dex), nextra, int(iters),
+                                 _ptr(scratch), nbytes, _ptr(out)), name)
+    o = to_host(out)
+    return o[:6].copy(), float(o[6])
+
+
 def wrapped_solve(pos, ang, y, k, *, mode: int, lo, hi, nv: int = 6, w: float = 0.01, vmax: float = 50.0,
                   wmax: float = 10.0, prev=None, extra=None, grid_n: int = 512, iters: int = 12,
                   ctx: Optional[Context] = None):
     """Global minimisation of the wrapped-phase cost (rsl_wrapped_solve): mode 0 = Improved regularisation,
     mode 1 = Advanced penalties.  Returns (x6, cost)."""
-    from ctypes import c_double
     c = _ctx(ctx)
-    torch = c.torch
-    pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 3))
-    ang = np.ascontiguousarray(np.asarray(ang, np.float64).reshape(-1, 2))
-    n = pos.shape[0]
-    ex = None if extra is None else np.ascontiguousarray(np.asarray(extra, np.float64).reshape(-1, 6))
-    nextra = 0 if ex is None else ex.shape[0]
-    nbytes = int(c.lib.rsl_wrapped_scratch_bytes(n, grid_n, nextra))
-    scratch = c.empty(((nbytes + 7) // 8,), torch.float64)
-    dp, da, dy = c.to_dev(pos.reshape(-1)), c.to_dev(ang.reshape(-1)), c.to_dev(np.asarray(y, np.float64))
-    dprev = c.to_dev(np.asarray(prev, np.float64).reshape(6)) if prev is not None else None
-    dex = c.to_dev(ex.reshape(-1)) if nextra else None
-    out = c.empty((8,), torch.float64)
-    lo6 = (c_double * 6)(*[float(v) for v in lo])
-    hi6 = (c_double * 6)(*[float(v) for v in hi])
-    c._bind()
-    c.check(c.lib.rsl_wrapped_solve(c.h, _ptr(dp), _ptr(da), n, _ptr(dy), float(k), int(mode), float(w), float(vmax),
-                                    float(wmax), _ptr(dprev), lo6, hi6, int(nv), int(grid_n), _ptr(dex), nextra,
-                                    int(iters), _ptr(scratch), nbytes, _ptr(out)), 'rsl_wrapped_solve')
-    o = to_host(out)
-    return o[:6].copy(), float(o[6])
+    return _wrapped_call(c, 'rsl_wrapped_solve', pos, ang, y, k, mode, w, vmax, wmax, prev, lo, hi, nv, (int(grid_n),),
+                         extra, iters, lambda n, lo6, hi6, nextra: c.lib.rsl_wrapped_scratch_bytes(n, grid_n, nextra))
 
 
 def wrapped_search(pos, ang, y, k, *, mode: int, lo, hi, nv: int = 6, w: float = 0.01, vmax: float = 50.0,
@@ -466,16 +473,7 @@ def wrapped_search(pos, ang, y, k, *, mode: int, lo, hi, nv: int = 6, w: float =
     """Basin-resolving global minimisation of the wrapped-phase cost (rsl_wrapped_search): 2-D Gauss-Newton in
     (v_x, v_y) from a grid whose spacing is spacing_frac of the wrap period 2 pi / k, then the nv-D refinement from the
     nbest best basins and the extra starts.  Returns (x6, cost)."""
-    from ctypes import c_double
     c = _ctx(ctx)
-    torch = c.torch
-    pos = np.ascontiguousarray(np.asarray(pos, np.float64).reshape(-1, 3))
-    ang = np.ascontiguousarray(np.asarray(ang, np.float64).reshape(-1, 2))
-    n = pos.shape[0]
-    ex = None if extra is None else np.ascontiguousarray(np.asarray(extra, np.float64).reshape(-1, 6))
-    nextra = 0 if ex is None else ex.shape[0]
-    lo6 = (c_double * 6)(*[float(v) for v in lo])
-    hi6 = (c_double * 6)(*[float(v) for v in hi])
     # x[2..5] during the 2-D stage: the regulariser's optimum for them (0; with a previous motion, Advanced's temporal
     # term w 0.1 |x - prev|^2 against 10 w v_z^2: v_z = prev_z / 101, w = prev_w)
     base = np.zeros(6)
@@ -490,17 +488,14 @@ def wrapped_search(pos, ang, y, k, *, mode: int, lo, hi, nv: int = 6, w: float =
     widths = [w for w in (float(hi[0]) - float(lo[0]), float(hi[1]) - float(lo[1])) if w > 1e-9]
     width = min(widths) if widths else 1e-9
     spacing = min(float(spacing_frac) * 2 * math.pi / abs(float(k)), width / 64)
-    nbytes = int(c.lib.rsl_wrapped_search_scratch_bytes(n, lo6, hi6, spacing, int(nbest), nextra))
-    if nbytes < 0:
-        raise ValueError('rsl_wrapped_search_scratch_bytes: bad arguments')
-    scratch = c.empty(((nbytes + 7) // 8,), torch.float64)
-    dp, da, dy = c.to_dev(pos.reshape(-1)), c.to_dev(ang.reshape(-1)), c.to_dev(np.asarray(y, np.float64))
-    dprev = c.to_dev(np.asarray(prev, np.float64).reshape(6)) if prev is not None else None
-    dex = c.to_dev(ex.reshape(-1)) if nextra else None
-    out = c.empty((8,), torch.float64)
-    c._bind()
-    c.check(c.lib.rsl_wrapped_search(c.h, _ptr(dp), _ptr(da), n, _ptr(dy), float(k), int(mode), float(w), float(vmax),
-                                     float(wmax), _ptr(dprev), lo6, hi6, int(nv), b6, spacing, int(nbest), _ptr(dex),
-                                     nextra, int(iters), _ptr(scratch), nbytes, _ptr(out)), 'rsl_wrapped_search')
-    o = to_host(out)
-    return o[:6].copy(), float(o[6])
+
+    def scratch_bytes(n, lo6, hi6, nextra):
+        nbytes = int(c.lib.rsl_wrapped_search_scratch_bytes(n, lo6, hi6, spacing, int(nbest), nextra))
+        if nbytes < 0:
+            raise ValueError('rsl_wrapped_search_scratch_bytes: bad arguments')
+        return nbytes
+
+    return _wrapped_call(c, 'rsl_wrapped_search', pos, ang, y, k, mode, w, vmax, wmax, prev, lo, hi, nv,
+                         (b6, spacing, int(nbest)), extra, iters, scratch_bytes)
+
+

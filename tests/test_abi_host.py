@@ -80,6 +80,44 @@ def test_fft_support_table_exhaustive():
         assert lib.rsl_fft_supported(n) == 0, n
 
 
+def test_wrapped_scratch_sizes():
+    """The ABI's scratch sizes of the two wrapped solvers, whatever lays the buffers out: rsl_wrapped_scratch_bytes =
+    8 (6 n + 36 + 8 (g^2 + e)); rsl_wrapped_search_scratch_bytes = 8 (9 n + 42 + 4 ceil(gx gy / 256) + 14 (nbest + e))
+    with ceil(width / spacing) points per axis clamped to [1, 32768]; -1 for arguments out of range."""
+    import math
+    import rsl
+    lib = rsl.load()
+    for n, g, e in ((0, 0, 0), (1, 0, 1), (4, 0, 3), (7, 1, 0), (20, 3, 2), (61, 64, 5), (1000, 512, 0)):
+        assert lib.rsl_wrapped_scratch_bytes(n, g, e) == 8 * (6 * n + 36 + 8 * (g * g + e)), (n, g, e)
+    for bad in ((-1, 4, 0), (4, -1, 0), (4, 4, -1)):
+        assert lib.rsl_wrapped_scratch_bytes(*bad) == -1, bad
+
+    six = ctypes.c_double * 6
+
+    def search_bytes(n, lo, hi, spacing, nbest, e):
+        return lib.rsl_wrapped_search_scratch_bytes(n, six(*lo, 0, 0, 0, 0), six(*hi, 0, 0, 0, 0), spacing, nbest, e)
+
+    def points(width, spacing):
+        return min(max(math.ceil(width / spacing), 1), 32768)
+
+    # the last boxes: a collapsed axis (lo == hi) gets one point; an axis of more than 32768 spacings is clamped
+    for n, lo, hi, spacing, nbest, e in ((0, (-1.0, -1.0), (1.0, 1.0), 0.5, 1, 0),
+                                         (4, (-2.0, -1.0), (2.0, 3.0), 0.25, 64, 2),
+                                         (7, (0.0, 0.0), (10.0, 0.3), 0.03, 3, 0),
+                                         (20, (-2.0, -2.0), (2.0, 2.0), 0.0097, 64, 5),
+                                         (61, (-1.0, 5.0), (1.0, 5.0), 0.125, 8, 1),
+                                         (5, (3.0, -4.0), (3.0, -4.0), 0.1, 2, 0),
+                                         (9, (-50.0, 0.0), (50.0, 0.001), 0.001, 1024, 0)):
+        gx, gy = points(hi[0] - lo[0], spacing), points(hi[1] - lo[1], spacing)
+        want = 8 * (9 * n + 42 + 4 * ((gx * gy + 255) // 256) + 14 * (nbest + e))
+        assert search_bytes(n, lo, hi, spacing, nbest, e) == want, (n, lo, hi, spacing, nbest, e, gx, gy)
+    box = ((-1.0, -1.0), (1.0, 1.0), 0.5)
+    for n, nbest, e in ((-1, 4, 0), (4, 0, 0), (4, 4, -1)):
+        assert search_bytes(n, *box, nbest, e) == -1, (n, nbest, e)
+    assert lib.rsl_wrapped_search_scratch_bytes(4, None, six(), 0.5, 4, 0) == -1
+    assert lib.rsl_wrapped_search_scratch_bytes(4, six(), None, 0.5, 4, 0) == -1
+
+
 def test_null_handle_errors():
     import rsl
     lib = rsl.load()

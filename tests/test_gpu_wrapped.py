@@ -64,6 +64,52 @@ def test_association_edge_cases(ctx):
     assert (m == mo).all() and np.allclose(d[m >= 0], do[mo >= 0], rtol=0, atol=1e-12)
 
 
+def test_association_tie_across_stripes(ctx):
+    """Two previous targets at exactly the same distance, at indices that different threads of the 256-thread scan
+    see (3 and 260 of 300): the lowest index wins across threads too, and the second current target, at the same
+    point, gets the other one."""
+    from rsl import ops
+    prev = np.stack([100.0 + np.arange(300), np.zeros(300)], axis=1)
+    prev[3], prev[260] = (1.0, 0.0), (-1.0, 0.0)
+    m, d = ops.associate(np.zeros((2, 2)), prev, 5.0, ctx=ctx)
+    assert m.tolist() == [3, 260] and d.tolist() == [1.0, 1.0]
+
+
+def _wrapped_solve_raw(ctx, pos, ang, y, extra=None, grid_n=0):
+    """rsl_wrapped_solve on the library itself (Improved cost, nv 3, box +-2 m/s, 12 iterations): all 8 output
+    doubles {x[6], cost, start index}."""
+    import ctypes
+    import torch
+    from rsl.runtime import _ptr
+    ex = np.zeros((0, 6)) if extra is None else np.asarray(extra, np.float64).reshape(-1, 6)
+    six = ctypes.c_double * 6
+    lo, hi = six(-2, -2, -2, -2, -2, -2), six(2, 2, 2, 2, 2, 2)
+    nbytes = ctx.lib.rsl_wrapped_scratch_bytes(len(y), grid_n, len(ex))
+    scratch = ctx.empty((nbytes // 8,), torch.float64)
+    dp, da, dy = (ctx.to_dev(np.ascontiguousarray(a, np.float64).reshape(-1)) for a in (pos, ang, y))
+    dex = ctx.to_dev(ex.reshape(-1)) if len(ex) else None
+    out = ctx.empty((8,), torch.float64)
+    ctx._bind()
+    ctx.check(ctx.lib.rsl_wrapped_solve(ctx.h, _ptr(dp), _ptr(da), len(y), _ptr(dy), K, 0, 0.01, 50.0, 10.0, None, lo,
+                                        hi, 3, grid_n, _ptr(dex), len(ex), 12, _ptr(scratch), nbytes, _ptr(out)),
+              'rsl_wrapped_solve')
+    return out.cpu().numpy()
+
+
+def test_wrapped_best_tie_rule(ctx, golden):
+    """The argmin over the starts takes the lowest cost and, among equal costs, the lowest start index: out[7] of
+    rsl_wrapped_solve with extra starts only.  Equal starts descend to equal costs bit for bit."""
+    pos, ang, y = (a[:4] for a in _geometry(golden('wrapped')))
+    good = _wrapped_solve_raw(ctx, pos, ang, y, grid_n=16)[:6]  # the best of a 16 x 16 grid's descents
+    bad = np.array([1.5, -1.5, 0.0, 0.0, 0.0, 0.0])
+    # the premise of the second case: the descent from bad ends above the one from good
+    assert _wrapped_solve_raw(ctx, pos, ang, y, [bad])[6] > _wrapped_solve_raw(ctx, pos, ang, y, [good])[6]
+    for starts, index in (([bad, bad, bad], 0), ([bad, good, good], 1)):
+        o = _wrapped_solve_raw(ctx, pos, ang, y, starts)
+        assert o[7] == index, (o[7], index)
+        assert abs(O.improved_cost(o[:6], pos, ang, y, K) - o[6]) <= TOL * o[6]
+
+
 def test_improved_solver_beats_reference_de(ctx, golden):
     from src.algorithms.velocity_solver_improved import ImprovedVelocitySolver
     z = golden('wrapped')
