@@ -373,6 +373,45 @@ int rsl_velocity_robust(rsl_handle h, const void* az, const void* gidx, const vo
                         double ridge, const double* bounds4, int loss, double c, double scale, int iters,
                         double tol, void* out, void* weight, void* resid);
 
+/* Consensus (RANSAC) ego-velocity solve (k_velocity_consensus): for frames where the static world is not the majority
+ *     of the cells.  Both solvers above start from the LS fit and need that majority; this one proposes two-cell
+ *     hypotheses, keeps the one the most cells agree with and refits on those cells, so it finds the largest coherent
+ *     population even where that is a minority.  Model and inputs are exactly those of rsl_velocity_robust (az / gidx +
+ *     az_table, y, amask, seg clamped to n, k, ridge, bounds4).  Per frame f with the cells b .. e, n_f = e - b: the
+ *     directions (c_i, s_i), the multiplicity m_i = popcount(amask[i]) (1 when amask is null), the residual
+ *     r_i(x) = y_i - k (x_0 c_i + x_1 s_i), the cut-off t = c scale.  scale > 0 is required: it is the sensor's
+ *     phase-noise sigma (radians).  The Python layers default c to 3.0.
+ *     Hypotheses h = 0 .. hyps - 1: (x0, x1, ., .) = Philox-4x32-10 with the counter (h, low32(frame0 + f),
+ *     high32(frame0 + f), 0) and the key (low32(seed), high32(seed)) (the generator of rsl_synth_cube);
+ *     i = (x0 n_f) >> 32; j = (x1 (n_f - 1)) >> 32, then j += (j >= i): two distinct local indices into the segment.
+ *     det = c_i s_j - c_j s_i; v_x = (y_i s_j - y_j s_i) / (k det); v_y = (c_i y_j - c_j y_i) / (k det).  The
+ *     hypothesis is valid iff n_f >= 2, m_i > 0 and m_j > 0, |det| >= min_det (the least |sin| of the pair's azimuth
+ *     difference; the Python default 0.1 lies between 5.5 and 6 degrees, so no pair of the 0.5 degree grid sits on it)
+ *     and (v_x, v_y) lies inside the box, edges included.
+ *     Score: score(h) = sum of m_i over the cells with |r_i(x_h)| <= t, an exact integer.  The winner is the valid
+ *     hypothesis with the largest score, ties going to the lowest h.  If no hypothesis is valid, the start is
+ *     rsl_velocity's solution of the frame (same moments, ridge, box and rule) and best_h = -1.  An empty frame, or one with sum m_i = 0, has no valid
+ *     hypothesis and keeps that LS start untouched, as rsl_velocity_robust does.
+ *     Refinement, repeated `refine` times: w_i = m_i where |r_i(x)| <= t, else 0; if sum w_i = 0, stop and keep x;
+ *     otherwise x = the box-constrained ridge LS with the weights w_i, by the 2x2 rule of the other two solvers (the
+ *     interior solution if feasible, else the best edge).
+ *     out f64 [F, 8] = {v_x, v_y, cost, rmse_in, n_in, n, best_h, n_valid}, all at the returned x:
+ *     cost = sum m_i min(r_i^2, t^2) + ridge |v|^2; n_in = sum of m_i over the cells with |r_i| <= t (the inliers);
+ *     rmse_in = sqrt(sum over the inliers of m_i r_i^2 / n_in) (0 when n_in = 0); n = sum m_i; best_h = the winning
+ *     hypothesis or -1; n_valid = the number of valid hypotheses.  weight f32 [N] (nullable): 1 where |r_i| <= t, else
+ *     0: the inlier mask, i.e. the static / moving labelling of the cells.  resid f64 [N] (nullable).
+ *     Rows [a, b) of a batch equal a launch of those frames alone with frame0 = a: the draws depend on
+ *     (seed, frame0 + f, h) only.
+ *     F = 0 launches nothing.  RSL_ERR_INVALID: c <= 0 or not finite; scale <= 0 or not finite; hyps outside
+ *     1 .. RSL_CONSENSUS_MAX_H; min_det outside (0, 1]; refine outside 0 .. 100; frame0 < 0; ridge < 0; gidx with
+ *     G > 2048 or without az_table; az and gidx both null; null y, seg, out or bounds4.  Timed under RSL_K_VELOCITY. */
+#define RSL_CONSENSUS_MAX_H 4096
+int rsl_velocity_consensus(rsl_handle h, const void* az, const void* gidx, const void* az_table, int G,
+                           const void* y, const void* amask, const void* seg, long long n, int F, double k,
+                           double ridge, const double* bounds4, double c, double scale, int hyps, double min_det,
+                           int refine, unsigned long long seed, long long frame0,
+                           void* out, void* weight, void* resid);
+
 /* a3-a6  SignalPreprocessor.dechirp_signal / apply_window / remove_dc / process_chirp (dechirp.py:85-166):
  *     out[r, s] = in[r, s] * table[s], then (dc != 0) minus the row's complex mean.  in/out c64 [rows, S]. */
 int rsl_preprocess_rows(rsl_handle h, const void* in, long long rows, int S, const void* table, int dc, void* out);

@@ -665,6 +665,38 @@ int rsl_velocity_robust(rsl_handle h, const void* az, const void* gidx, const vo
                    "velocity_robust");
 }
 
+int rsl_velocity_consensus(rsl_handle h, const void* az, const void* gidx, const void* az_table, int G, const void* y,
+                           const void* amask, const void* seg, long long n, int F, double k, double ridge,
+                           const double* bounds4, double c, double scale, int hyps, double min_det, int refine,
+                           unsigned long long seed, long long frame0, void* out, void* weight, void* resid) {
+  if (!h) return RSL_ERR_INVALID;
+  if (F < 0 || n < 0) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: bad argument");
+  if (!(c > 0) || !std::isfinite(c)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: c must be finite, > 0");
+  if (!(scale > 0) || !std::isfinite(scale))
+    return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: scale must be finite, > 0");
+  if (hyps < 1 || hyps > RSL_CONSENSUS_MAX_H)
+    return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: hyps outside 1..RSL_CONSENSUS_MAX_H");
+  if (!(min_det > 0) || !(min_det <= 1)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: min_det outside (0, 1]");
+  if (refine < 0 || refine > 100) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: refine outside 0..100");
+  if (frame0 < 0) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: frame0 must be >= 0");
+  if (!(ridge >= 0)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: ridge must be >= 0");
+  if (F == 0) return RSL_OK;
+  if ((!az && !gidx) || !y || !seg || !bounds4 || !out)
+    return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: null pointer");
+  if (gidx && (!az_table || G <= 0 || G > 2048))
+    return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: bad grid table");
+  if (!(bounds4[0] <= bounds4[1]) || !(bounds4[2] <= bounds4[3]))
+    return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: bad bounds");
+  Scope sc(h, RSL_K_VELOCITY);
+  return hip_check(h,
+                   rsl::launch_velocity_consensus(h->stream, (const double*)az, (const int*)gidx,
+                                                  (const double*)az_table, G, (const double*)y, (const unsigned*)amask,
+                                                  (const long long*)seg, n, F, k, ridge, bounds4, c, scale, hyps,
+                                                  min_det, refine, seed, frame0, (double*)out, (float*)weight,
+                                                  (double*)resid),
+                   "velocity_consensus");
+}
+
 int rsl_preprocess_rows(rsl_handle h, const void* in, long long rows, int S, const void* table, int dc, void* out) {
   if (!h) return RSL_ERR_INVALID;
   if (rows < 0 || S <= 0 || !in || !table || !out) return fail(h, RSL_ERR_INVALID, "rsl_preprocess_rows: bad argument");

@@ -144,6 +144,12 @@ hipError_t launch_velocity_robust(hipStream_t st, const double* az, const int* g
                                   const double* y, const unsigned* amask, const long long* seg, long long n, int F,
                                   double k, double ridge, const double* bounds4, int loss, double c, double scale,
                                   int iters, double tol, double* out, float* weight, double* resid);
+// K8c: consensus (RANSAC) velocity solve (rsl_vel_consensus.hip); the contract is rsl_velocity_consensus's in rsl.h.
+hipError_t launch_velocity_consensus(hipStream_t st, const double* az, const int* gidx, const double* az_table, int G,
+                                     const double* y, const unsigned* amask, const long long* seg, long long n, int F,
+                                     double k, double ridge, const double* bounds4, double c, double scale, int hyps,
+                                     double min_det, int refine, unsigned long long seed, long long frame0, double* out,
+                                     float* weight, double* resid);
 
 // K9: greedy association and wrapped-phase multi-start solve (rsl_wrap.hip).
 // configs[3] pattern (rsl_scene.hip): per-cube top-k peak selection and the analyser's nearest association.

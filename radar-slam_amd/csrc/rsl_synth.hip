@@ -17,6 +17,7 @@
 // bitwise, the reference's (numpy's legacy Mersenne-Twister stream cannot be split across lanes).
 #include "rsl_common.h"
 #include "rsl_internal.h"
+#include "rsl_philox.h"
 
 namespace rsl {
 
@@ -60,19 +61,6 @@ __global__ __launch_bounds__(256) void k_synth_pattern(const double* __restrict_
     acc_i += aph_r * bb_i + aph_i * bb_r;
   }
   pattern[idx] = make_double2(acc_r, acc_i);
-}
-
-// Philox-4x32-10 (Salmon et al., SC'11): counter ctr, key (k0, k1).
-RSL_DEV uint4 philox4x32_10(uint4 ctr, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * ctr.x;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * ctr.z;
-    ctr = make_uint4((unsigned)(p1 >> 32) ^ ctr.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ ctr.w ^ k1, (unsigned)p0);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return ctr;
 }
 
 // uint32 -> (0, 1]: (x + 1) 2^-32 (never 0, so log() is finite)

@@ -1,6 +1,7 @@
 // rsl_vel_common.h — what the velocity solvers share (k_velocity in rsl_vel.hip, k_velocity_robust in
-// rsl_vel_robust.hip): the cell loader, the workgroup sums, the quadratic cost and the 2x2 box solve.  The robust
-// solver starts from k_velocity's solution; both take it from these functions, in the same order of operations.
+// rsl_vel_robust.hip, k_velocity_consensus in rsl_vel_consensus.hip): the cell loader, the workgroup sums, the
+// quadratic cost and the 2x2 box solve.  The robust solver starts from k_velocity's solution, and the consensus solver
+// falls back on it; all take it from these functions, in the same order of operations.
 #pragma once
 #include "rsl_common.h"
 
@@ -100,6 +101,64 @@ RSL_DEV double2 box_solve(const double* m, double k, double ridge, double lx, do
     }
   }
   return make_double2(bx, by);
+}
+
+// -- what the iterating solvers share (k_velocity_robust, k_velocity_consensus): one workgroup of kThreads per frame ----
+
+// fn(i, ok, m, c, s, y) for the cells of [b, e) owned by this thread; gidx path: cells past e come as ok = false with
+// m = 0, y = 0 (they add 0 to every sum, as in k_velocity).
+template <int kThreads, class Fn>
+RSL_DEV void rv_cells(const double* __restrict__ az, const int* __restrict__ gidx, const double* __restrict__ y,
+                      const unsigned* __restrict__ amask, const double* cs_tab, int G, long long b, long long e,
+                      Fn&& fn) {
+  if (gidx) {
+    const long long step = (long long)kThreads * kVelU;
+    for (long long i0 = b + threadIdx.x; i0 < e; i0 += step) {
+      int gv[kVelU];
+      double yv[kVelU];
+      unsigned mv[kVelU];
+      vel_load(i0, e, kThreads, gidx, y, amask, gv, yv, mv);
+#pragma unroll
+      for (int u = 0; u < kVelU; ++u) {
+        const long long i = i0 + (long long)u * kThreads;
+        fn(i, i < e, __popc(mv[u]), cs_tab[gv[u]], cs_tab[G + gv[u]], yv[u]);
+      }
+    }
+  } else {
+    for (long long i = b + threadIdx.x; i < e; i += kThreads) {
+      double s, c;
+      sincos(az[i], &s, &c);
+      fn(i, true, amask ? __popc(amask[i]) : 1, c, s, y[i]);
+    }
+  }
+}
+
+// The residual, with explicit fma: every pass (select, score, moments, output) must see the same bits for a cell.
+RSL_DEV double rv_resid(double yi, double k, double vx, double vy, double c, double s) {
+  return fma(-k, fma(vx, c, vy * s), yi);
+}
+
+// Sums of 7 values over the workgroup into mom[0..6], in block_sum's order (wave shuffle tree, then the waves in order
+// on thread 0) with all 7 in one pass: 2 barriers instead of 21.  red: [kThreads / 64 * 7] doubles of LDS.  Valid for
+// every thread on return.  Kept beside block_sum7 (8 doubles of LDS, k_velocity's): with 7 x block_sum here the Huber
+// solve at a fixed scale took 2.376 instead of 2.210 ms per 2000 cfg2 frames.
+template <int kThreads>
+RSL_DEV void rv_reduce7(double (&v)[7], double* red, double* mom) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < 7; ++q)
+    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
+  if ((t & 63) == 0)
+#pragma unroll
+    for (int q = 0; q < 7; ++q) red[(t >> 6) * 7 + q] = v[q];
+  __syncthreads();
+  if (t == 0)
+    for (int q = 0; q < 7; ++q) {
+      double r = 0.0;
+      for (int w = 0; w < kThreads / 64; ++w) r += red[w * 7 + q];
+      mom[q] = r;
+    }
+  __syncthreads();
 }
 
 }  // namespace rsl

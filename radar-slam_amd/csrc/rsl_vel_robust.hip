@@ -13,7 +13,7 @@
 // re-reads its own lines, so all passes after the first are served by L2 / Infinity Cache.
 //
 // The start comes from k_velocity's own source: the cell loader and the 2x2 box solve are the functions k_velocity
-// calls (rsl_vel_common.h), and rv_reduce7 below adds in block_sum's order.  Same source, not guaranteed the same bits:
+// calls, and rv_reduce7 adds in block_sum's order (rsl_vel_common.h).  Same source, not guaranteed the same bits:
 // under fp-contract the compiler chooses per kernel which products it fuses into an fma, so the two starts may differ
 // in the last place (tests/test_gpu_vel_robust.py::test_ls_equivalence holds them within 1e-13).
 #include "rsl_common.h"
@@ -39,39 +39,6 @@ constexpr int kRvWtot = kRvSel + 2;          // [kRvWaves] wave totals of the hi
 constexpr int kRvHist = kRvWtot + kRvWaves;  // [kRvBins]
 constexpr int kRvLds = kRvHist + kRvBins;
 
-// fn(i, ok, m, c, s, y) for the cells of [b, e) owned by this thread; gidx path: cells past e come as ok = false with
-// m = 0, y = 0 (they add 0 to every sum, as in k_velocity).
-template <class Fn>
-RSL_DEV void rv_cells(const double* __restrict__ az, const int* __restrict__ gidx, const double* __restrict__ y,
-                      const unsigned* __restrict__ amask, const double* cs_tab, int G, long long b, long long e,
-                      Fn&& fn) {
-  if (gidx) {
-    const long long step = (long long)kRvThreads * kVelU;
-    for (long long i0 = b + threadIdx.x; i0 < e; i0 += step) {
-      int gv[kVelU];
-      double yv[kVelU];
-      unsigned mv[kVelU];
-      vel_load(i0, e, kRvThreads, gidx, y, amask, gv, yv, mv);
-#pragma unroll
-      for (int u = 0; u < kVelU; ++u) {
-        const long long i = i0 + (long long)u * kRvThreads;
-        fn(i, i < e, __popc(mv[u]), cs_tab[gv[u]], cs_tab[G + gv[u]], yv[u]);
-      }
-    }
-  } else {
-    for (long long i = b + threadIdx.x; i < e; i += kRvThreads) {
-      double s, c;
-      sincos(az[i], &s, &c);
-      fn(i, true, amask ? __popc(amask[i]) : 1, c, s, y[i]);
-    }
-  }
-}
-
-// The residual, with explicit fma: every pass (select, moments, output) must see the same bits for a cell.
-RSL_DEV double rv_resid(double yi, double k, double vx, double vy, double c, double s) {
-  return fma(-k, fma(vx, c, vy * s), yi);
-}
-
 // u(a), a = |r|, cut-off t = c sigma.  t = 0 (sigma = 0): 1 where the fit is exact, else 0, for both losses.
 RSL_DEV double rv_weight(int loss, double a, double t) {
   if (loss == RSL_LOSS_HUBER) return a <= t ? 1.0 : t / a;
@@ -89,28 +56,6 @@ RSL_DEV double rv_rho(int loss, double a, double t) {
     return (t * t / 3.0) * (1.0 - w * w * w);
   }
   return t * t / 3.0;
-}
-
-// Sums of 7 values over the workgroup into mom[0..6], in block_sum's order (wave shuffle tree, then the waves in order
-// on thread 0) with all 7 in one pass: 2 barriers instead of 21.  Valid for every thread on return.  Kept beside
-// block_sum7 (8 doubles of LDS, k_velocity's): with 7 x block_sum here the Huber solve at a fixed scale took 2.376
-// instead of 2.210 ms per 2000 cfg2 frames.
-RSL_DEV void rv_reduce7(double (&v)[7], double* red, double* mom) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < 7; ++q)
-    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
-  if ((t & 63) == 0)
-#pragma unroll
-    for (int q = 0; q < 7; ++q) red[(t >> 6) * 7 + q] = v[q];
-  __syncthreads();
-  if (t == 0)
-    for (int q = 0; q < 7; ++q) {
-      double r = 0.0;
-      for (int w = 0; w < kRvWaves; ++w) r += red[w * 7 + q];
-      mom[q] = r;
-    }
-  __syncthreads();
 }
 
 }  // namespace
@@ -141,7 +86,8 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
   // x0: the plain LS solve of k_velocity
   {
     double v[7] = {0, 0, 0, 0, 0, 0, 0};
-    rv_cells(az, gidx, y, amask, cs_tab, G, b, e, [&](long long, bool, int m, double c, double s, double yi) {
+    rv_cells<kRvThreads>(az, gidx, y, amask, cs_tab, G, b, e,
+                         [&](long long, bool, int m, double c, double s, double yi) {
       const double w = (double)m;
       v[0] += w;
       v[1] += w * c * c;
@@ -151,7 +97,7 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
       v[5] += w * s * yi;
       v[6] += w * yi * yi;
     });
-    rv_reduce7(v, red, mom);
+    rv_reduce7<kRvThreads>(v, red, mom);
   }
   const double W = mom[0];  // sum of the multiplicities: an exact integer
   auto solve = [&]() {  // thread 0: the box solve on the moments, broadcast through bc
@@ -181,7 +127,8 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
           sel[1] = rank;
         }
         __syncthreads();
-        rv_cells(az, gidx, y, amask, cs_tab, G, b, e, [&](long long, bool ok, int m, double c, double s, double yi) {
+        rv_cells<kRvThreads>(az, gidx, y, amask, cs_tab, G, b, e,
+                             [&](long long, bool ok, int m, double c, double s, double yi) {
           if (!ok || m == 0) return;
           const unsigned key = __float_as_uint((float)fabs(rv_resid(yi, k, vx, vy, c, s)));
           if (pass == 0 || (key >> (shift + bits)) == prefix)
@@ -232,7 +179,8 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
     }
     const double tc = c_tune * sigma;
     double v[7] = {0, 0, 0, 0, 0, 0, 0};
-    rv_cells(az, gidx, y, amask, cs_tab, G, b, e, [&](long long, bool, int m, double c, double s, double yi) {
+    rv_cells<kRvThreads>(az, gidx, y, amask, cs_tab, G, b, e,
+                         [&](long long, bool, int m, double c, double s, double yi) {
       const double w = m == 0 ? 0.0 : (double)m * rv_weight(loss, fabs(rv_resid(yi, k, vx, vy, c, s)), tc);
       v[0] += w;
       v[1] += w * c * c;
@@ -242,7 +190,7 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
       v[5] += w * s * yi;
       v[6] += w * yi * yi;
     });
-    rv_reduce7(v, red, mom);
+    rv_reduce7<kRvThreads>(v, red, mom);
     if (!(mom[0] != 0.0)) {  // every weight is 0: keep x
       conv = true;
       break;
@@ -262,7 +210,8 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
   // output pass at the returned x, with the last sigma
   const double tc = c_tune * sigma;
   double v[7] = {0, 0, 0, 0, 0, 0, 0};
-  rv_cells(az, gidx, y, amask, cs_tab, G, b, e, [&](long long i, bool ok, int m, double c, double s, double yi) {
+  rv_cells<kRvThreads>(az, gidx, y, amask, cs_tab, G, b, e,
+                       [&](long long i, bool ok, int m, double c, double s, double yi) {
     if (!ok) return;
     const double r = rv_resid(yi, k, vx, vy, c, s), a = fabs(r);
     const double u = rv_weight(loss, a, tc);
@@ -275,7 +224,7 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
     v[2] += w * u;
     if (loss == RSL_LOSS_HUBER ? a <= tc : (a < tc || (tc == 0.0 && a == 0.0))) v[3] += w;
   });
-  rv_reduce7(v, red, mom);
+  rv_reduce7<kRvThreads>(v, red, mom);
   if (t == 0) {
     double* o = out + f * 8;
     o[0] = vx;

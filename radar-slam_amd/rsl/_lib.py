@@ -25,6 +25,8 @@ SS_MAX_L = 8  # RSL_SS_MAX_L: the longest sub-array of rsl_doa_smoothed
 LOSS_HUBER, LOSS_TUKEY = 1, 2
 LOSS_IDS = {'huber': LOSS_HUBER, 'tukey': LOSS_TUKEY}
 LOSS_DEFAULT_C = {LOSS_HUBER: 1.345, LOSS_TUKEY: 4.685}  # 95 % efficiency at the normal distribution
+CONSENSUS_MAX_H = 4096  # RSL_CONSENSUS_MAX_H: the most hypotheses of rsl_velocity_consensus
+CONSENSUS_DEFAULT_C = 3.0  # cut-off of the consensus solver in units of the phase-noise sigma
 K_NAMES = ['range_fft', 'doppler_fft', 'detect', 'offsets', 'emit', 'doa_scan', 'cell_extras', 'confidence',
            'velocity', 'aux']
 
@@ -71,6 +73,9 @@ SIGNATURES = {
                              POINTER(c_double), _P, _P, _P]),
     'rsl_velocity_robust': (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_longlong, c_int, c_double, c_double,
                                     POINTER(c_double), c_int, c_double, c_double, c_int, c_double, _P, _P, _P]),
+    'rsl_velocity_consensus': (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_longlong, c_int, c_double, c_double,
+                                       POINTER(c_double), c_double, c_double, c_int, c_double, c_int, c_ulonglong,
+                                       c_longlong, _P, _P, _P]),
     'rsl_preprocess_rows': (c_int, [_P, _P, c_longlong, c_int, _P, c_int, _P]),
     'rsl_phase_model': (c_int, [_P, _P, _P, c_longlong, _P, c_double, _P, c_int, c_double, _P, _P, _P]),
     'rsl_associate': (c_int, [_P, _P, c_int, _P, c_int, c_double, _P, _P, _P]),

@@ -71,13 +71,19 @@ class ChainConfig:
                                                # is the rate per cell (alpha designed for a sum of num_antennas looks)
                                                # and threshold_db applies to the summed power
     velocity_loss: str = 'ls'                  # 'ls': rsl_velocity (plain box-constrained LS); 'huber' | 'tukey':
-                                               # rsl_velocity_robust (IRLS from the LS start, include/rsl.h)
+                                               # rsl_velocity_robust (IRLS from the LS start, include/rsl.h);
+                                               # 'consensus': rsl_velocity_consensus (two-cell hypotheses, for frames
+                                               # where the static cells are not the majority; needs velocity_scale)
     velocity_scale: Optional[float] = None     # residual scale sigma (the sensor's phase-noise sigma, radians); None:
                                                # estimated per iteration from the residuals' weighted median, which
                                                # is dependable only below roughly 30 % coherent outliers
-    velocity_c: Optional[float] = None         # tuning constant; None: 1.345 (huber) / 4.685 (tukey)
+    velocity_c: Optional[float] = None         # tuning constant; None: 1.345 (huber) / 4.685 (tukey) / 3.0 (consensus)
     velocity_iters: int = 30
     velocity_tol: float = 1e-9
+    velocity_hyps: int = 256                   # 'consensus': hypotheses per frame, 1 .. _lib.CONSENSUS_MAX_H
+    velocity_min_det: float = 0.1              # 'consensus': the least |sin| of a pair's azimuth difference, (0, 1]
+    velocity_refine: int = 3                   # 'consensus': LS passes on the winner's inliers, 0 .. 100
+    velocity_seed: int = 0                     # 'consensus': key of the hypothesis draws
     multi_source: bool = False                 # also run the spatially smoothed MUSIC (rsl_doa_smoothed) on every
                                                # cell: up to ss_max angles per cell in results()['ss_*']; gidx, esprit,
                                                # phase and the velocity solve keep using the one-angle scan
@@ -106,8 +112,18 @@ class ChainConfig:
                 raise ValueError(f'ss_len {L} exceeds the {A} antennas')
             if int(self.ss_sources) > min(int(self.ss_max), L - 1):
                 raise ValueError(f'ss_sources {self.ss_sources} exceeds the {L - 1} angles a sub-array of {L} resolves')
-        if self.velocity_loss not in ('ls', 'huber', 'tukey'):
-            raise ValueError(f"velocity_loss must be 'ls', 'huber' or 'tukey', not {self.velocity_loss!r}")
+        if self.velocity_loss not in ('ls', 'huber', 'tukey', 'consensus'):
+            raise ValueError("velocity_loss must be 'ls', 'huber', 'tukey' or 'consensus', "
+                             f'not {self.velocity_loss!r}')
+        if self.velocity_loss == 'consensus':
+            if self.velocity_scale is None or not float(self.velocity_scale) > 0.0:
+                raise ValueError("velocity_loss='consensus' needs velocity_scale > 0, the phase-noise sigma in radians")
+            if not 1 <= int(self.velocity_hyps) <= _lib.CONSENSUS_MAX_H:
+                raise ValueError(f'velocity_hyps must lie in [1, {_lib.CONSENSUS_MAX_H}], not {self.velocity_hyps!r}')
+            if not 0.0 < float(self.velocity_min_det) <= 1.0:
+                raise ValueError(f'velocity_min_det must lie in (0, 1], not {self.velocity_min_det!r}')
+            if not 0 <= int(self.velocity_refine) <= 100:
+                raise ValueError(f'velocity_refine must lie in [0, 100], not {self.velocity_refine!r}')
         if self.detector not in ('threshold', 'cfar'):
             raise ValueError(f"detector must be 'threshold' or 'cfar', not {self.detector!r}")
         if self.detect_on not in ('antenna', 'sum'):
@@ -201,7 +217,8 @@ class RadarChain:
         self.gidx = e((cc,), torch.int32)
         self.ext = dict(esprit=e((cc,), torch.float64), phase=e((cc,), torch.float64), az=e((cc,), torch.float64))
         self.vel = vel_out if vel_out is not None else e((F, 8), torch.float64)
-        self.vel_weight = e((cc,), torch.float32) if cfg.velocity_loss != 'ls' else None  # IRLS weight of every cell
+        # IRLS weight of every cell ('consensus': the inlier mask)
+        self.vel_weight = e((cc,), torch.float32) if cfg.velocity_loss != 'ls' else None
         self.ncell_dev = self.offs['cell_base'][F:F + 1]
         self.ss = None
         if cfg.multi_source:  # smoothed MUSIC: its own outputs on the same cell lists
@@ -316,7 +333,14 @@ class RadarChain:
         if self.ss is not None:
             ctx.doa_smoothed(self.rds, L['c_frame'], L['c_rc'], self.ss_steer, n=self.cell_cap, n_dev=self.ncell_dev,
                              nmax=self.ss_nmax, num_sources=cfg.ss_sources, rel=cfg.ss_rel, out=self.ss)
-        if velocity and cfg.velocity_loss != 'ls':
+        if velocity and cfg.velocity_loss == 'consensus':
+            # vel columns 2-7 become {cost, rmse_in, n_in, n, best_h, n_valid} (include/rsl.h)
+            ctx.velocity_consensus(None, self.ext['phase'], self.offs['cell_base'], k=self.k, scale=cfg.velocity_scale,
+                                   c=cfg.velocity_c, hyps=cfg.velocity_hyps, min_det=cfg.velocity_min_det,
+                                   refine=cfg.velocity_refine, seed=cfg.velocity_seed, frame0=0, ridge=cfg.ridge,
+                                   bounds=cfg.bounds, amask=L['c_amask'], out=self.vel, gidx=self.gidx,
+                                   az_table=self.az_table, n=self.cell_cap, want_weight=self.vel_weight)
+        elif velocity and cfg.velocity_loss != 'ls':
             # vel columns 2-7 become {cost, rmse_w, n_in, n, sigma, it} (include/rsl.h)
             ctx.velocity_robust(None, self.ext['phase'], self.offs['cell_base'], k=self.k, loss=cfg.velocity_loss,
                                 c=cfg.velocity_c, scale=cfg.velocity_scale, iters=cfg.velocity_iters,

@@ -411,6 +411,37 @@ def solve_velocity_robust(az, y, *, k, loss='tukey', c=None, scale=None, iters=3
                 weights=to_host(w, np.float64)[:n], residuals=to_host(r)[:n])
 
 
+def solve_velocity_consensus(az, y, *, k, scale, c=None, hyps=256, min_det=0.1, refine=3, seed=0, ridge=0.0,
+                             bounds=(-50.0, 50.0, -50.0, 50.0), amask=None, ctx: Optional[Context] = None):
+    """Consensus (RANSAC) solve of one host segment (rsl_velocity_consensus, one frame, frame0 = 0): az radians [N], y
+    observed phase [N], amask optional antenna masks (multiplicity = popcount), scale the sensor's phase-noise sigma in
+    radians (required; the cut-off is c * scale, c=None: 3.0).  Finds the largest coherent population even where it is
+    a minority of the cells.  Returns the out row by name (velocity [2], cost, rmse_in, num_inliers, num_targets,
+    best_hypothesis, num_valid) plus weights (the inlier mask) and residuals [N]."""
+    cx = _ctx(ctx)
+    az = np.ascontiguousarray(np.asarray(az, np.float64).reshape(-1))
+    yy = np.ascontiguousarray(np.asarray(y, np.float64).reshape(-1))
+    if az.shape != yy.shape:
+        raise ValueError(f'az and y must have the same length, not {az.shape[0]} and {yy.shape[0]}')
+    n = yy.shape[0]
+    pad = lambda a: a if n else np.zeros(1, a.dtype)  # an empty segment still needs a valid pointer
+    d_az, d_y = cx.to_dev(pad(az)), cx.to_dev(pad(yy))
+    d_m = None
+    if amask is not None:
+        am = np.asarray(amask).astype(np.int64).reshape(-1)
+        if am.shape[0] != n:
+            raise ValueError('amask must have the length of y')
+        d_m = cx.to_dev(pad((am & 0xffffffff).astype(np.uint32).view(np.int32)))
+    seg = cx.to_dev(np.array([0, n], np.int64))
+    out, w, r = cx.velocity_consensus(d_az, d_y, seg, k=k, scale=scale, c=c, hyps=hyps, min_det=min_det, refine=refine,
+                                      seed=seed, ridge=ridge, bounds=bounds, amask=d_m, n=n, want_weight=True,
+                                      want_resid=True)
+    o = to_host(out)[0]
+    return dict(velocity=o[:2].copy(), cost=float(o[2]), rmse_in=float(o[3]), num_inliers=int(o[4]),
+                num_targets=int(o[5]), best_hypothesis=int(o[6]), num_valid=int(o[7]),
+                weights=to_host(w, np.float64)[:n], residuals=to_host(r)[:n])
+
+
 # -- a30 / a31: cross-frame association and wrapped-phase solve ------------------------------------------
 def associate(cur_xy, prev_xy, thr: float, ctx: Optional[Context] = None):
     """Greedy nearest-unused association (velocity_solver_improved.py:74-129) on the device.

@@ -542,6 +542,45 @@ class Context:
                    'rsl_velocity_robust')
         return o, weight, resid
 
+    def velocity_consensus(self, az, y, seg, *, k: float, scale: float, c: Optional[float] = None, hyps: int = 256,
+                           min_det: float = 0.1, refine: int = 3, seed: int = 0, frame0: int = 0, ridge: float = 0.0,
+                           bounds=(-50.0, 50.0, -50.0, 50.0), amask=None, gidx=None, az_table=None, n=None, out=None,
+                           want_weight=False, want_resid=False):
+        """Consensus (RANSAC) velocity solve (rsl_velocity_consensus; the estimator is specified in include/rsl.h): for
+        frames where the static cells are not the majority.  scale: the sensor's phase-noise sigma in radians
+        (required); c=None: 3.0, the cut-off is c * scale; hyps two-cell hypotheses per frame, drawn from
+        (seed, frame0 + f, h); min_det: the least |sin| of a pair's azimuth difference; refine: LS passes on the
+        winner's inliers.  want_weight: True, or a device f32 [N] buffer to fill with the inlier mask.  Returns
+        (out f64 [F, 8] = {v_x, v_y, cost, rmse_in, n_in, n, best_h, n_valid}, weight f32 [N] or None, resid f64 [N]
+        or None)."""
+        torch = self.torch
+        if scale is None:
+            raise ValueError('velocity_consensus needs scale, the phase-noise sigma in radians')
+        if c is None:
+            c = _lib.CONSENSUS_DEFAULT_C
+        F = int(seg.shape[0]) - 1
+        o = out if out is not None else self.empty((max(F, 1), 8), torch.float64)
+        N = int(y.shape[0]) if n is None else min(int(n), int(y.shape[0]))
+        G = int(az_table.shape[0]) if az_table is not None else 0
+        if want_weight is True:
+            weight = self.empty((max(N, 1),), torch.float32)
+        else:
+            weight = None if want_weight is False or want_weight is None else want_weight
+        resid = self.empty((max(N, 1),), torch.float64) if want_resid else None
+        b4 = (c_double * 4)(*[float(x) for x in bounds])
+        seed, frame0 = int(seed), int(frame0)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f'seed must lie in [0, 2^64), not {seed!r}')
+        if not -2 ** 63 <= frame0 < 2 ** 63:
+            raise ValueError(f'frame0 must fit 64 bits, not {frame0!r}')
+        self._bind()
+        self.check(self.lib.rsl_velocity_consensus(self.h, _ptr(az), _ptr(gidx), _ptr(az_table), G, _ptr(y),
+                                                   _ptr(amask), _ptr(seg), N, F, float(k), float(ridge), b4, float(c),
+                                                   float(scale), int(hyps), float(min_det), int(refine), seed, frame0,
+                                                   _ptr(o), _ptr(weight), _ptr(resid)),
+                   'rsl_velocity_consensus')
+        return o, weight, resid
+
 
 _ctx_lock = threading.Lock()
 _ctx: Dict[int, Context] = {}

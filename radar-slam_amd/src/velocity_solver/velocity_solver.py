@@ -147,6 +147,30 @@ class VelocitySolver:
                 'num_targets': N, 'weights': r['weights'], 'num_inliers': r['num_inliers'], 'scale': r['scale'],
                 'iterations': r['iterations']}
 
+    def solve_velocity_consensus(self, rds_data: np.ndarray, target_info: List[Dict], dt: float = 0.1, *,
+                                 scale: float, c: Optional[float] = None, hyps: int = 256, min_det: float = 0.1,
+                                 refine: int = 3, seed: int = 0) -> Dict:
+        """Consensus (RANSAC) variant of solve_velocity (not in the reference) for scenes where the static targets are
+        not the majority: two-target hypotheses, the one most targets agree with, refitted on those targets
+        (``rsl_velocity_consensus``, specified in include/rsl.h).  ``scale`` is the sensor's phase-noise sigma in
+        radians; targets within ``c * scale`` (``c=None``: 3.0) of the motion are its inliers.  Returns the
+        solve_velocity keys it can fill plus ``weights`` (the inlier mask: 1 = static), ``num_inliers``,
+        ``best_hypothesis`` and ``num_valid``."""
+        N = len(target_info)
+        if N < 3:
+            logger.warning("Insufficient targets for optimization")
+            return {'success': False, 'message': 'Insufficient targets'}
+        az = np.array([t['azimuth_rad'] for t in target_info], dtype=np.float64)
+        obs = self.compute_observed_phase_differences(rds_data, target_info)
+        r = ops.solve_velocity_consensus(az, obs, k=self._k(dt), scale=scale, c=c, hyps=hyps, min_det=min_det,
+                                         refine=refine, seed=seed,
+                                         bounds=(_TRANS_BOUNDS[0][0], _TRANS_BOUNDS[0][1], _TRANS_BOUNDS[1][0],
+                                                 _TRANS_BOUNDS[1][1]))
+        return {'success': True, 'velocity': np.array([r['velocity'][0], r['velocity'][1], 0.0]),
+                'angular_velocity': np.zeros(3), 'cost': r['cost'], 'rmse': r['rmse_in'], 'residuals': r['residuals'],
+                'num_targets': N, 'weights': r['weights'], 'num_inliers': r['num_inliers'],
+                'best_hypothesis': r['best_hypothesis'], 'num_valid': r['num_valid']}
+
     def visualize_results(self, results: Dict, save_path: Optional[str] = None) -> None:
         if not results['success']:
             logger.warning("Cannot visualize failed optimization")
