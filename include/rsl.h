@@ -425,7 +425,9 @@ int rsl_phase_model(rsl_handle h, const void* pos, const void* ang, long long n,
 
 /* a28  two_step_optimization (velocity_solver.py:178-307) for arbitrary (pos, ang): exact box-constrained
  *     linear least squares over nv = 3 (v, w = 0) or 6 (v, w) unknowns (BVLS active set, fp64).
- *     lo/hi f64 [nv] device bounds; out f64 [nv + 1] = x, cost. */
+ *     lo/hi f64 [nv] device bounds; out f64 [nv + 1] = x, cost.  The cost is the per-target sum of squares
+ *     sum_i (y_i - k J_i.x)^2 + ridge |x|^2 evaluated at the returned x (the reference's result.fun), never negative;
+ *     it is not formed from the normal-equation moments, which cancel at a near-exact fit. */
 int rsl_bvls(rsl_handle h, const void* pos, const void* ang, long long n, const void* y, double k, int nv,
              double ridge, const void* lo, const void* hi, void* out);
 
@@ -452,7 +454,8 @@ int rsl_peak_topk(rsl_handle h, const void* entry_base, long long entry_cap, int
  *     [off[f], off[f+1]) of the concatenated f64 arrays range_m, az_rad and s0 (c128: the first component of each
  *     target's spatial signature); off i64 [nframes + 1] on the device.  For target i of frame f > 0: the target j of
  *     frame f-1 with the smallest sqrt((r_i - r_j)^2 + (az_i - az_j)^2), strict '<' against the running minimum and
- *     against thr (first minimum wins; previous targets may be matched many times), in exact float64.  Outputs
+ *     against thr (first minimum wins; previous targets may be matched many times), in float64 with each difference,
+ *     product, sum and the square root rounded to nearest on its own (no fused multiply-add).  Outputs
  *     [off[nframes]]: match i32 (index within frame f-1, -1 = none; always -1 in frame 0), dist f64, phase f64 =
  *     angle(s0_i * conj(s0_j)) (:296; 0 where unmatched). */
 int rsl_associate_nearest(rsl_handle h, const void* range_m, const void* az_rad, const void* s0, const void* off,

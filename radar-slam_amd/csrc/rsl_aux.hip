@@ -144,29 +144,11 @@ RSL_DEV void reduce(const double (&v)[N], double (*red)[N], double* m) {
     for (int c = 0; c < N; ++c) m[c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
 }
 
-// One block: normal equations of min |y - k J x|^2 + ridge |x|^2 over nv (3 or 6) unknowns, then BVLS.
-// out f64 [nv + 1] = x, cost.
-__global__ __launch_bounds__(256) void k_bvls(const double* __restrict__ pos, const double* __restrict__ ang, long n,
-                                              const double* __restrict__ y, double k, int nv, double ridge,
-                                              const double* __restrict__ lo, const double* __restrict__ hi,
-                                              double* __restrict__ out) {
-  __shared__ double red[4][28];
-  double acc[28];
-  for (int c = 0; c < 28; ++c) acc[c] = 0.0;
-  for (long i = threadIdx.x; i < n; i += 256) {
-    double J[6];
-    jacobian_row(pos + 3 * i, ang + 2 * i, J);
-    for (int c = 0; c < 6; ++c) J[c] *= k;
-    int t = 0;
-    for (int a = 0; a < 6; ++a)
-      for (int b = a; b < 6; ++b) acc[t++] += J[a] * J[b];  // 21
-    for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * y[i];  // 6
-    acc[27] += y[i] * y[i];
-  }
-  double m[28];
-  reduce<28>(acc, red, m);
-  if (threadIdx.x != 0) return;
-  double H[6][6], b[6], yy;
+// BVLS on the reduced moments m (21 of the upper triangle of J'J, then 6 of J'y; J scaled by k) over the first nv
+// unknowns; one thread.  xout [nv].
+RSL_DEV void bvls_solve(const double* m, int nv, double ridge, const double* __restrict__ lo,
+                        const double* __restrict__ hi, double* xout) {
+  double H[6][6], b[6];
   {
     int t = 0;
     for (int a = 0; a < 6; ++a)
@@ -177,7 +159,6 @@ __global__ __launch_bounds__(256) void k_bvls(const double* __restrict__ pos, co
       b[a] = m[21 + a];
       H[a][a] += ridge;
     }
-    yy = m[27];
   }
   // BVLS (Stark & Parker): state 0 free, -1 at lower, +1 at upper.  Start with all at bound nearest 0
   // (0 itself when inside the box: treat as free start).
@@ -241,13 +222,53 @@ __global__ __launch_bounds__(256) void k_bvls(const double* __restrict__ pos, co
     if (rel < 0) break;
     state[rel] = 0;
   }
-  double xHx = 0.0, bx = 0.0;
-  for (int a = 0; a < nv; ++a) {
-    bx += b[a] * x[a];
-    for (int c = 0; c < nv; ++c) xHx += x[a] * H[a][c] * x[c];
+  for (int a = 0; a < nv; ++a) xout[a] = x[a];
+}
+
+// One block: normal equations of min |y - k J x|^2 + ridge |x|^2 over nv (3 or 6) unknowns, then BVLS on thread 0, then
+// the cost at the solution as a per-target sum of squares over the workgroup.
+// out f64 [nv + 1] = x, cost.
+__global__ __launch_bounds__(256) void k_bvls(const double* __restrict__ pos, const double* __restrict__ ang, long n,
+                                              const double* __restrict__ y, double k, int nv, double ridge,
+                                              const double* __restrict__ lo, const double* __restrict__ hi,
+                                              double* __restrict__ out) {
+  __shared__ double red[4][27];
+  __shared__ double xs[6], sh[4];
+  double acc[27];
+  for (int c = 0; c < 27; ++c) acc[c] = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) {
+    double J[6];
+    jacobian_row(pos + 3 * i, ang + 2 * i, J);
+    for (int c = 0; c < 6; ++c) J[c] *= k;
+    int t = 0;
+    for (int a = 0; a < 6; ++a)
+      for (int b = a; b < 6; ++b) acc[t++] += J[a] * J[b];  // 21
+    for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * y[i];  // 6
   }
-  for (int a = 0; a < nv; ++a) out[a] = x[a];
-  out[nv] = yy - 2.0 * bx + xHx;  // includes ridge |x|^2 via H's diagonal
+  double m[27];
+  reduce<27>(acc, red, m);
+  if (threadIdx.x == 0) bvls_solve(m, nv, ridge, lo, hi, xs);
+  __syncthreads();
+  // The cost as the reference's sum of squares (step1_result.fun), in k_phase_model's operation order.  The moment form
+  // y'y - 2 b.x + x'Hx cancels at a near-exact fit: its error is ~1e-15 y'y whatever the residual (-3e-8 ... +6e-8 was
+  // returned at exact fits of 3 to 300 targets, where the sum of squares is ~1e-23).
+  double q = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) {
+    double J[6];
+    jacobian_row(pos + 3 * i, ang + 2 * i, J);
+    double p = 0.0;
+    for (int c = 0; c < nv; ++c) p += J[c] * xs[c];
+    const double r = y[i] - p * k;
+    q += r * r;
+  }
+  const double sum = block_sum(q, sh, 4);
+  if (threadIdx.x != 0) return;
+  double reg = 0.0;
+  for (int a = 0; a < nv; ++a) {
+    out[a] = xs[a];
+    reg += xs[a] * xs[a];
+  }
+  out[nv] = sum + ridge * reg;
 }
 
 hipError_t launch_bvls(hipStream_t st, const double* pos, const double* ang, long n, const double* y, double k, int nv,

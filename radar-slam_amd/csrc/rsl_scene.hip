@@ -22,9 +22,10 @@ namespace rsl {
 constexpr int kTopkThreads = 256;
 constexpr int kTopkMax = 256;  // max_targets supported by the in-LDS sort
 
-// Orderable key of an f32: larger float <=> larger unsigned key (NaN never occurs: dB of a finite power)
+// Orderable key of an f32: larger float <=> larger unsigned key, -0 and +0 the same key as they compare equal (NaN
+// never reaches here: it fails the threshold test)
 RSL_DEV unsigned f32_key(float v) {
-  const unsigned u = __float_as_uint(v);
+  const unsigned u = v == 0.f ? 0u : __float_as_uint(v);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -180,9 +181,24 @@ hipError_t launch_topk_entries(hipStream_t st, const long long* entry_base, long
   return hipGetLastError();
 }
 
+// a * b + c * d and a * b - c * d with each product and the sum rounded on its own, as numpy evaluates them.  The pragma
+// is what keeps the compiler from fusing them: HIP's __dmul_rn / __dadd_rn are plain operators that it contracts into
+// an FMA like any others.
+RSL_DEV double mul_add_rn(double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+  const double ab = a * b, cd = c * d;
+  return ab + cd;
+}
+RSL_DEV double mul_sub_rn(double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+  const double ab = a * b, cd = c * d;
+  return ab - cd;
+}
+
 // One thread per current target i of frame f (targets of frame f are [off[f], off[f + 1]) in the concatenated
-// arrays; the previous frame's are [off[f - 1], off[f]); frame 0 has no previous frame).  Exact float64 arithmetic in
-// the reference's operation order (no FMA contraction): range_diff**2 + azimuth_diff**2, sqrt, strict '<'.
+// arrays; the previous frame's are [off[f - 1], off[f]); frame 0 has no previous frame).  float64 arithmetic in the
+// reference's operation order with every operation rounded on its own (mul_add_rn): range_diff**2 + azimuth_diff**2,
+// sqrt, strict '<'.
 __global__ __launch_bounds__(256) void k_associate_nearest(const double* __restrict__ range_m,
                                                            const double* __restrict__ az_rad,
                                                            const double2* __restrict__ s0, const long long* __restrict__ off,
@@ -204,8 +220,8 @@ __global__ __launch_bounds__(256) void k_associate_nearest(const double* __restr
   if (f > 0) {
     const double r = range_m[i], a = az_rad[i];
     for (long long j = off[f - 1]; j < off[f]; ++j) {
-      const double dr = __dsub_rn(r, range_m[j]), da = __dsub_rn(a, az_rad[j]);
-      const double d = __dsqrt_rn(__dadd_rn(__dmul_rn(dr, dr), __dmul_rn(da, da)));
+      const double dr = r - range_m[j], da = a - az_rad[j];
+      const double d = sqrt(mul_add_rn(dr, dr, da, da));
       if (d < bd && d < thr) {
         bd = d;
         bj = (int)(j - off[f - 1]);
@@ -217,8 +233,8 @@ __global__ __launch_bounds__(256) void k_associate_nearest(const double* __restr
   if (bj >= 0) {
     // angle(c * conj(p)) of the two targets' first signature components (radarscenes_complete_analysis.py:296)
     const double2 c = s0[i], p = s0[off[f - 1] + bj];
-    const double re = __dadd_rn(__dmul_rn(c.x, p.x), __dmul_rn(c.y, p.y));
-    const double im = __dsub_rn(__dmul_rn(c.y, p.x), __dmul_rn(c.x, p.y));
+    const double re = mul_add_rn(c.x, p.x, c.y, p.y);
+    const double im = mul_sub_rn(c.y, p.x, c.x, p.y);
     phase[i] = atan2(im, re);
   } else {
     phase[i] = 0.0;
