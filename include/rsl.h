@@ -468,7 +468,13 @@ int rsl_associate_nearest(rsl_handle h, const void* range_m, const void* az_rad,
  *             velocity vmax, max angular velocity wmax and previous motion prev f64 [6] (device, nullable).
  *     nv = 3 (w fixed at 0; step 1) or 6.  Multi-start projected Gauss-Newton from a grid_n x grid_n grid
  *     over (v_x, v_y) plus nextra extra starts extra f64 [nextra][6] (device), iters iterations each;
- *     out f64 [8] (device) = {x[6], cost, start index}.  scratch >= rsl_wrapped_scratch_bytes(n, grid_n, nextra). */
+ *     out f64 [8] (device) = {x[6], cost, start index}.  scratch >= rsl_wrapped_scratch_bytes(n, grid_n, nextra).
+ *     "Projected": every start is clipped to the box, and each iteration solves the Newton system on the free
+ *     coordinates only.  A coordinate is held while it sits exactly on a bound and the total gradient points out of
+ *     the box there; the others take the step of the reduced Hessian, and the trial points x + step d (step 1, 1/2,
+ *     ..., 1/32, the first that lowers the cost) are clipped to the box.  A converged descent so ends at the minimiser
+ *     over the box of the quadratic piece it is in (a KKT point), not at the clipped unconstrained minimiser; with
+ *     no bound active the step is the plain Newton step. */
 long long rsl_wrapped_scratch_bytes(long long n, int grid_n, int nextra);
 
 int rsl_wrapped_solve(rsl_handle h, const void* pos, const void* ang, long long n, const void* y, double k, int mode,

@@ -17,6 +17,11 @@
 // runs DE over the box and reports whichever basin DE settles in.  Here every thread runs a projected
 // Gauss-Newton descent (the data Hessian 2 k^2 sum J J^T is constant, precomputed) from one start of a dense
 // (v_x, v_y) grid over the box, with backtracking on the true cost, and a reduction keeps the lowest cost.
+// "Projected" means: each iteration solves the Newton system on the free coordinates only -- a coordinate is held
+// while it sits exactly on a bound and the total gradient points out of the box there; the others get the step of the
+// reduced Hessian -- and the trial points x + step d are clamped to the box.  The descent so ends at the minimiser
+// over the box of the piece it is in (a KKT point), not at the clamped unconstrained minimiser, which differs from it
+// whenever a bound is active and the Hessian is not diagonal.  With no bound active the step is the plain one.
 // Parity contract: cost <= the reference's DE cost (the argmin itself is not unique).
 #include "rsl_common.h"
 #include "rsl_internal.h"
@@ -200,13 +205,29 @@ RSL_DEV bool backtrack(const WrapProblem& P, double* x, const double* d, double&
   return !(df <= 1e-13 * (1.0 + f));
 }
 
-// Solve H d = -g on the first nv coordinates (Cholesky with a tiny diagonal floor), d[nv..5] = 0.
-RSL_DEV void newton_step(const double (*H)[6], const double* g, int nv, double* d) {
+// The free set of a projected step over the first nx coordinates, bit a per coordinate: a coordinate is held (its bit
+// clear) while it sits on a bound of the box and the total gradient g points out of the box there, so that the
+// descent direction would only be clamped back.  A held coordinate is released as soon as its gradient turns inward.
+RSL_DEV unsigned free_set(const WrapProblem& P, const double* x, const double* g, int nx) {
+  unsigned fr = 0u;
+  for (int a = 0; a < nx; ++a) {
+    const bool held = (x[a] <= P.lo[a] && g[a] > 0.0) || (x[a] >= P.hi[a] && g[a] < 0.0);
+    if (!held) fr |= 1u << a;
+  }
+  return fr;
+}
+
+// Solve H d = -g on the free coordinates among the first nv (fr: free_set; Cholesky of the reduced Hessian with a tiny
+// diagonal floor), d = 0 on the held ones and on [nv..5].  A held coordinate's row and column of L stay 0, so with
+// every coordinate free the operations are those of the plain nv x nv solve, in its order.
+RSL_DEV void newton_step(const double (*H)[6], const double* g, int nv, unsigned fr, double* d) {
   double L[6][6];
   for (int a = 0; a < 6; ++a)
     for (int b = 0; b < 6; ++b) L[a][b] = 0.0;
   for (int a = 0; a < nv; ++a) {
+    if (!((fr >> a) & 1u)) continue;
     for (int b = 0; b <= a; ++b) {
+      if (!((fr >> b) & 1u)) continue;
       double s = H[a][b];
       for (int q = 0; q < b; ++q) s -= L[a][q] * L[b][q];
       if (a == b) {
@@ -218,11 +239,15 @@ RSL_DEV void newton_step(const double (*H)[6], const double* g, int nv, double* 
   }
   double z[6];
   for (int a = 0; a < nv; ++a) {
+    z[a] = 0.0;
+    if (!((fr >> a) & 1u)) continue;
     double s = -g[a];
     for (int q = 0; q < a; ++q) s -= L[a][q] * z[q];
     z[a] = s / L[a][a];
   }
   for (int a = nv - 1; a >= 0; --a) {
+    d[a] = 0.0;
+    if (!((fr >> a) & 1u)) continue;
     double s = z[a];
     for (int q = a + 1; q < nv; ++q) s -= L[q][a] * d[q];
     d[a] = s / L[a][a];
@@ -259,7 +284,7 @@ __global__ __launch_bounds__(256) void k_wrapped_ms(WrapProblem P, const double*
       g[a] += gr[a];
       for (int b = 0; b < 6; ++b) H[a][b] += Hd[a * 6 + b];
     }
-    newton_step(H, g, P.nv, d);
+    newton_step(H, g, P.nv, free_set(P, x, g, P.nv), d);
     if (!backtrack<6>(P, x, d, f, cost)) break;
     data_cost<true>(P, x, g);  // gradient at the new point
   }
@@ -410,10 +435,20 @@ __global__ __launch_bounds__(256) void k_wrapped_grid2(WrapProblem P, const doub
       double gr[6], H[6][6];
       reg_grad_hess(P, x, gr, H);
       const double a = h00 + H[0][0], b = h01 + H[0][1], c = h11 + H[1][1];
-      const double g0 = g[0] + gr[0], g1 = g[1] + gr[1];
-      double det = a * c - b * b;
-      if (!(det > 1e-300)) det = 1e-300;
-      const double d[2] = {-(c * g0 - b * g1) / det, -(a * g1 - b * g0) / det};
+      const double gt[2] = {g[0] + gr[0], g[1] + gr[1]};
+      const double g0 = gt[0], g1 = gt[1];
+      const unsigned fr = free_set(P, x, gt, 2);
+      double d[2] = {0.0, 0.0};
+      if (fr == 3u) {
+        double det = a * c - b * b;
+        if (!(det > 1e-300)) det = 1e-300;
+        d[0] = -(c * g0 - b * g1) / det;
+        d[1] = -(a * g1 - b * g0) / det;
+      } else if (fr == 1u) {  // x1 held: the reduced Hessian is a
+        d[0] = -g0 / (a > 1e-300 ? a : 1e-300);
+      } else if (fr == 2u) {  // x0 held
+        d[1] = -g1 / (c > 1e-300 ? c : 1e-300);
+      }
       if (!backtrack<2>(P, x, d, f, cost)) break;
       data_cost2<true>(T, P.n, P.k, x, g);
     }
