@@ -300,6 +300,41 @@ int rsl_doa_smoothed(rsl_handle h, const void* rds, int A, int S, int C, const v
                      int num_sources, double rel, void* out_nsrc, void* out_idx, void* out_den, void* out_eig,
                      void* out_spec);
 
+/* Range-azimuth maps: the multi-snapshot spatial covariance of every range bin and the Bartlett / Capon (MVDR) power
+ *     over an azimuth grid computed from it (rsl_ramap.hip; the reference project has no counterpart, this comment is
+ *     the specification).  The Doppler bins of one range row are the snapshots: reflectors that share a range bin but
+ *     differ in radial velocity are incoherent across them, so Capon separates them below the beamwidth with the full
+ *     aperture.  Both functions are timed under RSL_K_DOA_SCAN.
+ *
+ *     rsl_range_cov: rds c64 [F, A, S, C], 2 <= A <= RSL_RA_MAX_A, Doppler window 0 <= c0 < c1 <= C, Cw = c1 - c0.
+ *       cov[f, r, p, q] = (1/Cw) sum_{c0 <= c < c1} rds[f, p, r, c] conj(rds[f, q, r, c]),  cov c64 [F, S, A, A],
+ *     accumulated in fp32 on the matrix pipe (a k-ordered fmaf chain of the real Gram matrix of [Re X; Im X], then one
+ *     add or subtract and one multiply by (float)(1/Cw): |cov - exact| <= 2 (Cw + 4) 2^-24 sqrt(cov_pp cov_qq)).
+ *     The result is exactly Hermitian: cov[q][p] is the bitwise conjugate of cov[p][q] and the diagonal's imaginary
+ *     part is exactly 0.  Row (f, r) depends on its own inputs only: a batch equals its frames run alone, bit for bit.
+ *     F = 0 launches nothing.  RSL_ERR_INVALID: A, c0 or c1 out of range, S or C <= 0, null pointers with F > 0.
+ *
+ *     rsl_range_azimuth: cov c64 [n, A, A], Hermitian positive semi-definite; its upper triangle and the diagonal's
+ *     real part define it (the rest is not read).  steer_c64 device c64 [G][A]: any array's steering matrix rounded
+ *     to c64 (unit-modulus entries; it need not be uniform linear), G >= 1.  map f32 [n, G]; arg i32 [n] (nullable) =
+ *     the first-index argmax of the row.  With t = Re tr(cov_i): if t <= 0 the row is all 0 and arg is 0; otherwise
+ *       RSL_RA_BARTLETT  map[g] = Re(a_g^H R a_g) / A^2
+ *       RSL_RA_CAPON     map[g] = 1 / Re(a_g^H R_l^-1 a_g),  R_l = R + loading (t / A) I
+ *     (fp32; R_l^-1 from a Cholesky factorisation, its triangular inverse T and T^H T).  Both return the source power
+ *     + noise / A for a single source in white noise, so their values are directly comparable.  loading lies in
+ *     [RSL_RA_MIN_LOADING, 1] and is read by Capon only: cond(R_l) <= A / loading + 1, and below 1e-4 an fp32
+ *     factorisation has no digits left.  A cov that is not positive semi-definite is the caller's business (Capon's
+ *     factorisation may then give a NaN row, whose arg is 0).
+ *     n = 0 launches nothing.  RSL_ERR_INVALID: a bad method, A outside [2, RSL_RA_MAX_A], G < 1, loading out of
+ *     range or NaN, n < 0, null cov / steer_c64 / map with n > 0. */
+#define RSL_RA_BARTLETT 0
+#define RSL_RA_CAPON 1
+#define RSL_RA_MAX_A 16
+#define RSL_RA_MIN_LOADING 1e-4
+int rsl_range_cov(rsl_handle h, const void* rds, int F, int A, int S, int C, int c0, int c1, void* cov);
+int rsl_range_azimuth(rsl_handle h, const void* cov, long long n, int A, const void* steer_c64, int G,
+                      int method, double loading, void* map, void* arg);
+
 /* a11, a15, a26  normalised signature (c64 [n, A], nullable), ESPRIT closed form (f64 deg, nullable;
  *     angle_estimation.py:178-225 with esprit_scale = lambda / (2 pi d)), spatial phase
  *     angle(s1 conj(s0)) (f64, nullable; velocity_solver.py:136), az_out = az_table[gidx] (f64, nullable). */

@@ -588,6 +588,38 @@ int rsl_doa_smoothed(rsl_handle h, const void* rds, int A, int S, int C, const v
                    "doa_smoothed");
 }
 
+int rsl_range_cov(rsl_handle h, const void* rds, int F, int A, int S, int C, int c0, int c1, void* cov) {
+  if (!h) return RSL_ERR_INVALID;
+  if (F < 0 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_range_cov: bad shape");
+  if (A < 2 || A > RSL_RA_MAX_A) return fail(h, RSL_ERR_INVALID, "rsl_range_cov: antennas outside [2, RSL_RA_MAX_A]");
+  if (c0 < 0 || c0 >= c1 || c1 > C) return fail(h, RSL_ERR_INVALID, "rsl_range_cov: window needs 0 <= c0 < c1 <= C");
+  if (F == 0) return RSL_OK;
+  if (!rds || !cov) return fail(h, RSL_ERR_INVALID, "rsl_range_cov: null pointer");
+  Scope sc(h, RSL_K_DOA_SCAN);
+  return hip_check(h, rsl::launch_range_cov(h->stream, (const float2*)rds, F, A, S, C, c0, c1, (float2*)cov),
+                   "range_cov");
+}
+
+int rsl_range_azimuth(rsl_handle h, const void* cov, long long n, int A, const void* steer_c64, int G, int method,
+                      double loading, void* map, void* arg) {
+  if (!h) return RSL_ERR_INVALID;
+  if (n < 0) return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: n < 0");
+  if (method != RSL_RA_BARTLETT && method != RSL_RA_CAPON)
+    return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: method must be RSL_RA_BARTLETT or RSL_RA_CAPON");
+  if (A < 2 || A > RSL_RA_MAX_A)
+    return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: antennas outside [2, RSL_RA_MAX_A]");
+  if (G < 1) return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: G < 1");
+  if (!(loading >= RSL_RA_MIN_LOADING && loading <= 1.0))
+    return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: loading outside [RSL_RA_MIN_LOADING, 1]");
+  if (n == 0) return RSL_OK;
+  if (!cov || !steer_c64 || !map) return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: null pointer");
+  Scope sc(h, RSL_K_DOA_SCAN);
+  return hip_check(h,
+                   rsl::launch_range_azimuth(h->stream, (const float2*)cov, n, A, (const float2*)steer_c64, G,
+                                             method == RSL_RA_CAPON, (float)loading, (float*)map, (int*)arg),
+                   "range_azimuth");
+}
+
 int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
                     const void* ncell_dev, long long ncell, double esprit_scale, const void* gidx,
                     const void* az_table, void* sig_out, void* esprit_deg, void* phase, void* az_out) {

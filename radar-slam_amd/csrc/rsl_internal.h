@@ -125,6 +125,14 @@ hipError_t launch_doa_toep(hipStream_t st, CellList cl, const void* toep_tab, in
 hipError_t launch_doa_smoothed(hipStream_t st, CellList cl, const float2* steer, int G, int L, int nmax,
                                int num_sources, float rel, int* out_nsrc, int* out_idx, float* out_den, float* out_eig,
                                float* out_spec);
+// Range-azimuth maps (rsl_ramap.hip; the contracts are rsl_range_cov's and rsl_range_azimuth's in rsl.h): the
+// covariance of every range bin over the Doppler window [c0, c1) as one fp32 MFMA Gram tile, rds c64 [F, A, S, C] ->
+// cov c64 [F, S, A, A] (2 <= A <= 16), and the Bartlett (capon = 0) / Capon power of n covariances over the grid of
+// steer c64 [G][A] -> map f32 [n, G], arg i32 [n] (nullable).
+hipError_t launch_range_cov(hipStream_t st, const float2* rds, int F, int A, int S, int C, int c0, int c1,
+                            float2* cov);
+hipError_t launch_range_azimuth(hipStream_t st, const float2* cov, long long n, int A, const float2* steer, int G,
+                                int capon, float loading, float* map, int* arg);
 // Host: builds the Toeplitz operand table; returns 1 if the steering matrix is a uniform linear array.
 int toep_table_build(const double* steer_c128, int G, int M, uint16_t* out);
 // K4/K6: normalised signature, ESPRIT closed form (fp64), spatial phase, azimuth lookup.

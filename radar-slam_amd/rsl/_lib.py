@@ -22,6 +22,10 @@ STEER_TOEPLITZ = 1
 RULE_THRESHOLD, RULE_CA, RULE_OS = 0, 1, 2  # RSL_RULE_*: the detection rule of rsl_detect_power
 RULE_IDS = {'threshold': RULE_THRESHOLD, 'ca': RULE_CA, 'os': RULE_OS}
 SS_MAX_L = 8  # RSL_SS_MAX_L: the longest sub-array of rsl_doa_smoothed
+RA_BARTLETT, RA_CAPON = 0, 1  # RSL_RA_*: the method of rsl_range_azimuth
+RA_IDS = {'bartlett': RA_BARTLETT, 'capon': RA_CAPON}
+RA_MAX_A = 16  # RSL_RA_MAX_A: the most antennas of rsl_range_cov / rsl_range_azimuth
+RA_MIN_LOADING = 1e-4  # RSL_RA_MIN_LOADING: the least diagonal loading of the Capon map
 LOSS_HUBER, LOSS_TUKEY = 1, 2
 LOSS_IDS = {'huber': LOSS_HUBER, 'tukey': LOSS_TUKEY}
 LOSS_DEFAULT_C = {LOSS_HUBER: 1.345, LOSS_TUKEY: 4.685}  # 95 % efficiency at the normal distribution
@@ -66,6 +70,8 @@ SIGNATURES = {
                                _P, _P, _P, _P]),
     'rsl_doa_smoothed': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_longlong, _P, c_int, c_int, c_int, c_int,
                                  c_double, _P, _P, _P, _P, _P]),
+    'rsl_range_cov': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    'rsl_range_azimuth': (c_int, [_P, _P, c_longlong, c_int, _P, c_int, c_int, c_double, _P, _P]),
     'rsl_cell_extras': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_longlong, c_double, _P, _P, _P, _P,
                                 _P, _P]),
     'rsl_confidence': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_longlong, _P, _P, _P, _P]),

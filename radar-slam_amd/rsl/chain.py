@@ -93,8 +93,25 @@ class ChainConfig:
                                                # setting
     ss_rel: float = 0.05
     ss_max: int = 3                            # angles kept per cell (lowered to L - 1 where it exceeds it)
+    ra_map: Optional[str] = None               # 'bartlett' | 'capon': also form every range bin's spatial covariance
+                                               # over its Doppler bins (rsl_range_cov) and the range-azimuth power map
+                                               # on the chain's grid (rsl_range_azimuth): results()['ra_map'], ['ra_arg'];
+                                               # None: nothing is allocated or launched
+    ra_doppler: Optional[tuple] = None         # Doppler window (c0, c1) of the covariance; None: all num_chirps bins
+    ra_loading: float = 1e-2                   # Capon's diagonal loading, in [_lib.RA_MIN_LOADING, 1]
 
     def __post_init__(self):
+        if self.ra_map is not None and self.ra_map not in _lib.RA_IDS:
+            raise ValueError(f"ra_map must be None, 'bartlett' or 'capon', not {self.ra_map!r}")
+        if self.ra_doppler is not None:
+            if len(tuple(self.ra_doppler)) != 2 or not (0 <= int(self.ra_doppler[0]) < int(self.ra_doppler[1])
+                                                        <= int(self.num_chirps)):
+                raise ValueError(f'ra_doppler must be (c0, c1) with 0 <= c0 < c1 <= {int(self.num_chirps)}, '
+                                 f'not {self.ra_doppler!r}')
+        if not _lib.RA_MIN_LOADING <= float(self.ra_loading) <= 1.0:
+            raise ValueError(f'ra_loading must lie in [{_lib.RA_MIN_LOADING}, 1], not {self.ra_loading!r}')
+        if self.ra_map is not None and not 2 <= int(self.num_antennas) <= _lib.RA_MAX_A:
+            raise ValueError(f'ra_map needs 2 to {_lib.RA_MAX_A} antennas, not {self.num_antennas}')
         if self.ss_len is not None and not 2 <= int(self.ss_len) <= _lib.SS_MAX_L:
             raise ValueError(f'ss_len must lie in [2, {_lib.SS_MAX_L}], not {self.ss_len!r}')
         if int(self.ss_max) < 1:
@@ -227,6 +244,12 @@ class RadarChain:
             self.ss_steer = ctx.steering_sub(steer_c128, L)
             self.ss = dict(nsrc=e((cc,), torch.int32), idx=e((cc, self.ss_nmax), torch.int32),
                            den=e((cc, self.ss_nmax), torch.float32))
+        self.ra = None
+        if cfg.ra_map is not None:  # range-azimuth map: per-range covariance, then its power over the grid
+            self.ra_steer = ctx.steering_c64(steer_c128)
+            self.ra_win = (0, C) if cfg.ra_doppler is None else (int(cfg.ra_doppler[0]), int(cfg.ra_doppler[1]))
+            self.ra_cov = e((F, S, A, A), torch.complex64)
+            self.ra = dict(map=e((F, S, len(self.grid)), torch.float32), arg=e((F, S), torch.int32))
         # one signature gather for DoA + ESPRIT + phase when the Toeplitz path applies (uniform linear array)
         self.fused_doa = bool(self.steer['toeplitz']) and A >= 2 and not cfg.spectrum
         self.spec = None
@@ -333,6 +356,9 @@ class RadarChain:
         if self.ss is not None:
             ctx.doa_smoothed(self.rds, L['c_frame'], L['c_rc'], self.ss_steer, n=self.cell_cap, n_dev=self.ncell_dev,
                              nmax=self.ss_nmax, num_sources=cfg.ss_sources, rel=cfg.ss_rel, out=self.ss)
+        if self.ra is not None:
+            ctx.range_cov(self.rds, self.ra_win, out=self.ra_cov)
+            ctx.range_azimuth(self.ra_cov, self.ra_steer, cfg.ra_map, loading=cfg.ra_loading, out=self.ra)
         if velocity and cfg.velocity_loss == 'consensus':
             # vel columns 2-7 become {cost, rmse_in, n_in, n, best_h, n_valid} (include/rsl.h)
             ctx.velocity_consensus(None, self.ext['phase'], self.offs['cell_base'], k=self.k, scale=cfg.velocity_scale,
@@ -368,6 +394,8 @@ class RadarChain:
         if self.ss is not None:
             extra.update(ss_nsrc=h(self.ss['nsrc'], nc), ss_gidx=h(self.ss['idx'], nc).astype(np.int64),
                          ss_den=h(self.ss['den'], nc).astype(np.float64))
+        if self.ra is not None:  # f32 [F, S, G] and i32 [F, S]: every range bin of every frame
+            extra.update(ra_map=self.ra['map'].cpu().numpy(), ra_arg=self.ra['arg'].cpu().numpy())
         return dict(entry_base=self.offs['entry_base'].cpu().numpy(), cell_base=self.offs['cell_base'].cpu().numpy(),
                     **dict(zip(('e_ant', 'e_rbin', 'e_dbin'), unpack_coord(h(L['e_coord'], ne)))),
                     e_cell=h(L['e_cell'], ne), e_pdb=h(L['e_pdb'], ne).astype(np.float64), c_frame=h(L['c_frame'], nc),

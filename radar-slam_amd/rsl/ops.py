@@ -278,6 +278,87 @@ def doa_smoothed(steer_c128: np.ndarray, *, sigs=None, rds=None, rbins=None, dbi
     return res
 
 
+# -- range-azimuth maps: per-range covariance, Bartlett and Capon ----------------------------------------
+def _ra_check_rds(fn: str, rds, doppler):
+    """Shape, antenna-count and window checks of an RDS [A, S, C] or [F, A, S, C]; returns the window (c0, c1)."""
+    shape = tuple(int(d) for d in rds.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError(f'{fn}: rds must be [A, S, C] or [F, A, S, C], not {len(shape)} axes')
+    A, S, C = shape[-3:]
+    if not 2 <= A <= _lib.RA_MAX_A:
+        raise ValueError(f'{fn}: {A} antennas outside [2, {_lib.RA_MAX_A}]')
+    if S < 1 or C < 1:
+        raise ValueError(f'{fn}: empty range or Doppler axis {shape}')
+    c0, c1 = (0, C) if doppler is None else (int(doppler[0]), int(doppler[1]))
+    if not 0 <= c0 < c1 <= C:
+        raise ValueError(f'{fn}: Doppler window ({c0}, {c1}) outside 0 <= c0 < c1 <= {C}')
+    return c0, c1
+
+
+def range_covariance(rds, doppler=None, ctx: Optional[Context] = None, keep_on_device=False):
+    """rds [A, S, C] or [F, A, S, C] -> the multi-snapshot spatial covariance of every range bin, [S, A, A] or
+    [F, S, A, A] (rsl_range_cov): the mean of x x^H over the Doppler bins doppler = (c0, c1) (None: all), accumulated
+    in fp32 and exactly Hermitian.  complex128 host array, or the complex64 device tensor."""
+    win = _ra_check_rds('range_covariance', rds, doppler)
+    c = _ctx(ctx)
+    single = len(rds.shape) == 3
+    cov = c.range_cov(_dev_rds4(c, rds), win)
+    if not keep_on_device:
+        cov = to_host(cov, np.complex128)
+    return cov[0] if single else cov
+
+
+def range_azimuth_map(steer_c128: np.ndarray, *, rds=None, cov=None, method='capon', doppler=None, loading=1e-2,
+                      want_arg=False, ctx: Optional[Context] = None):
+    """The range-azimuth power map (rsl_range_azimuth, specified in include/rsl.h) over the grid of the [G, A]
+    steering matrix steer_c128 (any array geometry), from an RDS [A, S, C] / [F, A, S, C] (its per-range covariance
+    over the Doppler window is formed first, rsl_range_cov) or from given Hermitian covariances cov [.., A, A].
+    method 'bartlett': a^H R a / A^2; 'capon': 1 / (a^H R_l^-1 a) with R_l = R + loading (tr R / A) I, loading in
+    [1e-4, 1].  Returns a dict of host arrays: map f64 [.., S, G] ([.., G] from cov), arg i64 (the first-index argmax
+    of every row, on request) and, when computed from an RDS, cov c128 [.., S, A, A]."""
+    st = np.asarray(steer_c128)
+    if st.ndim != 2 or st.shape[0] < 1:
+        raise ValueError('range_azimuth_map: steer_c128 must be [G, A] with G >= 1')
+    G, A = st.shape
+    if method not in _lib.RA_IDS:
+        raise ValueError(f"range_azimuth_map: method must be 'bartlett' or 'capon', not {method!r}")
+    if not _lib.RA_MIN_LOADING <= float(loading) <= 1.0:
+        raise ValueError(f'range_azimuth_map: loading {loading} outside [{_lib.RA_MIN_LOADING}, 1]')
+    if (rds is None) == (cov is None):
+        raise ValueError('range_azimuth_map: give exactly one of rds and cov')
+    if not 2 <= A <= _lib.RA_MAX_A:
+        raise ValueError(f'range_azimuth_map: {A} antennas outside [2, {_lib.RA_MAX_A}]')
+    if rds is not None:
+        win = _ra_check_rds('range_azimuth_map', rds, doppler)
+        if int(rds.shape[-3]) != A:
+            raise ValueError(f'range_azimuth_map: RDS of {int(rds.shape[-3])} antennas, steering matrix of {A}')
+    else:
+        shape = tuple(int(d) for d in cov.shape)
+        if len(shape) < 2 or shape[-1] != shape[-2]:
+            raise ValueError(f'range_azimuth_map: cov must be [.., A, A], not {shape}')
+        if shape[-1] != A:
+            raise ValueError(f'range_azimuth_map: covariances of {shape[-1]} antennas, steering matrix of {A}')
+    c = _ctx(ctx)
+    res = {}
+    if rds is not None:
+        single = len(rds.shape) == 3
+        d_cov = c.range_cov(_dev_rds4(c, rds), win)
+        if single:
+            d_cov = d_cov[0]
+        res['cov'] = to_host(d_cov, np.complex128)
+    else:
+        d_cov = as_dev_c64(c, cov).contiguous()
+        if d_cov.dim() == 2:
+            d_cov = d_cov.unsqueeze(0)
+    m, arg = c.range_azimuth(d_cov, c.steering_c64(st), method, loading=loading, want_arg=want_arg)
+    if rds is None and len(cov.shape) == 2:
+        m, arg = m[0], (arg[0] if arg is not None else None)
+    res['map'] = to_host(m, np.float64)
+    if want_arg:
+        res['arg'] = to_host(arg).astype(np.int64)
+    return res
+
+
 def subspace_music(sigs, steer_c128: np.ndarray, num_sources: int, ctx: Optional[Context] = None) -> np.ndarray:
     """MUSIC spectrum f64 [n, G] for any num_sources (angle_estimation.py:109-154; rsl_music_subspace)."""
     c = _ctx(ctx)

@@ -435,6 +435,58 @@ class Context:
                                              _ptr(idx), _ptr(den), _ptr(eig), _ptr(spec)), 'rsl_doa_smoothed')
         return nsrc, idx, den, eig, spec
 
+    # -- range-azimuth maps -----------------------------------------------------------------------
+    def range_cov(self, rds, doppler=None, out=None):
+        """rds complex64 [F, A, S, C] -> the spatial covariance of every range bin over the Doppler window
+        doppler = (c0, c1) (None: all C bins), complex64 [F, S, A, A], exactly Hermitian (rsl_range_cov)."""
+        torch = self.torch
+        if rds.dim() != 4 or rds.dtype != torch.complex64:
+            raise ValueError('range_cov: rds must be complex64 [F, A, S, C]')
+        F, A, S, C = rds.shape
+        c0, c1 = (0, C) if doppler is None else (int(doppler[0]), int(doppler[1]))
+        if out is None:
+            out = self.empty((F, S, A, A), torch.complex64)
+        self._bind()
+        self.check(self.lib.rsl_range_cov(self.h, _ptr(rds), F, A, S, C, c0, c1, _ptr(out)), 'rsl_range_cov')
+        return out
+
+    def steering_c64(self, steer_c128: np.ndarray):
+        """Upload a steering matrix [G, A] rounded to complex64 (the table of rsl_range_azimuth), cached."""
+        st = np.ascontiguousarray(np.asarray(steer_c128, dtype=np.complex128))
+        key = ('c64', st.shape, hash(st.tobytes()))
+        hit = self._steer_cache.get(key)
+        if hit is None:
+            hit = self.to_dev(st.astype(np.complex64))
+            self._steer_cache[key] = hit
+        return hit
+
+    def range_azimuth(self, cov, steer_c64, method, loading: float = 1e-2, want_arg: bool = False, out=None):
+        """cov complex64 [.., A, A] (Hermitian) -> the Bartlett or Capon power over the grid of steer_c64 (device c64
+        [G, A], steering_c64), float32 [.., G], and on request the first-index argmax of every row, int32 [..]
+        (rsl_range_azimuth).  method: 'bartlett' / 'capon' or the _lib.RA_* id; loading is read by Capon only.
+        out: optional dict of preallocated map / arg.  Returns (map, arg or None)."""
+        torch = self.torch
+        if cov.dim() < 3 or cov.dtype != torch.complex64 or cov.shape[-1] != cov.shape[-2]:
+            raise ValueError('range_azimuth: cov must be complex64 [.., A, A]')
+        if isinstance(method, str):
+            if method not in _lib.RA_IDS:
+                raise ValueError(f"range_azimuth: method must be 'bartlett' or 'capon', not {method!r}")
+            method = _lib.RA_IDS[method]
+        A = int(cov.shape[-1])
+        if steer_c64.dim() != 2 or steer_c64.dtype != torch.complex64 or int(steer_c64.shape[1]) != A:
+            raise ValueError(f'range_azimuth: steer_c64 must be complex64 [G, {A}]')
+        G = int(steer_c64.shape[0])
+        lead = tuple(cov.shape[:-2])
+        n = 1
+        for d in lead:
+            n *= int(d)
+        m = self._buf(out, 'map', lead + (G,), torch.float32)
+        arg = self._buf(out, 'arg', lead, torch.int32) if want_arg else (out or {}).get('arg')
+        self._bind()
+        self.check(self.lib.rsl_range_azimuth(self.h, _ptr(cov), n, A, _ptr(steer_c64), G, int(method),
+                                              float(loading), _ptr(m), _ptr(arg)), 'rsl_range_azimuth')
+        return m, arg
+
     def cell_extras(self, rds, c_frame, c_rc, *, n: int, n_dev=None, esprit_scale: float = 1 / math.pi,
                     want_sig=False, want_esprit=False, want_phase=False, gidx=None, az_table=None, bufs=None):
         torch = self.torch

@@ -165,6 +165,16 @@ class AngleEstimator:
         logger.info(f"Processed {len(targets)} targets using smoothed music")
         return targets
 
+    def range_azimuth_map(self, rds: np.ndarray, method: str = 'capon', doppler: Optional[Tuple[int, int]] = None,
+                          loading: float = 1e-2) -> Dict:
+        """The range-azimuth power map of an RDS [A, S, C] on this estimator's grid (ops.range_azimuth_map): every
+        range bin's spatial covariance over its Doppler bins (doppler = (c0, c1); None: all), then 'bartlett' (a^H R a
+        / A^2) or 'capon' (1 / a^H R_l^-1 a, diagonal loading `loading`).  Returns 'map' f64 [S, G], 'angles_deg' (the
+        grid) and 'arg' i64 [S] (the grid index of every range bin's maximum)."""
+        res = ops.range_azimuth_map(self._steer, rds=rds, method=method, doppler=doppler, loading=loading,
+                                    want_arg=True)
+        return {'map': res['map'], 'angles_deg': self.azimuth_grid, 'arg': res['arg']}
+
     def visualize_angle_spectrum(self, targets: List[Dict], save_path: Optional[str] = None) -> None:
         if not targets:
             logger.warning("No targets to visualize")

@@ -1,4 +1,4 @@
-"""What the measurement tools (cfar_bench, oscfar_bench, nci_bench, ssmusic_bench, vel_robust_bench) share: the event timer, the
+"""What the measurement tools (cfar_bench, oscfar_bench, nci_bench, ssmusic_bench, vel_robust_bench, ra_map_bench) share: the event timer, the
 timed launches through rsl_timing_*, the whole-step measurement of a chain at configs[2], and the part runner.
 
 The part runner starts one child process per part (the tool itself with --part NAME), each under its own time limit;
