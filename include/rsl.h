@@ -366,7 +366,10 @@ int rsl_confidence(rsl_handle h, const void* rds, int A, int S, int C, const voi
  *     observed phase, amask u32 [N] (nullable; multiplicity = popcount), seg i64 [F+1] (device; bounds
  *     clamped to n = N, the arrays' length: a capacity-sized list that overflowed ends at its capacity),
  *     k = 4 pi dt / lambda, ridge >= 0, bounds4 (host) = {vx_lo, vx_hi, vy_lo, vy_hi};
- *     out f64 [F, 8] = {vx, vy, cost, rmse, max_residual, n, det, 0}; resid/pred f64 [N] nullable. */
+ *     out f64 [F, 8] = {vx, vy, cost, rmse, max_residual, n, det, 0}; resid/pred f64 [N] nullable.
+ *     F = 0 launches nothing.  RSL_ERR_INVALID: F < 0 or n < 0; ridge < 0 or NaN (also at F = 0); gidx with G <= 0,
+ *     G > 2048 or without az_table; az and gidx both null; null y, seg, out or bounds4; a box with lo > hi or a NaN.
+ *     Timed under RSL_K_VELOCITY. */
 int rsl_velocity(rsl_handle h, const void* az, const void* gidx, const void* az_table, int G, const void* y,
                  const void* amask, const void* seg, long long n, int F, double k, double ridge, const double* bounds4,
                  void* out, void* resid, void* pred);

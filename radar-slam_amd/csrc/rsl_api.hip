@@ -650,50 +650,57 @@ int rsl_confidence(rsl_handle h, const void* rds, int A, int S, int C, const voi
                    "confidence");
 }
 
+// The checks rsl_velocity, rsl_velocity_robust and rsl_velocity_consensus (fn) share, in one order: the counts; the
+// entry point's own scalars (own: the message of the first that fails, else null); the ridge; an empty batch (RSL_OK
+// with p->F = 0: nothing to launch); the pointers; the grid table; the box.  Fills *p with the typed problem.
+static int velocity_problem(rsl_handle h, const char* fn, const char* own, const void* az, const void* gidx,
+                            const void* az_table, int G, const void* y, const void* amask, const void* seg, long long n,
+                            int F, double k, double ridge, const double* bounds4, const void* out, rsl::VelProblem* p) {
+  *p = {};
+  if (!h) return RSL_ERR_INVALID;
+  auto bad = [&](const char* what) { return fail(h, RSL_ERR_INVALID, std::string(fn) + ": " + what); };
+  if (F < 0 || n < 0) return bad("bad argument");
+  if (own) return bad(own);
+  if (!(ridge >= 0)) return bad("ridge must be >= 0");
+  if (F == 0) return RSL_OK;
+  if ((!az && !gidx) || !y || !seg || !bounds4 || !out) return bad("null pointer");
+  if (gidx && (!az_table || G <= 0 || G > 2048)) return bad("bad grid table");
+  if (!(bounds4[0] <= bounds4[1]) || !(bounds4[2] <= bounds4[3])) return bad("bad bounds");
+  *p = {(const double*)az, (const int*)gidx, (const double*)az_table, G, (const double*)y, (const unsigned*)amask,
+        (const long long*)seg, n, F, k, ridge, bounds4[0], bounds4[1], bounds4[2], bounds4[3]};
+  return RSL_OK;
+}
+
 int rsl_velocity(rsl_handle h, const void* az, const void* gidx, const void* az_table, int G, const void* y,
                  const void* amask, const void* seg, long long n, int F, double k, double ridge, const double* bounds4,
                  void* out, void* resid, void* pred) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || n < 0) return fail(h, RSL_ERR_INVALID, "rsl_velocity: bad argument");
-  if (F == 0) return RSL_OK;
-  if ((!az && !gidx) || !y || !seg || !bounds4 || !out) return fail(h, RSL_ERR_INVALID, "rsl_velocity: bad argument");
-  if (gidx && (!az_table || G <= 0 || G > 2048)) return fail(h, RSL_ERR_INVALID, "rsl_velocity: bad grid table");
-  if (!(bounds4[0] <= bounds4[1]) || !(bounds4[2] <= bounds4[3]) || ridge < 0)
-    return fail(h, RSL_ERR_INVALID, "rsl_velocity: bad bounds/ridge");
+  rsl::VelProblem p;
+  const int rc = velocity_problem(h, "rsl_velocity", nullptr, az, gidx, az_table, G, y, amask, seg, n, F, k, ridge,
+                                  bounds4, out, &p);
+  if (rc || p.F == 0) return rc;
   Scope sc(h, RSL_K_VELOCITY);
-  return hip_check(h,
-                   rsl::launch_velocity(h->stream, (const double*)az, (const int*)gidx, (const double*)az_table, G,
-                                        (const double*)y, (const unsigned*)amask, (const long long*)seg, n, F, k, ridge,
-                                        bounds4, (double*)out, (double*)resid, (double*)pred),
-                   "velocity");
+  return hip_check(h, rsl::launch_velocity(h->stream, p, (double*)out, (double*)resid, (double*)pred), "velocity");
 }
 
 int rsl_velocity_robust(rsl_handle h, const void* az, const void* gidx, const void* az_table, int G, const void* y,
                         const void* amask, const void* seg, long long n, int F, double k, double ridge,
                         const double* bounds4, int loss, double c, double scale, int iters, double tol, void* out,
                         void* weight, void* resid) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || n < 0) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: bad argument");
-  if (loss != RSL_LOSS_HUBER && loss != RSL_LOSS_TUKEY)
-    return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: loss must be RSL_LOSS_HUBER or RSL_LOSS_TUKEY");
-  if (!(c > 0) || !std::isfinite(c)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: c must be finite, > 0");
-  if (std::isnan(scale) || (std::isinf(scale) && scale > 0))
-    return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: scale must be finite (<= 0: estimated)");
-  if (iters < 1 || iters > 1000) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: iters outside 1..1000");
-  if (!(tol >= 0)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: tol must be >= 0");
-  if (!(ridge >= 0)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: ridge must be >= 0");
-  if (F == 0) return RSL_OK;
-  if ((!az && !gidx) || !y || !seg || !bounds4 || !out)
-    return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: null pointer");
-  if (gidx && (!az_table || G <= 0 || G > 2048)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: bad grid table");
-  if (!(bounds4[0] <= bounds4[1]) || !(bounds4[2] <= bounds4[3]))
-    return fail(h, RSL_ERR_INVALID, "rsl_velocity_robust: bad bounds");
+  const char* own = (loss != RSL_LOSS_HUBER && loss != RSL_LOSS_TUKEY) ? "loss must be RSL_LOSS_HUBER or RSL_LOSS_TUKEY"
+                    : (!(c > 0) || !std::isfinite(c))                  ? "c must be finite, > 0"
+                    : (std::isnan(scale) || (std::isinf(scale) && scale > 0))
+                        ? "scale must be finite (<= 0: estimated)"
+                    : (iters < 1 || iters > 1000) ? "iters outside 1..1000"
+                    : !(tol >= 0)                 ? "tol must be >= 0"
+                                                  : nullptr;
+  rsl::VelProblem p;
+  const int rc = velocity_problem(h, "rsl_velocity_robust", own, az, gidx, az_table, G, y, amask, seg, n, F, k, ridge,
+                                  bounds4, out, &p);
+  if (rc || p.F == 0) return rc;
   Scope sc(h, RSL_K_VELOCITY);
   return hip_check(h,
-                   rsl::launch_velocity_robust(h->stream, (const double*)az, (const int*)gidx, (const double*)az_table,
-                                               G, (const double*)y, (const unsigned*)amask, (const long long*)seg, n, F,
-                                               k, ridge, bounds4, loss, c, scale, iters, tol, (double*)out,
-                                               (float*)weight, (double*)resid),
+                   rsl::launch_velocity_robust(h->stream, p, loss, c, scale, iters, tol, (double*)out, (float*)weight,
+                                               (double*)resid),
                    "velocity_robust");
 }
 
@@ -701,31 +708,21 @@ int rsl_velocity_consensus(rsl_handle h, const void* az, const void* gidx, const
                            const void* amask, const void* seg, long long n, int F, double k, double ridge,
                            const double* bounds4, double c, double scale, int hyps, double min_det, int refine,
                            unsigned long long seed, long long frame0, void* out, void* weight, void* resid) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || n < 0) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: bad argument");
-  if (!(c > 0) || !std::isfinite(c)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: c must be finite, > 0");
-  if (!(scale > 0) || !std::isfinite(scale))
-    return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: scale must be finite, > 0");
-  if (hyps < 1 || hyps > RSL_CONSENSUS_MAX_H)
-    return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: hyps outside 1..RSL_CONSENSUS_MAX_H");
-  if (!(min_det > 0) || !(min_det <= 1)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: min_det outside (0, 1]");
-  if (refine < 0 || refine > 100) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: refine outside 0..100");
-  if (frame0 < 0) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: frame0 must be >= 0");
-  if (!(ridge >= 0)) return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: ridge must be >= 0");
-  if (F == 0) return RSL_OK;
-  if ((!az && !gidx) || !y || !seg || !bounds4 || !out)
-    return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: null pointer");
-  if (gidx && (!az_table || G <= 0 || G > 2048))
-    return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: bad grid table");
-  if (!(bounds4[0] <= bounds4[1]) || !(bounds4[2] <= bounds4[3]))
-    return fail(h, RSL_ERR_INVALID, "rsl_velocity_consensus: bad bounds");
+  const char* own = (!(c > 0) || !std::isfinite(c))           ? "c must be finite, > 0"
+                    : (!(scale > 0) || !std::isfinite(scale)) ? "scale must be finite, > 0"
+                    : (hyps < 1 || hyps > RSL_CONSENSUS_MAX_H) ? "hyps outside 1..RSL_CONSENSUS_MAX_H"
+                    : (!(min_det > 0) || !(min_det <= 1))     ? "min_det outside (0, 1]"
+                    : (refine < 0 || refine > 100)            ? "refine outside 0..100"
+                    : frame0 < 0                              ? "frame0 must be >= 0"
+                                                              : nullptr;
+  rsl::VelProblem p;
+  const int rc = velocity_problem(h, "rsl_velocity_consensus", own, az, gidx, az_table, G, y, amask, seg, n, F, k,
+                                  ridge, bounds4, out, &p);
+  if (rc || p.F == 0) return rc;
   Scope sc(h, RSL_K_VELOCITY);
   return hip_check(h,
-                   rsl::launch_velocity_consensus(h->stream, (const double*)az, (const int*)gidx,
-                                                  (const double*)az_table, G, (const double*)y, (const unsigned*)amask,
-                                                  (const long long*)seg, n, F, k, ridge, bounds4, c, scale, hyps,
-                                                  min_det, refine, seed, frame0, (double*)out, (float*)weight,
-                                                  (double*)resid),
+                   rsl::launch_velocity_consensus(h->stream, p, c, scale, hyps, min_det, refine, seed, frame0,
+                                                  (double*)out, (float*)weight, (double*)resid),
                    "velocity_consensus");
 }
 

@@ -142,20 +142,28 @@ hipError_t launch_cell_extras(hipStream_t st, CellList cl, double esprit_scale, 
 // K7: robust confidence for (cell, grid index) pairs (fp64).
 hipError_t launch_confidence(hipStream_t st, CellList cl, const int* gidx, const double* steer_c128,
                              const double* steer_phase, double* conf_out);
+// The problem the three velocity solvers share (rsl_velocity's inputs in include/rsl.h), checked and typed by
+// velocity_problem (rsl_api.hip); the box is bounds4 unpacked.  Host side only, like DetectArgs: the kernels take the
+// members as separate `__restrict__` arguments (a member loses it, and they store weight / resid between loads of y).
+struct VelProblem {
+  const double* az;
+  const int* gidx;
+  const double* az_table;
+  int G;
+  const double* y;
+  const unsigned* amask;
+  const long long* seg;
+  long long n;
+  int F;
+  double k, ridge, lx, hx, ly, hy;
+};
 // K8: batched bounded / ridge least squares velocity solve, one segment per frame.
-hipError_t launch_velocity(hipStream_t st, const double* az, const int* gidx, const double* az_table, int G,
-                           const double* y, const unsigned* amask, const long long* seg, long long n, int F, double k,
-                           double ridge,
-                           const double* bounds4, double* out, double* resid, double* pred);
+hipError_t launch_velocity(hipStream_t st, const VelProblem& p, double* out, double* resid, double* pred);
 // K8 alternative (rsl_vel_robust.hip): Huber / Tukey IRLS from the LS start, fixed or median-estimated scale.
-hipError_t launch_velocity_robust(hipStream_t st, const double* az, const int* gidx, const double* az_table, int G,
-                                  const double* y, const unsigned* amask, const long long* seg, long long n, int F,
-                                  double k, double ridge, const double* bounds4, int loss, double c, double scale,
-                                  int iters, double tol, double* out, float* weight, double* resid);
+hipError_t launch_velocity_robust(hipStream_t st, const VelProblem& p, int loss, double c, double scale, int iters,
+                                  double tol, double* out, float* weight, double* resid);
 // K8c: consensus (RANSAC) velocity solve (rsl_vel_consensus.hip); the contract is rsl_velocity_consensus's in rsl.h.
-hipError_t launch_velocity_consensus(hipStream_t st, const double* az, const int* gidx, const double* az_table, int G,
-                                     const double* y, const unsigned* amask, const long long* seg, long long n, int F,
-                                     double k, double ridge, const double* bounds4, double c, double scale, int hyps,
+hipError_t launch_velocity_consensus(hipStream_t st, const VelProblem& p, double c, double scale, int hyps,
                                      double min_det, int refine, unsigned long long seed, long long frame0, double* out,
                                      float* weight, double* resid);
 

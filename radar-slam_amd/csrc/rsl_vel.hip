@@ -8,11 +8,15 @@
 // best of the four edge minimisers (1-D clamp).  ``ridge`` adds ridge*(vx^2+vy^2)
 // (velocity_solver_improved.py:261 without the wrap).  Items carry a multiplicity (popcount of the
 // antenna mask of a deduplicated cell) so duplicate per-antenna detections count as in the reference.
+// The cell loader, the moments, the frame prologue, the reduction and the 2x2 box solve are rsl_vel_common.h's.
 #include "rsl_common.h"
 #include "rsl_internal.h"
 #include "rsl_vel_common.h"
 
 namespace rsl {
+
+constexpr int kVelThreads = 512;  // k_velocity's only launch shape
+constexpr int kVelWaves = kVelThreads / 64;
 
 __device__ double block_max(double v, double* sh) {
   const int t = threadIdx.x;
@@ -22,7 +26,7 @@ __device__ double block_max(double v, double* sh) {
   __syncthreads();
   double r = -1.0;
   if (t == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r = fmax(r, sh[w]);
+    for (int w = 0; w < kVelWaves; ++w) r = fmax(r, sh[w]);
   __syncthreads();
   return r;
 }
@@ -44,56 +48,37 @@ RSL_DEV double unkey(unsigned long long k) {
 // of squares is the quadratic form of the moments; it is used when its terms do not cancel (R2 >= 1e-6 of their
 // magnitude sum, i.e. < 1e-9 relative rounding), else (a near-perfect fit) R2 is summed per cell in a second pass,
 // as it is for the az path and whenever per-cell residuals / predictions are requested.
-__global__ __launch_bounds__(512) void k_velocity(const double* __restrict__ az, const int* __restrict__ gidx,
-                                                  const double* __restrict__ az_table, int G,
-                                                  const double* __restrict__ y, const unsigned* __restrict__ amask,
-                                                  const long long* __restrict__ seg, long long nmax, double k, double ridge,
-                                                  double lx, double hx, double ly, double hy,
-                                                  double* __restrict__ out, double* __restrict__ resid,
-                                                  double* __restrict__ pred) {
-  __shared__ double sh[8];
+__global__ __launch_bounds__(kVelThreads) void k_velocity(
+    const double* __restrict__ az, const int* __restrict__ gidx, const double* __restrict__ az_table, int G,
+    const double* __restrict__ y, const unsigned* __restrict__ amask, const long long* __restrict__ seg, long long nmax,
+    double k, double ridge, double lx, double hx, double ly, double hy, double* __restrict__ out,
+    double* __restrict__ resid, double* __restrict__ pred) {
+  __shared__ double red[kVelWaves * 7];  // wave partials of the moments, then of R2 and the maximum
   __shared__ double mom[7];
   __shared__ double sol[3];
   extern __shared__ double cs_tab[];  // [2G] cos, sin of the grid azimuths, then [2G] min / max phase keys (gidx path)
-  const bool tab = gidx != nullptr;
-  const bool grp = tab;  // per-group extremes: 32 G B of LDS (rsl_velocity admits G <= 2048)
+  const bool tab = gidx != nullptr;  // with it, per-group extremes: 32 G B of LDS (rsl_velocity admits G <= 2048)
   unsigned long long* ymn = reinterpret_cast<unsigned long long*>(cs_tab + 2 * G);
   unsigned long long* ymx = ymn + G;
-  if (tab) {
-    for (int g = threadIdx.x; g < G; g += blockDim.x) {
-      sincos(az_table[g], &cs_tab[G + g], &cs_tab[g]);
-      if (grp) {
-        ymn[g] = ~0ull;
-        ymx[g] = 0ull;  // no key is 0 (that would be a NaN's bits): 0 marks an empty group
-      }
-    }
-    __syncthreads();
+  for (int g = threadIdx.x; tab && g < G; g += kVelThreads) {
+    ymn[g] = ~0ull;
+    ymx[g] = 0ull;  // no key is 0 (that would be a NaN's bits): 0 marks an empty group
   }
   const long f = blockIdx.x;
-  // segment bounds clamped to the arrays' length (an overflowed capacity-sized list ends at its capacity)
-  const long long b = seg[f] < nmax ? seg[f] : nmax, e = seg[f + 1] < nmax ? seg[f + 1] : nmax;
-  double n = 0, cc = 0, cs = 0, ss = 0, cy = 0, sy = 0, yy = 0;
-  auto acc1 = [&](double w, double c, double s, double yi) {
-    n += w;
-    cc += w * c * c;
-    cs += w * c * s;
-    ss += w * s * s;
-    cy += w * c * yi;
-    sy += w * s * yi;
-    yy += w * yi * yi;
-  };
-  const long long step = (long long)blockDim.x * kVelU;
+  long long b, e;
+  vel_frame<kVelThreads>(tab, az_table, G, seg, nmax, f, cs_tab, b, e);  // its barrier publishes the keys too
+  // the first pass is not an rv_cells callback: the extremes need the grid index and the raw mask
+  double v[7] = {0, 0, 0, 0, 0, 0, 0};
   if (tab) {
-    // kVelU cells per thread per trip, all loads issued first: the loop is HBM-latency bound otherwise
-    for (long long i0 = b + threadIdx.x; i0 < e; i0 += step) {
+    for (long long i0 = b + threadIdx.x; i0 < e; i0 += (long long)kVelThreads * kVelU) {
       int gv[kVelU];
       double yv[kVelU];
       unsigned mv[kVelU];
-      vel_load(i0, e, blockDim.x, gidx, y, amask, gv, yv, mv);
+      vel_load(i0, e, kVelThreads, gidx, y, amask, gv, yv, mv);
 #pragma unroll
       for (int u = 0; u < kVelU; ++u) {
-        acc1((double)__popc(mv[u]), cs_tab[gv[u]], cs_tab[G + gv[u]], yv[u]);
-        if (grp && mv[u] != 0u && yv[u] == yv[u]) {  // weight > 0, not NaN (fmax ignores a NaN residual)
+        vel_moments(v, (double)__popc(mv[u]), cs_tab[gv[u]], cs_tab[G + gv[u]], yv[u]);
+        if (mv[u] != 0u && yv[u] == yv[u]) {  // weight > 0, not NaN (fmax ignores a NaN residual)
           const unsigned long long kk = okey(yv[u]);
           atomicMin(&ymn[gv[u]], kk);
           atomicMax(&ymx[gv[u]], kk);
@@ -101,14 +86,13 @@ __global__ __launch_bounds__(512) void k_velocity(const double* __restrict__ az,
       }
     }
   } else {
-    for (long long i = b + threadIdx.x; i < e; i += blockDim.x) {
+    for (long long i = b + threadIdx.x; i < e; i += kVelThreads) {
       double s, c;
       sincos(az[i], &s, &c);
-      acc1(amask ? (double)__popc(amask[i]) : 1.0, c, s, y[i]);
+      vel_moments(v, amask ? (double)__popc(amask[i]) : 1.0, c, s, y[i]);
     }
   }
-  const double vals[7] = {n, cc, cs, ss, cy, sy, yy};
-  block_sum7(vals, sh, mom);
+  rv_reduce7<kVelThreads>(v, red, mom);
   if (threadIdx.x == 0) {
     // the moments in registers, read once for the solve and the residual form below: which product the compiler fuses
     // into each fma of that form (the last bit of the cost) follows the order of these reads
@@ -124,11 +108,14 @@ __global__ __launch_bounds__(512) void k_velocity(const double* __restrict__ az,
     const double q = m[6] - 2.0 * (kx * m[4] + ky * m[5]) + kx * kx * m[1] + 2.0 * kx * ky * m[2] + ky * ky * m[3];
     const double mag = m[6] + 2.0 * (fabs(kx * m[4]) + fabs(ky * m[5])) + kx * kx * m[1] + 2.0 * fabs(kx * ky * m[2]) +
                        ky * ky * m[3];
-    sol[2] = (grp && q >= 1e-6 * mag) ? q : -1.0;
+    sol[2] = (tab && q >= 1e-6 * mag) ? q : -1.0;
   }
   __syncthreads();
   const double vx = sol[0], vy = sol[1], r2m = sol[2];
   double r2 = 0.0, rmax = 0.0;
+  // The second pass keeps its own loops although it has the shape of an rv_cells callback: as one, the compiler fuses
+  // vx * c + vy * s the other way round on the gidx path (fma(vy, s, vx c) for fma(vx, c, vy s)), and the residuals
+  // and predictions change in the last bit.
   auto acc2 = [&](long long i, double w, double c, double s, double yi) {
     const double pr = k * (vx * c + vy * s);
     const double r = yi - pr;
@@ -138,35 +125,37 @@ __global__ __launch_bounds__(512) void k_velocity(const double* __restrict__ az,
     if (pred) pred[i] = pr;
   };
   if (tab) {
-    if (!grp || r2m < 0.0 || resid || pred) {
-      for (long long i0 = b + threadIdx.x; i0 < e; i0 += step) {
+    if (r2m < 0.0 || resid || pred) {
+      for (long long i0 = b + threadIdx.x; i0 < e; i0 += (long long)kVelThreads * kVelU) {
         int gv[kVelU];
         double yv[kVelU];
         unsigned mv[kVelU];
-        vel_load(i0, e, blockDim.x, gidx, y, amask, gv, yv, mv);
+        vel_load(i0, e, kVelThreads, gidx, y, amask, gv, yv, mv);
 #pragma unroll
         for (int u = 0; u < kVelU; ++u)
-          if (i0 + (long long)u * blockDim.x < e)
-            acc2(i0 + (long long)u * blockDim.x, (double)__popc(mv[u]), cs_tab[gv[u]], cs_tab[G + gv[u]], yv[u]);
+          if (i0 + (long long)u * kVelThreads < e)
+            acc2(i0 + (long long)u * kVelThreads, (double)__popc(mv[u]), cs_tab[gv[u]], cs_tab[G + gv[u]], yv[u]);
       }
     }
-    if (grp) rmax = 0.0;  // from the per-group extremes (same values as the per-cell maximum)
-    for (int g = threadIdx.x; grp && g < G; g += blockDim.x) {
-      const unsigned long long hi = ymx[g];
-      if (hi == 0ull) continue;
-      const double pr = k * (vx * cs_tab[g] + vy * cs_tab[G + g]);
-      rmax = fmax(rmax, fmax(fabs(unkey(ymn[g]) - pr), fabs(unkey(hi) - pr)));
-    }
   } else {
-    for (long long i = b + threadIdx.x; i < e; i += blockDim.x) {
+    for (long long i = b + threadIdx.x; i < e; i += kVelThreads) {
       double s, c;
       sincos(az[i], &s, &c);
       acc2(i, amask ? (double)__popc(amask[i]) : 1.0, c, s, y[i]);
     }
   }
-  const double R2s = block_sum(r2, sh, (int)(blockDim.x >> 6));
+  if (tab) {
+    rmax = 0.0;  // from the per-group extremes (same values as the per-cell maximum)
+    for (int g = threadIdx.x; g < G; g += kVelThreads) {
+      const unsigned long long hi = ymx[g];
+      if (hi == 0ull) continue;
+      const double pr = k * (vx * cs_tab[g] + vy * cs_tab[G + g]);
+      rmax = fmax(rmax, fmax(fabs(unkey(ymn[g]) - pr), fabs(unkey(hi) - pr)));
+    }
+  }
+  const double R2s = block_sum(r2, red, kVelWaves);
   const double R2 = r2m >= 0.0 ? r2m : R2s;
-  const double RM = block_max(rmax, sh);
+  const double RM = block_max(rmax, red);
   if (threadIdx.x == 0) {
     double* o = out + f * 8;
     o[0] = vx;
@@ -180,13 +169,11 @@ __global__ __launch_bounds__(512) void k_velocity(const double* __restrict__ az,
   }
 }
 
-hipError_t launch_velocity(hipStream_t st, const double* az, const int* gidx, const double* az_table, int G,
-                           const double* y, const unsigned* amask, const long long* seg, long long n, int F, double k, double ridge,
-                           const double* bounds4, double* out, double* resid, double* pred) {
-  if (F <= 0) return hipSuccess;
-  const size_t lds = gidx ? sizeof(double) * 4 * (size_t)G : 0;
-  hipLaunchKernelGGL(k_velocity, dim3(F), dim3(512), lds, st, az, gidx, az_table, G, y, amask, seg, n, k, ridge,
-                     bounds4[0], bounds4[1], bounds4[2], bounds4[3], out, resid, pred);
+hipError_t launch_velocity(hipStream_t st, const VelProblem& p, double* out, double* resid, double* pred) {
+  if (p.F <= 0) return hipSuccess;
+  const size_t lds = p.gidx ? sizeof(double) * 4 * (size_t)p.G : 0;
+  hipLaunchKernelGGL(k_velocity, dim3(p.F), dim3(kVelThreads), lds, st, p.az, p.gidx, p.az_table, p.G, p.y, p.amask,
+                     p.seg, p.n, p.k, p.ridge, p.lx, p.hx, p.ly, p.hy, out, resid, pred);
   return hipGetLastError();
 }
 

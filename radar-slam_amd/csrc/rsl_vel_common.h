@@ -1,7 +1,18 @@
 // rsl_vel_common.h — what the velocity solvers share (k_velocity in rsl_vel.hip, k_velocity_robust in
-// rsl_vel_robust.hip, k_velocity_consensus in rsl_vel_consensus.hip): the cell loader, the workgroup sums, the
-// quadratic cost and the 2x2 box solve.  The robust solver starts from k_velocity's solution, and the consensus solver
-// falls back on it; all take it from these functions, in the same order of operations.
+// rsl_vel_robust.hip, k_velocity_consensus in rsl_vel_consensus.hip), each step said once:
+//   block_sum      one workgroup sum (k_velocity's R2; rsl_aux.hip has uses of its own)
+//   vel_load       kVelU cells of one thread, all loads issued first
+//   vel_moments    one cell into the 7 moments [n, cc, cs, ss, cy, sy, yy]
+//   vel_frame      the frame prologue: the cos / sin table in LDS and the frame's clamped cell range (k_velocity and
+//                  k_velocity_robust; k_velocity_consensus keeps these lines open-coded and says why)
+//   qcost, box_solve, vel_solve_bcast   the quadratic cost, the 2x2 box solve, and thread 0's solve into LDS
+//   rv_cells       the cell loop of a pass (grid-index or azimuth path) around a callback
+//   rv_resid       the residual of a cell, with explicit fma
+//   rv_reduce7     7 workgroup sums in one pass
+// The robust solver starts from k_velocity's solution, and the consensus solver falls back on it; all take it from these
+// functions, in the same order of operations.  Every helper is force-inlined and holds the expression text of the
+// kernels it came from: under fp-contract the compiler picks per kernel which products it fuses into an fma, so a
+// helper that is rewritten (an explicit fma, other brackets) may change a kernel's last bit.
 #pragma once
 #include "rsl_common.h"
 
@@ -19,17 +30,6 @@ RSL_DEV double block_sum(double v, double* sh, int nw) {
     for (int w = 0; w < nw; ++w) r += sh[w];
   __syncthreads();
   return r;  // valid on thread 0
-}
-
-// The 7 moment sums [n, cc, cs, ss, cy, sy, yy] of a pass into mom, each a block_sum.  mom is written by thread 0:
-// a barrier comes before any other thread reads it.  (k_velocity_robust adds in the same order in one pass over 56
-// doubles of LDS: rv_reduce7.)
-RSL_DEV void block_sum7(const double (&v)[7], double* sh, double* mom) {
-  const int nw = (int)(blockDim.x >> 6);  // read once: not again between each sum's barriers
-  for (int q = 0; q < 7; ++q) {
-    const double r = block_sum(v[q], sh, nw);
-    if (threadIdx.x == 0) mom[q] = r;
-  }
 }
 
 constexpr int kVelU = 8;
@@ -53,6 +53,32 @@ RSL_DEV void vel_load(long long i0, long long e, unsigned stride, const int* __r
       mv[u] = 0u;
     }
   }
+}
+
+// One cell of weight w, direction (c, s) and phase yi into the 7 moments v = [n, cc, cs, ss, cy, sy, yy].
+RSL_DEV void vel_moments(double (&v)[7], double w, double c, double s, double yi) {
+  v[0] += w;
+  v[1] += w * c * c;
+  v[2] += w * c * s;
+  v[3] += w * s * s;
+  v[4] += w * c * yi;
+  v[5] += w * s * yi;
+  v[6] += w * yi * yi;
+}
+
+// Frame prologue of a workgroup of kThreads.  gidx path (tab, the kernel's own flag: passing the pointer instead
+// changes the register allocation of the whole kernel): cs_tab[0..G) = cos, cs_tab[G..2G) = sin of the grid azimuths,
+// then a barrier.  Returns the cells [b, e) of frame f, both ends clamped to nmax, the arrays' length (an overflowed
+// capacity-sized list ends at its capacity).
+template <int kThreads>
+RSL_DEV void vel_frame(bool tab, const double* az_table, int G, const long long* seg, long long nmax, long f,
+                       double* cs_tab, long long& b, long long& e) {
+  if (tab) {
+    for (int g = threadIdx.x; g < G; g += kThreads) sincos(az_table[g], &cs_tab[G + g], &cs_tab[g]);
+    __syncthreads();
+  }
+  b = seg[f] < nmax ? seg[f] : nmax;
+  e = seg[f + 1] < nmax ? seg[f + 1] : nmax;
 }
 
 RSL_DEV double qcost(double vx, double vy, double k, double ridge, const double* m) {
@@ -103,10 +129,21 @@ RSL_DEV double2 box_solve(const double* m, double k, double ridge, double lx, do
   return make_double2(bx, by);
 }
 
-// -- what the iterating solvers share (k_velocity_robust, k_velocity_consensus): one workgroup of kThreads per frame ----
+// Thread 0: the box solve on the moments mom into bc[0..1].  The barrier that publishes bc is the caller's: each call
+// site orders different reads with it.
+RSL_DEV void vel_solve_bcast(const double* mom, double k, double ridge, double lx, double hx, double ly, double hy,
+                             double* bc) {
+  if (threadIdx.x == 0) {
+    const double2 x = box_solve(mom, k, ridge, lx, hx, ly, hy);
+    bc[0] = x.x;
+    bc[1] = x.y;
+  }
+}
+
+// -- the passes over a frame's cells: one workgroup of kThreads per frame ---------------------------------------------
 
 // fn(i, ok, m, c, s, y) for the cells of [b, e) owned by this thread; gidx path: cells past e come as ok = false with
-// m = 0, y = 0 (they add 0 to every sum, as in k_velocity).
+// m = 0, y = 0 (they add 0 to every sum).
 template <int kThreads, class Fn>
 RSL_DEV void rv_cells(const double* __restrict__ az, const int* __restrict__ gidx, const double* __restrict__ y,
                       const unsigned* __restrict__ amask, const double* cs_tab, int G, long long b, long long e,
@@ -140,8 +177,8 @@ RSL_DEV double rv_resid(double yi, double k, double vx, double vy, double c, dou
 
 // Sums of 7 values over the workgroup into mom[0..6], in block_sum's order (wave shuffle tree, then the waves in order
 // on thread 0) with all 7 in one pass: 2 barriers instead of 21.  red: [kThreads / 64 * 7] doubles of LDS.  Valid for
-// every thread on return.  Kept beside block_sum7 (8 doubles of LDS, k_velocity's): with 7 x block_sum here the Huber
-// solve at a fixed scale took 2.376 instead of 2.210 ms per 2000 cfg2 frames.
+// every thread on return.  With 7 x block_sum here the Huber solve at a fixed scale took 2.376 instead of 2.210 ms per
+// 2000 cfg2 frames.
 template <int kThreads>
 RSL_DEV void rv_reduce7(double (&v)[7], double* red, double* mom) {
   const int t = threadIdx.x;

@@ -11,9 +11,9 @@
 // in chunks of kCvChunk as (c, s, y, m) through the shared cell loader, and every lane walks the chunk reading the same
 // LDS address (a broadcast: no bank conflict), so the cells are streamed from memory once for all hypotheses and there
 // is no per-hypothesis reduction.  The winner is one workgroup-wide max over the 64-bit key (count + 1, hyps - 1 - h);
-// an invalid hypothesis has key 0.  The LS fallback, the refinement passes and the output pass are the loader, the
-// residual and the 7-sum reduction of k_velocity_robust (rsl_vel_common.h); every pass, scoring included, evaluates
-// the residual with the one rv_resid, so score, refinement and output see the same bits for a cell.
+// an invalid hypothesis has key 0.  The loader, moments, residual, 7-sum reduction and box solve of the LS fallback,
+// the refinement passes and the output pass are rsl_vel_common.h's; every pass, scoring included, evaluates the
+// residual with the one rv_resid, so score, refinement and output see the same bits for a cell.
 //
 // Scoring is bound by fp64 VALU issue (mul + 2 fma + compare per cell and hypothesis), not by memory.  Measured on
 // 2000 cfg2 frames of 35.5 k cells: 4.17 / 4.53 / 12.3 ms at 64 / 256 / 1024 hypotheses, against 2.39 ms
@@ -74,6 +74,8 @@ __global__ __launch_bounds__(kCvThreads) void k_velocity_consensus(
   double* ly_ = wk + kCvY;
   int* lm = reinterpret_cast<int*>(wk + kCvM);
   const int t = threadIdx.x;
+  // vel_frame's text, open-coded: this kernel keeps wave-uniform values in VGPR lanes, and with the prologue inlined
+  // from the helper the compiler places them differently throughout (the other two kernels compile as before with it)
   if (tab) {
     for (int g = t; g < G; g += kCvThreads) sincos(az_table[g], &cs_tab[G + g], &cs_tab[g]);
     __syncthreads();
@@ -201,21 +203,10 @@ __global__ __launch_bounds__(kCvThreads) void k_velocity_consensus(
     double v[7] = {0, 0, 0, 0, 0, 0, 0};
     rv_cells<kCvThreads>(az, gidx, y, amask, cs_tab, G, b, e,
                          [&](long long, bool, int m, double c, double s, double yi) {
-                           const double w = (double)m;
-                           v[0] += w;
-                           v[1] += w * c * c;
-                           v[2] += w * c * s;
-                           v[3] += w * s * s;
-                           v[4] += w * c * yi;
-                           v[5] += w * s * yi;
-                           v[6] += w * yi * yi;
+                           vel_moments(v, (double)m, c, s, yi);
                          });
     rv_reduce7<kCvThreads>(v, red, mom);
-    if (t == 0) {
-      const double2 x = box_solve(mom, k, ridge, lx, hx, ly, hy);
-      bc[0] = x.x;
-      bc[1] = x.y;
-    }
+    vel_solve_bcast(mom, k, ridge, lx, hx, ly, hy, bc);
   }
   __syncthreads();
   double vx = bc[0], vy = bc[1];
@@ -226,21 +217,11 @@ __global__ __launch_bounds__(kCvThreads) void k_velocity_consensus(
     rv_cells<kCvThreads>(az, gidx, y, amask, cs_tab, G, b, e,
                          [&](long long, bool, int m, double c, double s, double yi) {
                            const double w = fabs(rv_resid(yi, k, vx, vy, c, s)) <= tc ? (double)m : 0.0;
-                           v[0] += w;
-                           v[1] += w * c * c;
-                           v[2] += w * c * s;
-                           v[3] += w * s * s;
-                           v[4] += w * c * yi;
-                           v[5] += w * s * yi;
-                           v[6] += w * yi * yi;
+                           vel_moments(v, w, c, s, yi);
                          });
     rv_reduce7<kCvThreads>(v, red, mom);  // its first barrier also orders the reads of bc above before the write below
     if (!(mom[0] != 0.0)) break;          // no inlier: keep x
-    if (t == 0) {
-      const double2 x = box_solve(mom, k, ridge, lx, hx, ly, hy);
-      bc[0] = x.x;
-      bc[1] = x.y;
-    }
+    vel_solve_bcast(mom, k, ridge, lx, hx, ly, hy, bc);
     __syncthreads();
     vx = bc[0];
     vy = bc[1];
@@ -277,18 +258,16 @@ __global__ __launch_bounds__(kCvThreads) void k_velocity_consensus(
 
 }  // namespace
 
-hipError_t launch_velocity_consensus(hipStream_t st, const double* az, const int* gidx, const double* az_table, int G,
-                                     const double* y, const unsigned* amask, const long long* seg, long long n, int F,
-                                     double k, double ridge, const double* bounds4, double c, double scale, int hyps,
+hipError_t launch_velocity_consensus(hipStream_t st, const VelProblem& p, double c, double scale, int hyps,
                                      double min_det, int refine, unsigned long long seed, long long frame0, double* out,
                                      float* weight, double* resid) {
-  if (F <= 0) return hipSuccess;
-  const size_t lds = sizeof(double) * ((gidx ? 2 * (size_t)G : 0) + kCvLds);
+  if (p.F <= 0) return hipSuccess;
+  const size_t lds = sizeof(double) * ((p.gidx ? 2 * (size_t)p.G : 0) + kCvLds);
   const int per = (hyps + kCvThreads - 1) / kCvThreads;
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(F), dim3(kCvThreads), lds, st, az, gidx, az_table, G, y, amask, seg, n, k, ridge,
-                       bounds4[0], bounds4[1], bounds4[2], bounds4[3], c * scale, hyps, min_det, refine,
-                       (unsigned)seed, (unsigned)(seed >> 32), frame0, out, weight, resid);
+    hipLaunchKernelGGL(kern, dim3(p.F), dim3(kCvThreads), lds, st, p.az, p.gidx, p.az_table, p.G, p.y, p.amask, p.seg,
+                       p.n, p.k, p.ridge, p.lx, p.hx, p.ly, p.hy, c * scale, hyps, min_det, refine, (unsigned)seed,
+                       (unsigned)(seed >> 32), frame0, out, weight, resid);
   };
   // hypotheses per thread, in registers: the smallest instantiation that holds hyps
   if (per <= 1)

@@ -12,8 +12,8 @@
 // scale costs 1 pass per iteration, the estimated scale 4; the LS start and the output pass add 2.  The workgroup
 // re-reads its own lines, so all passes after the first are served by L2 / Infinity Cache.
 //
-// The start comes from k_velocity's own source: the cell loader and the 2x2 box solve are the functions k_velocity
-// calls, and rv_reduce7 adds in block_sum's order (rsl_vel_common.h).  Same source, not guaranteed the same bits:
+// The start comes from k_velocity's own source: the frame prologue, the cell loader, the moments, the reduction and the
+// 2x2 box solve are the helpers of rsl_vel_common.h in both kernels.  Same source, not guaranteed the same bits:
 // under fp-contract the compiler chooses per kernel which products it fuses into an fma, so the two starts may differ
 // in the last place (tests/test_gpu_vel_robust.py::test_ls_equivalence holds them within 1e-13).
 #include "rsl_common.h"
@@ -76,36 +76,21 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
   u64* wtot = reinterpret_cast<u64*>(wk + kRvWtot);
   u64* hist = reinterpret_cast<u64*>(wk + kRvHist);
   const int t = threadIdx.x;
-  if (tab) {
-    for (int g = t; g < G; g += kRvThreads) sincos(az_table[g], &cs_tab[G + g], &cs_tab[g]);
-    __syncthreads();
-  }
   const long f = blockIdx.x;
-  const long long b = seg[f] < nmax ? seg[f] : nmax, e = seg[f + 1] < nmax ? seg[f + 1] : nmax;
+  long long b, e;
+  vel_frame<kRvThreads>(tab, az_table, G, seg, nmax, f, cs_tab, b, e);
 
   // x0: the plain LS solve of k_velocity
   {
     double v[7] = {0, 0, 0, 0, 0, 0, 0};
     rv_cells<kRvThreads>(az, gidx, y, amask, cs_tab, G, b, e,
                          [&](long long, bool, int m, double c, double s, double yi) {
-      const double w = (double)m;
-      v[0] += w;
-      v[1] += w * c * c;
-      v[2] += w * c * s;
-      v[3] += w * s * s;
-      v[4] += w * c * yi;
-      v[5] += w * s * yi;
-      v[6] += w * yi * yi;
+      vel_moments(v, (double)m, c, s, yi);
     });
     rv_reduce7<kRvThreads>(v, red, mom);
   }
   const double W = mom[0];  // sum of the multiplicities: an exact integer
-  auto solve = [&]() {  // thread 0: the box solve on the moments, broadcast through bc
-    const double2 x = box_solve(mom, k, ridge, lx, hx, ly, hy);
-    bc[0] = x.x;
-    bc[1] = x.y;
-  };
-  if (t == 0) solve();
+  vel_solve_bcast(mom, k, ridge, lx, hx, ly, hy, bc);
   __syncthreads();
   double vx = bc[0], vy = bc[1];
 
@@ -182,20 +167,14 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
     rv_cells<kRvThreads>(az, gidx, y, amask, cs_tab, G, b, e,
                          [&](long long, bool, int m, double c, double s, double yi) {
       const double w = m == 0 ? 0.0 : (double)m * rv_weight(loss, fabs(rv_resid(yi, k, vx, vy, c, s)), tc);
-      v[0] += w;
-      v[1] += w * c * c;
-      v[2] += w * c * s;
-      v[3] += w * s * s;
-      v[4] += w * c * yi;
-      v[5] += w * s * yi;
-      v[6] += w * yi * yi;
+      vel_moments(v, w, c, s, yi);
     });
     rv_reduce7<kRvThreads>(v, red, mom);
     if (!(mom[0] != 0.0)) {  // every weight is 0: keep x
       conv = true;
       break;
     }
-    if (t == 0) solve();
+    vel_solve_bcast(mom, k, ridge, lx, hx, ly, hy, bc);
     __syncthreads();
     const double nx = bc[0], ny = bc[1];
     const double dx = fmax(fabs(nx - vx), fabs(ny - vy));
@@ -238,14 +217,12 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
   }
 }
 
-hipError_t launch_velocity_robust(hipStream_t st, const double* az, const int* gidx, const double* az_table, int G,
-                                  const double* y, const unsigned* amask, const long long* seg, long long n, int F,
-                                  double k, double ridge, const double* bounds4, int loss, double c, double scale,
-                                  int iters, double tol, double* out, float* weight, double* resid) {
-  if (F <= 0) return hipSuccess;
-  const size_t lds = sizeof(double) * ((gidx ? 2 * (size_t)G : 0) + kRvLds);
-  hipLaunchKernelGGL(k_velocity_robust, dim3(F), dim3(kRvThreads), lds, st, az, gidx, az_table, G, y, amask, seg, n, k,
-                     ridge, bounds4[0], bounds4[1], bounds4[2], bounds4[3], loss, c, scale, iters, tol, out, weight,
+hipError_t launch_velocity_robust(hipStream_t st, const VelProblem& p, int loss, double c, double scale, int iters,
+                                  double tol, double* out, float* weight, double* resid) {
+  if (p.F <= 0) return hipSuccess;
+  const size_t lds = sizeof(double) * ((p.gidx ? 2 * (size_t)p.G : 0) + kRvLds);
+  hipLaunchKernelGGL(k_velocity_robust, dim3(p.F), dim3(kRvThreads), lds, st, p.az, p.gidx, p.az_table, p.G, p.y,
+                     p.amask, p.seg, p.n, p.k, p.ridge, p.lx, p.hx, p.ly, p.hy, loss, c, scale, iters, tol, out, weight,
                      resid);
   return hipGetLastError();
 }

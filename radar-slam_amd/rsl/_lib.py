@@ -35,6 +35,9 @@ K_NAMES = ['range_fft', 'doppler_fft', 'detect', 'offsets', 'emit', 'doa_scan', 
            'velocity', 'aux']
 
 _P = c_void_p
+# the handle and the problem the three velocity solvers share: az, gidx, az_table, G, y, amask, seg, n, F, k, ridge,
+# bounds4
+_VEL = [_P, _P, _P, _P, c_int, _P, _P, _P, c_longlong, c_int, c_double, c_double, POINTER(c_double)]
 # name -> (restype, argtypes); must mirror include/rsl.h (tests/test_abi.py checks both directions)
 SIGNATURES = {
     'rsl_version': (c_int, []),
@@ -75,13 +78,10 @@ SIGNATURES = {
     'rsl_cell_extras': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_longlong, c_double, _P, _P, _P, _P,
                                 _P, _P]),
     'rsl_confidence': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_longlong, _P, _P, _P, _P]),
-    'rsl_velocity': (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_longlong, c_int, c_double, c_double,
-                             POINTER(c_double), _P, _P, _P]),
-    'rsl_velocity_robust': (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_longlong, c_int, c_double, c_double,
-                                    POINTER(c_double), c_int, c_double, c_double, c_int, c_double, _P, _P, _P]),
-    'rsl_velocity_consensus': (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_longlong, c_int, c_double, c_double,
-                                       POINTER(c_double), c_double, c_double, c_int, c_double, c_int, c_ulonglong,
-                                       c_longlong, _P, _P, _P]),
+    'rsl_velocity': (c_int, _VEL + [_P, _P, _P]),
+    'rsl_velocity_robust': (c_int, _VEL + [c_int, c_double, c_double, c_int, c_double, _P, _P, _P]),
+    'rsl_velocity_consensus': (c_int, _VEL + [c_double, c_double, c_int, c_double, c_int, c_ulonglong, c_longlong,
+                                              _P, _P, _P]),
     'rsl_preprocess_rows': (c_int, [_P, _P, c_longlong, c_int, _P, c_int, _P]),
     'rsl_phase_model': (c_int, [_P, _P, _P, c_longlong, _P, c_double, _P, c_int, c_double, _P, _P, _P]),
     'rsl_associate': (c_int, [_P, _P, c_int, _P, c_int, c_double, _P, _P, _P]),

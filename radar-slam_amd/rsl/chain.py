@@ -359,24 +359,23 @@ class RadarChain:
         if self.ra is not None:
             ctx.range_cov(self.rds, self.ra_win, out=self.ra_cov)
             ctx.range_azimuth(self.ra_cov, self.ra_steer, cfg.ra_map, loading=cfg.ra_loading, out=self.ra)
-        if velocity and cfg.velocity_loss == 'consensus':
+        if not velocity:
+            return
+        # the problem the three solvers share: the chain's own lists, on the grid-index path
+        prob = dict(az=None, y=self.ext['phase'], seg=self.offs['cell_base'], k=self.k, ridge=cfg.ridge,
+                    bounds=cfg.bounds, amask=L['c_amask'], out=self.vel, gidx=self.gidx, az_table=self.az_table,
+                    n=self.cell_cap)
+        if cfg.velocity_loss == 'consensus':
             # vel columns 2-7 become {cost, rmse_in, n_in, n, best_h, n_valid} (include/rsl.h)
-            ctx.velocity_consensus(None, self.ext['phase'], self.offs['cell_base'], k=self.k, scale=cfg.velocity_scale,
-                                   c=cfg.velocity_c, hyps=cfg.velocity_hyps, min_det=cfg.velocity_min_det,
-                                   refine=cfg.velocity_refine, seed=cfg.velocity_seed, frame0=0, ridge=cfg.ridge,
-                                   bounds=cfg.bounds, amask=L['c_amask'], out=self.vel, gidx=self.gidx,
-                                   az_table=self.az_table, n=self.cell_cap, want_weight=self.vel_weight)
-        elif velocity and cfg.velocity_loss != 'ls':
+            ctx.velocity_consensus(**prob, scale=cfg.velocity_scale, c=cfg.velocity_c, hyps=cfg.velocity_hyps,
+                                   min_det=cfg.velocity_min_det, refine=cfg.velocity_refine, seed=cfg.velocity_seed,
+                                   frame0=0, want_weight=self.vel_weight)
+        elif cfg.velocity_loss != 'ls':
             # vel columns 2-7 become {cost, rmse_w, n_in, n, sigma, it} (include/rsl.h)
-            ctx.velocity_robust(None, self.ext['phase'], self.offs['cell_base'], k=self.k, loss=cfg.velocity_loss,
-                                c=cfg.velocity_c, scale=cfg.velocity_scale, iters=cfg.velocity_iters,
-                                tol=cfg.velocity_tol, ridge=cfg.ridge, bounds=cfg.bounds, amask=L['c_amask'],
-                                out=self.vel, gidx=self.gidx, az_table=self.az_table, n=self.cell_cap,
-                                want_weight=self.vel_weight)
-        elif velocity:
-            ctx.velocity(None, self.ext['phase'], self.offs['cell_base'], k=self.k, ridge=cfg.ridge,
-                         bounds=cfg.bounds, amask=L['c_amask'], out=self.vel, gidx=self.gidx, az_table=self.az_table,
-                         n=self.cell_cap)
+            ctx.velocity_robust(**prob, loss=cfg.velocity_loss, c=cfg.velocity_c, scale=cfg.velocity_scale,
+                                iters=cfg.velocity_iters, tol=cfg.velocity_tol, want_weight=self.vel_weight)
+        else:
+            ctx.velocity(**prob)
 
     def totals(self):
         eb = self.offs['entry_base'][self.F].item()

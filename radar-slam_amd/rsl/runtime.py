@@ -543,17 +543,28 @@ class Context:
         return match, dist, phase
 
     # -- a25-a29 ---------------------------------------------------------------------------------
-    def velocity(self, az, y, seg, *, k: float, ridge: float = 0.0, bounds=(-50.0, 50.0, -50.0, 50.0),
-                 amask=None, want_resid=False, out=None, gidx=None, az_table=None, n=None):
-        """n: the per-target arrays' length (default len(y)); the segments in seg are clamped to it."""
+    def _vel_problem(self, y, seg, n, az_table, bounds, out, want_weight, want_resid):
+        """What the three velocity solvers derive from their shared inputs: F, N (n, default len(y), clamped to it), G,
+        the box as c_double[4], the row buffer, and the optional weight (want_weight: True, or a device f32 [N] buffer
+        to fill) and resid buffers."""
         torch = self.torch
         F = int(seg.shape[0]) - 1
         o = out if out is not None else self.empty((max(F, 1), 8), torch.float64)
         N = int(y.shape[0]) if n is None else min(int(n), int(y.shape[0]))
         G = int(az_table.shape[0]) if az_table is not None else 0
+        if want_weight is True:
+            weight = self.empty((max(N, 1),), torch.float32)
+        else:
+            weight = None if want_weight is False or want_weight is None else want_weight
         resid = self.empty((max(N, 1),), torch.float64) if want_resid else None
-        pred = self.empty((max(N, 1),), torch.float64) if want_resid else None
         b4 = (c_double * 4)(*[float(x) for x in bounds])
+        return F, N, G, b4, o, weight, resid
+
+    def velocity(self, az, y, seg, *, k: float, ridge: float = 0.0, bounds=(-50.0, 50.0, -50.0, 50.0),
+                 amask=None, want_resid=False, out=None, gidx=None, az_table=None, n=None):
+        """n: the per-target arrays' length (default len(y)); the segments in seg are clamped to it."""
+        F, N, G, b4, o, _, resid = self._vel_problem(y, seg, n, az_table, bounds, out, False, want_resid)
+        pred = self.empty((max(N, 1),), self.torch.float64) if want_resid else None
         self._bind()
         self.check(self.lib.rsl_velocity(self.h, _ptr(az), _ptr(gidx), _ptr(az_table), G, _ptr(y), _ptr(amask),
                                          _ptr(seg), N, F, float(k), float(ridge), b4, _ptr(o), _ptr(resid), _ptr(pred)),
@@ -568,7 +579,6 @@ class Context:
         estimated per iteration from the residuals' weighted median (dependable only below roughly 30 % coherent
         outliers; pass the sensor's phase-noise sigma where it is known).  want_weight: True, or a device f32 [N]
         buffer to fill.  Returns (out f64 [F, 8], weight f32 [N] or None, resid f64 [N] or None)."""
-        torch = self.torch
         if isinstance(loss, str):
             if loss not in _lib.LOSS_IDS:
                 raise ValueError(f"loss must be 'huber' or 'tukey', not {loss!r}")
@@ -576,16 +586,7 @@ class Context:
         loss = int(loss)
         if c is None:
             c = _lib.LOSS_DEFAULT_C.get(loss, 1.0)  # an unknown id is rejected by the library
-        F = int(seg.shape[0]) - 1
-        o = out if out is not None else self.empty((max(F, 1), 8), torch.float64)
-        N = int(y.shape[0]) if n is None else min(int(n), int(y.shape[0]))
-        G = int(az_table.shape[0]) if az_table is not None else 0
-        if want_weight is True:
-            weight = self.empty((max(N, 1),), torch.float32)
-        else:
-            weight = None if want_weight is False or want_weight is None else want_weight
-        resid = self.empty((max(N, 1),), torch.float64) if want_resid else None
-        b4 = (c_double * 4)(*[float(x) for x in bounds])
+        F, N, G, b4, o, weight, resid = self._vel_problem(y, seg, n, az_table, bounds, out, want_weight, want_resid)
         self._bind()
         self.check(self.lib.rsl_velocity_robust(self.h, _ptr(az), _ptr(gidx), _ptr(az_table), G, _ptr(y), _ptr(amask),
                                                 _ptr(seg), N, F, float(k), float(ridge), b4, loss, float(c),
@@ -605,26 +606,16 @@ class Context:
         winner's inliers.  want_weight: True, or a device f32 [N] buffer to fill with the inlier mask.  Returns
         (out f64 [F, 8] = {v_x, v_y, cost, rmse_in, n_in, n, best_h, n_valid}, weight f32 [N] or None, resid f64 [N]
         or None)."""
-        torch = self.torch
         if scale is None:
             raise ValueError('velocity_consensus needs scale, the phase-noise sigma in radians')
         if c is None:
             c = _lib.CONSENSUS_DEFAULT_C
-        F = int(seg.shape[0]) - 1
-        o = out if out is not None else self.empty((max(F, 1), 8), torch.float64)
-        N = int(y.shape[0]) if n is None else min(int(n), int(y.shape[0]))
-        G = int(az_table.shape[0]) if az_table is not None else 0
-        if want_weight is True:
-            weight = self.empty((max(N, 1),), torch.float32)
-        else:
-            weight = None if want_weight is False or want_weight is None else want_weight
-        resid = self.empty((max(N, 1),), torch.float64) if want_resid else None
-        b4 = (c_double * 4)(*[float(x) for x in bounds])
         seed, frame0 = int(seed), int(frame0)
         if not 0 <= seed < 2 ** 64:
             raise ValueError(f'seed must lie in [0, 2^64), not {seed!r}')
         if not -2 ** 63 <= frame0 < 2 ** 63:
             raise ValueError(f'frame0 must fit 64 bits, not {frame0!r}')
+        F, N, G, b4, o, weight, resid = self._vel_problem(y, seg, n, az_table, bounds, out, want_weight, want_resid)
         self._bind()
         self.check(self.lib.rsl_velocity_consensus(self.h, _ptr(az), _ptr(gidx), _ptr(az_table), G, _ptr(y),
                                                    _ptr(amask), _ptr(seg), N, F, float(k), float(ridge), b4, float(c),

@@ -82,3 +82,33 @@ def test_velocity_grid_path(ridge):
         sl = slice(seg[f], seg[f + 1])
         r = yf - K * (v[0] * np.cos(grid[gf]) + v[1] * np.sin(grid[gf]))
         assert np.allclose(res[sl], r, rtol=0, atol=1e-10)
+
+
+def test_bad_arguments(ctx):
+    """rsl_velocity's checks are those of the other two solvers: the ridge (a NaN too, and also for an empty batch),
+    the grid table, the cell path and the box."""
+    torch = ctx.torch
+    nan = float('nan')
+    n = 40
+    y = torch.zeros((n,), dtype=torch.float64, device=ctx.device)
+    gidx = torch.zeros((n,), dtype=torch.int32, device=ctx.device)
+    tab = ctx.to_dev(np.radians(np.linspace(-90.0, 90.0, 361)))
+    big = torch.zeros((2049,), dtype=torch.float64, device=ctx.device)
+    seg = ctx.to_dev(np.array([0, n], np.int64))
+    seg0 = ctx.to_dev(np.array([0], np.int64))  # an empty batch
+    good = dict(k=K, gidx=gidx, az_table=tab)
+    for bad in (dict(ridge=-1.0), dict(ridge=nan), dict(az_table=None), dict(az_table=big),
+                dict(gidx=None, az_table=None),
+                dict(bounds=(nan, 50.0, -50.0, 50.0)), dict(bounds=(-50.0, 50.0, -50.0, nan)),
+                dict(bounds=(1.0, -1.0, -50.0, 50.0)), dict(bounds=(-50.0, 50.0, 1.0, -1.0))):
+        with pytest.raises(ValueError):
+            ctx.velocity(None, y, seg, **{**good, **bad})
+    for ridge in (-1.0, nan):
+        with pytest.raises(ValueError):
+            ctx.velocity(None, y, seg0, ridge=ridge, **good)
+    # a valid empty batch succeeds and writes nothing
+    o = torch.full((1, 8), nan, dtype=torch.float64, device=ctx.device)
+    ctx.velocity(None, y, seg0, out=o, **good)
+    ctx.velocity(y, y, seg, **{**good, 'gidx': None, 'az_table': None})  # the azimuth path alone is valid
+    torch.cuda.synchronize()
+    assert torch.isnan(o).all()

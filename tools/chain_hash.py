@@ -1,9 +1,10 @@
 """SHA-256 of every output of one cfg2 chain batch (RDS, masks, row counts, peak powers, offsets, lists, DoA, ESPRIT,
-phase, velocity), of the detectors the chain does not run (rsl_detect, rsl_detect_cfar and rsl_detect_oscfar on the
-chain's RDS; window (2, 2) / (8, 8), fixed alpha, rank 0.75) and of the
-DoA paths it does not run (f32 scans, spectra, smoothed MUSIC; on the first NDOA cells of the chain's list) under the
-library RSL_LIBRARY: equal hashes across two libraries = bit-identical chains.  cfg1 / cfg2 / cfg5 reach the packed
-kernels, gen32 the general fused tile body, gen64 the register body on padded rows, unf48 the unfused fall-back.
+phase, velocity), of the three velocity solvers on the chain's own lists (vel_hashes), of the detectors the chain does
+not run (rsl_detect, rsl_detect_cfar and rsl_detect_oscfar on the chain's RDS; window (2, 2) / (8, 8), fixed alpha,
+rank 0.75) and of the DoA paths it does not run (f32 scans, spectra, smoothed MUSIC; on the first NDOA cells of the
+chain's list) under the library RSL_LIBRARY: equal hashes across two libraries = bit-identical chains.  cfg1 / cfg2 /
+cfg5 reach the packed kernels, gen32 the general fused tile body, gen64 the register body on padded rows, unf48 the
+unfused fall-back.
 GPU box:  [CFG=cfg1|cfg2|cfg5|gen32|gen64|unf48] [F=frames] [NDOA=cells] RSL_LIBRARY=... python tools/chain_hash.py"""
 import hashlib
 import json
@@ -23,6 +24,52 @@ from bench import make_cubes  # noqa: E402
 # (antennas, chirps, chirp duration) by CFG name
 CONFIGS = {'cfg1': (8, 64, 25.6e-6), 'cfg2': (8, 128, 51.2e-6), 'cfg5': (16, 256, 102.4e-6), 'gen32': (4, 32, 12.8e-6),
            'gen64': (2, 64, 6.4e-6), 'unf48': (6, 48, 9.6e-6)}
+
+
+def vel_hashes(ctx, ch, nc, sha):
+    """The velocity family on the chain's lists: every solver, option and cell path, rows with weight / resid / pred."""
+    cfg, out = ch.cfg, {}
+    y, seg, am, N = ch.ext['phase'], ch.offs['cell_base'], ch.lists['c_amask'], ch.cell_cap
+    grid = dict(gidx=ch.gidx, az_table=ch.az_table, amask=am)
+    az = ch.az_table[ch.gidx.long().clamp(0, ch.az_table.shape[0] - 1)]
+    rows = ch.vel.cpu().numpy()
+    sigma = float(np.median(rows[:, 3]))  # the median LS rmse as the given scale
+    vmag = float(np.median(np.abs(rows[:, :2])))
+    tight = (-0.1 * vmag, 0.1 * vmag, -0.1 * vmag, 0.1 * vmag)  # the box is active in the typical frame
+
+    def put(name, res):
+        torch.cuda.synchronize()
+        o, a, b = res
+        out[name] = ':'.join([sha(o)] + [sha(t[:nc]) for t in (a, b) if t is not None])
+
+    def ls(name, az_, **kw):
+        put(name, ctx.velocity(az_, y, seg, k=ch.k, n=N, want_resid=True, **kw))
+
+    def robust(name, az_, **kw):
+        put(name, ctx.velocity_robust(az_, y, seg, k=ch.k, n=N, iters=30, want_weight=True, want_resid=True,
+                                      **{'ridge': cfg.ridge, 'bounds': cfg.bounds, 'tol': 1e-9, **kw}))
+
+    def consensus(name, az_, **kw):
+        put(name, ctx.velocity_consensus(az_, y, seg, k=ch.k, n=N, scale=sigma, seed=20240607, want_weight=True,
+                                         want_resid=True, **{'ridge': cfg.ridge, 'bounds': cfg.bounds, **kw}))
+
+    for ridge in (0.0, 0.01):
+        ls(f'v_ls_r{ridge}', None, ridge=ridge, bounds=cfg.bounds, **grid)
+    for loss in ('huber', 'tukey'):
+        for sname, scale in (('given', sigma), ('est', None)):
+            for tol in (1e-9, 0.0):
+                robust(f'v_{loss}_{sname}_tol{tol}', None, loss=loss, scale=scale, tol=tol, **grid)
+    for hyps in (64, 1024, 4096):
+        for refine in (0, 3):
+            consensus(f'v_cons_h{hyps}_r{refine}', None, hyps=hyps, refine=refine, **grid)
+    for mname, m in (('mask', am), ('nomask', None)):  # the azimuth path: sincos per cell, no grid table
+        ls(f'v_az_{mname}_ls', az, ridge=cfg.ridge, bounds=cfg.bounds, amask=m)
+        robust(f'v_az_{mname}_tukey', az, loss='tukey', scale=sigma, amask=m)
+        consensus(f'v_az_{mname}_cons', az, hyps=256, amask=m)
+    ls('v_box_ls', None, ridge=cfg.ridge, bounds=tight, **grid)
+    robust('v_box_huber', None, loss='huber', scale=sigma, bounds=tight, **grid)
+    consensus('v_box_cons', None, hyps=256, bounds=tight, **grid)
+    return out
 
 
 def main():
@@ -46,6 +93,7 @@ def main():
                     ('c_rc', ch.lists['c_rc'][:nc]), ('gidx', ch.gidx[:nc]), ('esprit', ch.ext['esprit'][:nc]),
                     ('phase', ch.ext['phase'][:nc]), ('vel', ch.vel)):
         out[name] = sha(t)
+    out.update(vel_hashes(ctx, ch, nc, sha))
 
     # The detectors the chain does not run, on the chain's RDS: mask, row counts and the row-compact peak powers'
     # prefix.
