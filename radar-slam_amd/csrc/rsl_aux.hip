@@ -11,9 +11,11 @@
 #include "rsl_common.h"
 #include "rsl_internal.h"
 #include "rsl_phase_common.h"
-#include "rsl_vel_common.h"
+#include "rsl_reduce.h"
 
 namespace rsl {
+
+constexpr int kAuxWaves = 256 / 64;  // every kernel of this file runs 256 threads
 
 __global__ __launch_bounds__(256) void k_preprocess_rows(const float2* __restrict__ in, int S,
                                                          const float2* __restrict__ table, int dc,
@@ -21,19 +23,19 @@ __global__ __launch_bounds__(256) void k_preprocess_rows(const float2* __restric
   const long r = blockIdx.x;
   const float2* src = in + (size_t)r * S;
   float2* dst = out + (size_t)r * S;
-  double ax = 0.0, ay = 0.0;  // fp64 mean accumulation
+  double a[2] = {0.0, 0.0};  // fp64 mean accumulation: re, im
   for (int s = threadIdx.x; s < S; s += 256) {
     const float2 v = cmul(src[s], table[s]);
     dst[s] = v;
-    ax += v.x;
-    ay += v.y;
+    a[0] += v.x;
+    a[1] += v.y;
   }
   if (!dc) return;
-  __shared__ double sh[4], mean[2];
-  const double sx = block_sum(ax, sh, 4), sy = block_sum(ay, sh, 4);
+  __shared__ double red[kAuxWaves * 2], mean[2];
+  wg_partials<Red::Sum>(a, red);
   if (threadIdx.x == 0) {
-    mean[0] = sx / S;
-    mean[1] = sy / S;
+    mean[0] = wg_fold<kAuxWaves, 2, Red::Sum>(red, 0, 0.0) / S;
+    mean[1] = wg_fold<kAuxWaves, 2, Red::Sum>(red, 1, 0.0) / S;
   }
   __syncthreads();
   const double mx = mean[0], my = mean[1];
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(256) void k_phase_model(const double* __restrict__ 
                                                      const double* __restrict__ y, int wrap, double ridge,
                                                      double* __restrict__ pred, double* __restrict__ resid,
                                                      double* __restrict__ cost_out) {
-  __shared__ double sh[4];
+  __shared__ double red[kAuxWaves];
   double acc = 0.0;
   for (long i = threadIdx.x; i < n; i += 256) {
     double J[6];
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(256) void k_phase_model(const double* __restrict__ 
       acc += r * r;
     }
   }
-  const double sum = block_sum(acc, sh, 4);
+  const double sum = wg_one<kAuxWaves, Red::Sum>(acc, red, 0.0);
   if (threadIdx.x == 0 && cost_out) {
     double reg = 0.0;
     for (int c = 0; c < 6; ++c) reg += x[c] * x[c];
@@ -126,22 +128,6 @@ RSL_DEV void solve_free(const double H[6][6], const double* g, const int* freev,
     for (int c = col + 1; c < nf; ++c) s -= M[col][c] * z[c];
     z[col] = s / M[col][col];
   }
-}
-
-// Sums of N values over the 256-thread workgroup into m[0..N-1] on thread 0, in block_sum's order (wave shuffle tree,
-// then the waves in order) with all N in one pass: 1 barrier, where N x block_sum takes 3 N (with 28 x block_sum
-// k_bvls took 49.8 instead of 47.6 us at 26 targets).
-template <int N>
-RSL_DEV void reduce(const double (&v)[N], double (*red)[N], double* m) {
-#pragma unroll
-  for (int c = 0; c < N; ++c) {
-    double s = v[c];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int c = 0; c < N; ++c) m[c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
 }
 
 // BVLS on the reduced moments m (21 of the upper triangle of J'J, then 6 of J'y; J scaled by k) over the first nv
@@ -232,8 +218,8 @@ __global__ __launch_bounds__(256) void k_bvls(const double* __restrict__ pos, co
                                               const double* __restrict__ y, double k, int nv, double ridge,
                                               const double* __restrict__ lo, const double* __restrict__ hi,
                                               double* __restrict__ out) {
-  __shared__ double red[4][27];
-  __shared__ double xs[6], sh[4];
+  __shared__ double red[kAuxWaves * 27];
+  __shared__ double xs[6];
   double acc[27];
   for (int c = 0; c < 27; ++c) acc[c] = 0.0;
   for (long i = threadIdx.x; i < n; i += 256) {
@@ -245,10 +231,12 @@ __global__ __launch_bounds__(256) void k_bvls(const double* __restrict__ pos, co
       for (int b = a; b < 6; ++b) acc[t++] += J[a] * J[b];  // 21
     for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * y[i];  // 6
   }
+  // all 27 in one pass, 1 barrier: with one-value sums, then of 3 barriers each, for these and the cost (28 in all)
+  // k_bvls took 49.8 instead of 47.6 us at 26 targets
   double m[27];
-  reduce<27>(acc, red, m);
+  wg_sums<kAuxWaves>(acc, red, m);
   if (threadIdx.x == 0) bvls_solve(m, nv, ridge, lo, hi, xs);
-  __syncthreads();
+  __syncthreads();  // publishes xs; red is free again for the cost's sum
   // The cost as the reference's sum of squares (step1_result.fun), in k_phase_model's operation order.  The moment form
   // y'y - 2 b.x + x'Hx cancels at a near-exact fit: its error is ~1e-15 y'y whatever the residual (-3e-8 ... +6e-8 was
   // returned at exact fits of 3 to 300 targets, where the sum of squares is ~1e-23).
@@ -261,7 +249,7 @@ __global__ __launch_bounds__(256) void k_bvls(const double* __restrict__ pos, co
     const double r = y[i] - p * k;
     q += r * r;
   }
-  const double sum = block_sum(q, sh, 4);
+  const double sum = wg_one<kAuxWaves, Red::Sum>(q, red, 0.0);
   if (threadIdx.x != 0) return;
   double reg = 0.0;
   for (int a = 0; a < nv; ++a) {

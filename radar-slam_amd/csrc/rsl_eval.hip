@@ -14,11 +14,13 @@
 
 #include "rsl_common.h"
 #include "rsl_internal.h"
+#include "rsl_reduce.h"
 
 namespace rsl {
 
 namespace {
 constexpr int kPeThreads = 256;
+constexpr int kPeWaves = kPeThreads / 64;
 
 struct Q {  // scipy order: x, y, z, w
   double x, y, z, w;
@@ -39,27 +41,6 @@ RSL_DEV void qmat(Q q, double (&m)[3][3]) {  // unit quaternion -> rotation matr
   m[2][0] = 2 * (x * z - y * w); m[2][1] = 2 * (y * z + x * w); m[2][2] = 1 - 2 * (x * x + y * y);
 }
 RSL_DEV Q load_q(const double* p) { return qnorm({p[3], p[4], p[5], p[6]}); }
-
-// Block sum of K doubles per thread into part[blockIdx.x * K + k] (wave shuffles, then LDS).
-template <int K>
-RSL_DEV void block_sum(double (&v)[K], double* part) {
-  __shared__ double red[kPeThreads / 64][K];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double x = v[k];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
-    if (lane == 0) red[w][k] = x;
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < K; k += kPeThreads) {
-    double s = 0;
-#pragma unroll
-    for (int j = 0; j < kPeThreads / 64; ++j) s += red[j][k];
-    part[(size_t)blockIdx.x * K + k] = s;
-  }
-}
 
 // Every thread: the sum over NB blocks of the K partials (NB <= a few hundred: a redundant read per block).
 template <int K>
@@ -83,7 +64,10 @@ __global__ __launch_bounds__(kPeThreads) void k_pe_sums(const double* __restrict
       v[3 + k] += gt[7 * i + k];
     }
   }
-  block_sum<6>(v, part);
+  __shared__ double red[kPeWaves * 6];
+  wg_partials<Red::Sum>(v, red);
+  const int q = threadIdx.x;  // thread q folds value q into the block's partial
+  if (q < 6) part[(size_t)blockIdx.x * 6 + q] = wg_fold<kPeWaves, 6, Red::Sum>(red, q, 0.0);
 }
 
 // Pass 2: centred cross-covariance H = S_c^T T_c (:116) and the quaternion-mean matrix K = sum r r^T of the relative
@@ -118,7 +102,10 @@ __global__ __launch_bounds__(kPeThreads) void k_pe_moments(const double* __restr
 #pragma unroll
       for (int b = a; b < 4; ++b) v[o++] += q4[a] * q4[b];
   }
-  block_sum<19>(v, part);
+  __shared__ double red[kPeWaves * 19];
+  wg_partials<Red::Sum>(v, red);
+  const int q = threadIdx.x;  // thread q folds value q into the block's partial
+  if (q < 19) part[(size_t)blockIdx.x * 19 + q] = wg_fold<kPeWaves, 19, Red::Sum>(red, q, 0.0);
 }
 
 // 3x3 SVD H = U diag(s) V^T by one-sided Jacobi on the columns of H; singular values in descending order.
@@ -434,39 +421,20 @@ __global__ __launch_bounds__(kPeThreads) void k_pe_stats1(const double* __restri
                                                           double* __restrict__ part) {
   const int s = blockIdx.y;
   const long m = lens ? (long)lens[s] : n;
-  double v[2] = {0, 0};
-  double mx = -INFINITY;
+  double v[3] = {0, 0, -INFINITY};  // sum, sum of squares, max
   for (long i = blockIdx.x * (long)kPeThreads + threadIdx.x; i < m; i += (long)gridDim.x * kPeThreads) {
     const double a = x[(size_t)s * stride + i];
     v[0] += a;
     v[1] += a * a;
-    mx = fmax(mx, a);
+    v[2] = fmax(v[2], a);
   }
-  __shared__ double red[kPeThreads / 64][3];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    v[0] += __shfl_xor(v[0], d);
-    v[1] += __shfl_xor(v[1], d);
-    mx = fmax(mx, __shfl_xor(mx, d));
-  }
-  if (lane == 0) {
-    red[w][0] = v[0];
-    red[w][1] = v[1];
-    red[w][2] = mx;
-  }
-  __syncthreads();
+  __shared__ double red[kPeWaves * 3];
+  wg_partials<Red::Sum, Red::Sum, Red::Max>(v, red);
   if (threadIdx.x == 0) {
-    double a = 0, b = 0, c = -INFINITY;
-    for (int j = 0; j < kPeThreads / 64; ++j) {
-      a += red[j][0];
-      b += red[j][1];
-      c = fmax(c, red[j][2]);
-    }
     double* o = part + ((size_t)s * gridDim.x + blockIdx.x) * 4;
-    o[0] = a;
-    o[1] = b;
-    o[2] = c;
+    o[0] = wg_fold<kPeWaves, 3, Red::Sum>(red, 0, 0.0);
+    o[1] = wg_fold<kPeWaves, 3, Red::Sum>(red, 1, 0.0);
+    o[2] = wg_fold<kPeWaves, 3, Red::Max>(red, 2, -(double)INFINITY);
   }
 }
 
@@ -478,21 +446,14 @@ __global__ __launch_bounds__(kPeThreads) void k_pe_stats2(const double* __restri
   double mean = 0;
   for (unsigned b = 0; b < gridDim.x; ++b) mean += part[((size_t)s * gridDim.x + b) * 4];
   mean = m > 0 ? mean / (double)m : 0.0;
-  double v[1] = {0};
+  double v = 0;
   for (long i = blockIdx.x * (long)kPeThreads + threadIdx.x; i < m; i += (long)gridDim.x * kPeThreads) {
     const double a = x[(size_t)s * stride + i] - mean;
-    v[0] += a * a;
+    v += a * a;
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v[0] += __shfl_xor(v[0], d);
-  __shared__ double red[kPeThreads / 64];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v[0];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0;
-    for (int j = 0; j < kPeThreads / 64; ++j) a += red[j];
-    part[((size_t)s * gridDim.x + blockIdx.x) * 4 + 3] = a;
-  }
+  __shared__ double red[kPeWaves];
+  const double dev = wg_one<kPeWaves, Red::Sum>(v, red, 0.0);
+  if (threadIdx.x == 0) part[((size_t)s * gridDim.x + blockIdx.x) * 4 + 3] = dev;
 }
 
 __global__ void k_pe_stats3(const double* __restrict__ part, int nb, long n,

@@ -8,7 +8,8 @@
 // best of the four edge minimisers (1-D clamp).  ``ridge`` adds ridge*(vx^2+vy^2)
 // (velocity_solver_improved.py:261 without the wrap).  Items carry a multiplicity (popcount of the
 // antenna mask of a deduplicated cell) so duplicate per-antenna detections count as in the reference.
-// The cell loader, the moments, the frame prologue, the reduction and the 2x2 box solve are rsl_vel_common.h's.
+// The cell loader, the moments, the frame prologue and the 2x2 box solve are rsl_vel_common.h's, the workgroup
+// reductions rsl_reduce.h's.
 #include "rsl_common.h"
 #include "rsl_internal.h"
 #include "rsl_vel_common.h"
@@ -17,19 +18,6 @@ namespace rsl {
 
 constexpr int kVelThreads = 512;  // k_velocity's only launch shape
 constexpr int kVelWaves = kVelThreads / 64;
-
-__device__ double block_max(double v, double* sh) {
-  const int t = threadIdx.x;
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off));
-  __syncthreads();
-  if ((t & 63) == 0) sh[t >> 6] = v;
-  __syncthreads();
-  double r = -1.0;
-  if (t == 0)
-    for (int w = 0; w < kVelWaves; ++w) r = fmax(r, sh[w]);
-  __syncthreads();
-  return r;
-}
 
 // Order-preserving key of a finite or infinite double (NaN never enters): min / max of keys = min / max of values.
 RSL_DEV unsigned long long okey(double v) {
@@ -92,7 +80,8 @@ __global__ __launch_bounds__(kVelThreads) void k_velocity(
       vel_moments(v, amask ? (double)__popc(amask[i]) : 1.0, c, s, y[i]);
     }
   }
-  rv_reduce7<kVelThreads>(v, red, mom);
+  wg_sums<kVelWaves>(v, red, mom);
+  __syncthreads();  // publishes mom; red is free again
   if (threadIdx.x == 0) {
     // the moments in registers, read once for the solve and the residual form below: which product the compiler fuses
     // into each fma of that form (the last bit of the cost) follows the order of these reads
@@ -153,9 +142,13 @@ __global__ __launch_bounds__(kVelThreads) void k_velocity(
       rmax = fmax(rmax, fmax(fabs(unkey(ymn[g]) - pr), fabs(unkey(hi) - pr)));
     }
   }
-  const double R2s = block_sum(r2, red, kVelWaves);
+  // Two one-value reductions back to back on the same red.  The first may write it because the barrier behind the
+  // moments' fold above came after that fold's reads; the second because of the barrier between the two, which comes
+  // after thread 0 has folded R2s.  Nothing writes red after the second.
+  const double R2s = wg_one<kVelWaves, Red::Sum>(r2, red, 0.0);
   const double R2 = r2m >= 0.0 ? r2m : R2s;
-  const double RM = block_max(rmax, red);
+  __syncthreads();
+  const double RM = wg_one<kVelWaves, Red::Max>(rmax, red, -1.0);
   if (threadIdx.x == 0) {
     double* o = out + f * 8;
     o[0] = vx;

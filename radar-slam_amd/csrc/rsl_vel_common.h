@@ -1,6 +1,5 @@
 // rsl_vel_common.h — what the velocity solvers share (k_velocity in rsl_vel.hip, k_velocity_robust in
 // rsl_vel_robust.hip, k_velocity_consensus in rsl_vel_consensus.hip), each step said once:
-//   block_sum      one workgroup sum (k_velocity's R2; rsl_aux.hip has uses of its own)
 //   vel_load       kVelU cells of one thread, all loads issued first
 //   vel_moments    one cell into the 7 moments [n, cc, cs, ss, cy, sy, yy]
 //   vel_frame      the frame prologue: the cos / sin table in LDS and the frame's clamped cell range (k_velocity and
@@ -8,29 +7,17 @@
 //   qcost, box_solve, vel_solve_bcast   the quadratic cost, the 2x2 box solve, and thread 0's solve into LDS
 //   rv_cells       the cell loop of a pass (grid-index or azimuth path) around a callback
 //   rv_resid       the residual of a cell, with explicit fma
-//   rv_reduce7     7 workgroup sums in one pass
+// The workgroup sums of the 7 moments (and k_velocity's R2 and maximum, the consensus solver's winner) are
+// rsl_reduce.h's, which this header includes for the three solvers.
 // The robust solver starts from k_velocity's solution, and the consensus solver falls back on it; all take it from these
 // functions, in the same order of operations.  Every helper is force-inlined and holds the expression text of the
 // kernels it came from: under fp-contract the compiler picks per kernel which products it fuses into an fma, so a
 // helper that is rewritten (an explicit fma, other brackets) may change a kernel's last bit.
 #pragma once
 #include "rsl_common.h"
+#include "rsl_reduce.h"
 
 namespace rsl {
-
-// Sum of v over the workgroup's nw waves: wave shuffle tree, then the waves in order on thread 0.  sh: 8 doubles of LDS.
-RSL_DEV double block_sum(double v, double* sh, int nw) {
-  const int t = threadIdx.x;
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  __syncthreads();
-  if ((t & 63) == 0) sh[t >> 6] = v;
-  __syncthreads();
-  double r = 0.0;
-  if (t == 0)
-    for (int w = 0; w < nw; ++w) r += sh[w];
-  __syncthreads();
-  return r;  // valid on thread 0
-}
 
 constexpr int kVelU = 8;
 
@@ -173,29 +160,6 @@ RSL_DEV void rv_cells(const double* __restrict__ az, const int* __restrict__ gid
 // The residual, with explicit fma: every pass (select, score, moments, output) must see the same bits for a cell.
 RSL_DEV double rv_resid(double yi, double k, double vx, double vy, double c, double s) {
   return fma(-k, fma(vx, c, vy * s), yi);
-}
-
-// Sums of 7 values over the workgroup into mom[0..6], in block_sum's order (wave shuffle tree, then the waves in order
-// on thread 0) with all 7 in one pass: 2 barriers instead of 21.  red: [kThreads / 64 * 7] doubles of LDS.  Valid for
-// every thread on return.  With 7 x block_sum here the Huber solve at a fixed scale took 2.376 instead of 2.210 ms per
-// 2000 cfg2 frames.
-template <int kThreads>
-RSL_DEV void rv_reduce7(double (&v)[7], double* red, double* mom) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < 7; ++q)
-    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
-  if ((t & 63) == 0)
-#pragma unroll
-    for (int q = 0; q < 7; ++q) red[(t >> 6) * 7 + q] = v[q];
-  __syncthreads();
-  if (t == 0)
-    for (int q = 0; q < 7; ++q) {
-      double r = 0.0;
-      for (int w = 0; w < kThreads / 64; ++w) r += red[w * 7 + q];
-      mom[q] = r;
-    }
-  __syncthreads();
 }
 
 }  // namespace rsl

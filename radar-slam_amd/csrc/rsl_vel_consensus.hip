@@ -11,8 +11,8 @@
 // in chunks of kCvChunk as (c, s, y, m) through the shared cell loader, and every lane walks the chunk reading the same
 // LDS address (a broadcast: no bank conflict), so the cells are streamed from memory once for all hypotheses and there
 // is no per-hypothesis reduction.  The winner is one workgroup-wide max over the 64-bit key (count + 1, hyps - 1 - h);
-// an invalid hypothesis has key 0.  The loader, moments, residual, 7-sum reduction and box solve of the LS fallback,
-// the refinement passes and the output pass are rsl_vel_common.h's; every pass, scoring included, evaluates the
+// an invalid hypothesis has key 0.  The loader, moments, residual and box solve of the LS fallback, the
+// refinement passes and the output pass are rsl_vel_common.h's, the reductions rsl_reduce.h's; every pass, scoring included, evaluates the
 // residual with the one rv_resid, so score, refinement and output see the same bits for a cell.
 //
 // Scoring is bound by fp64 VALU issue (mul + 2 fma + compare per cell and hypothesis), not by memory.  Measured on
@@ -39,9 +39,9 @@ static_assert(RSL_CONSENSUS_MAX_H == 4096, "the winner's key keeps h in its low 
 constexpr int kCvRed = 0;                      // [kCvWaves * 7] wave partials
 constexpr int kCvMom = kCvRed + kCvWaves * 7;  // [8] reduced sums
 constexpr int kCvBc = kCvMom + 8;              // [2] solution broadcast
-constexpr int kCvKey = kCvBc + 2;              // [kCvWaves] wave maxima of the key, then [0] the winner's
-constexpr int kCvNv = kCvKey + kCvWaves;       // [kCvWaves] wave counts of valid hypotheses, then [0] their sum
-constexpr int kCvC = kCvNv + kCvWaves;         // [kCvChunk] cos
+constexpr int kCvKey = kCvBc + 2;              // [kCvWaves * 2] wave partials: maximum key, count of valid hypotheses
+constexpr int kCvWin = kCvKey + kCvWaves * 2;  // [2] the winner's key, the number of valid hypotheses
+constexpr int kCvC = kCvWin + 2;               // [kCvChunk] cos
 constexpr int kCvS = kCvC + kCvChunk;          // [kCvChunk] sin
 constexpr int kCvY = kCvS + kCvChunk;          // [kCvChunk] y
 constexpr int kCvM = kCvY + kCvChunk;          // [kCvChunk] int multiplicities (kCvChunk / 2 doubles)
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(kCvThreads) void k_velocity_consensus(
   double* mom = wk + kCvMom;
   double* bc = wk + kCvBc;
   u64* keyw = reinterpret_cast<u64*>(wk + kCvKey);
-  u64* nvw = reinterpret_cast<u64*>(wk + kCvNv);
+  u64* win = reinterpret_cast<u64*>(wk + kCvWin);
   double* lc = wk + kCvC;
   double* ls = wk + kCvS;
   double* ly_ = wk + kCvY;
@@ -159,36 +159,23 @@ __global__ __launch_bounds__(kCvThreads) void k_velocity_consensus(
   }
 
   // the winner: the largest count, ties to the lowest h; and the number of valid hypotheses
-  u64 key = 0, nv = 0;
+  u64 kn[2] = {0, 0};  // key, valid count
 #pragma unroll
   for (int q = 0; q < kPer; ++q)
     if (hok[q]) {
       const u64 kq = ((cnt[q] + 1) << 12) | (u64)(hyps - 1 - (t + q * kCvThreads));
-      key = kq > key ? kq : key;
-      ++nv;
+      kn[0] = kq > kn[0] ? kq : kn[0];
+      ++kn[1];
     }
-  const u64 mine = key;
-  for (int off = 32; off > 0; off >>= 1) {
-    const u64 o = __shfl_down(key, off);
-    key = o > key ? o : key;
-    nv += __shfl_down(nv, off);
-  }
-  if ((t & 63) == 0) {
-    keyw[t >> 6] = key;
-    nvw[t >> 6] = nv;
-  }
-  __syncthreads();
+  const u64 mine = kn[0];
+  wg_partials<Red::Max, Red::Sum>(kn, keyw);  // integers: exact in any order
   if (t == 0) {
-    for (int w = 1; w < kCvWaves; ++w) {
-      key = keyw[w] > key ? keyw[w] : key;
-      nv += nvw[w];
-    }
-    keyw[0] = key;
-    nvw[0] = nv;
+    win[0] = wg_fold<kCvWaves, 2, Red::Max>(keyw, 0, (u64)0);
+    win[1] = wg_fold<kCvWaves, 2, Red::Sum>(keyw, 1, (u64)0);
   }
   __syncthreads();
-  const u64 best = keyw[0];
-  const int n_valid = (int)nvw[0];
+  const u64 best = win[0];
+  const int n_valid = (int)win[1];
   const int best_h = best ? hyps - 1 - (int)(best & 0xfffull) : -1;
   if (best) {
     if (mine == best)  // exactly one thread: h is part of the key
@@ -205,7 +192,8 @@ __global__ __launch_bounds__(kCvThreads) void k_velocity_consensus(
                          [&](long long, bool, int m, double c, double s, double yi) {
                            vel_moments(v, (double)m, c, s, yi);
                          });
-    rv_reduce7<kCvThreads>(v, red, mom);
+    wg_sums<kCvWaves>(v, red, mom);
+    __syncthreads();  // publishes mom; red is free again (so at every fold below)
     vel_solve_bcast(mom, k, ridge, lx, hx, ly, hy, bc);
   }
   __syncthreads();
@@ -219,8 +207,9 @@ __global__ __launch_bounds__(kCvThreads) void k_velocity_consensus(
                            const double w = fabs(rv_resid(yi, k, vx, vy, c, s)) <= tc ? (double)m : 0.0;
                            vel_moments(v, w, c, s, yi);
                          });
-    rv_reduce7<kCvThreads>(v, red, mom);  // its first barrier also orders the reads of bc above before the write below
-    if (!(mom[0] != 0.0)) break;          // no inlier: keep x
+    wg_sums<kCvWaves>(v, red, mom);  // its barrier also orders the reads of bc above before the write below
+    __syncthreads();
+    if (!(mom[0] != 0.0)) break;  // no inlier: keep x
     vel_solve_bcast(mom, k, ridge, lx, hx, ly, hy, bc);
     __syncthreads();
     vx = bc[0];
@@ -242,7 +231,8 @@ __global__ __launch_bounds__(kCvThreads) void k_velocity_consensus(
                          v[2] += in ? w : 0.0;
                          v[3] += w;
                        });
-  rv_reduce7<kCvThreads>(v, red, mom);
+  wg_sums<kCvWaves>(v, red, mom);
+  __syncthreads();
   if (t == 0) {
     double* o = out + f * 8;
     o[0] = vx;

@@ -12,9 +12,9 @@
 // scale costs 1 pass per iteration, the estimated scale 4; the LS start and the output pass add 2.  The workgroup
 // re-reads its own lines, so all passes after the first are served by L2 / Infinity Cache.
 //
-// The start comes from k_velocity's own source: the frame prologue, the cell loader, the moments, the reduction and the
-// 2x2 box solve are the helpers of rsl_vel_common.h in both kernels.  Same source, not guaranteed the same bits:
-// under fp-contract the compiler chooses per kernel which products it fuses into an fma, so the two starts may differ
+// The start comes from k_velocity's own source: the frame prologue, the cell loader, the moments and the 2x2 box solve
+// are the helpers of rsl_vel_common.h, the reduction is rsl_reduce.h's, in both kernels.  Same source, not guaranteed
+// the same bits: under fp-contract the compiler chooses per kernel which products it fuses into an fma, so the two starts may differ
 // in the last place (tests/test_gpu_vel_robust.py::test_ls_equivalence holds them within 1e-13).
 #include "rsl_common.h"
 #include "rsl_internal.h"
@@ -87,7 +87,8 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
                          [&](long long, bool, int m, double c, double s, double yi) {
       vel_moments(v, (double)m, c, s, yi);
     });
-    rv_reduce7<kRvThreads>(v, red, mom);
+    wg_sums<kRvWaves>(v, red, mom);
+    __syncthreads();  // publishes mom; red is free again (so at every fold below)
   }
   const double W = mom[0];  // sum of the multiplicities: an exact integer
   vel_solve_bcast(mom, k, ridge, lx, hx, ly, hy, bc);
@@ -169,7 +170,10 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
       const double w = m == 0 ? 0.0 : (double)m * rv_weight(loss, fabs(rv_resid(yi, k, vx, vy, c, s)), tc);
       vel_moments(v, w, c, s, yi);
     });
-    rv_reduce7<kRvThreads>(v, red, mom);
+    // all 7 in one pass: as 7 one-value sums (21 barriers for these 2) the Huber solve at a fixed scale took 2.376
+    // instead of 2.210 ms per 2000 cfg2 frames
+    wg_sums<kRvWaves>(v, red, mom);
+    __syncthreads();
     if (!(mom[0] != 0.0)) {  // every weight is 0: keep x
       conv = true;
       break;
@@ -203,7 +207,8 @@ __global__ __launch_bounds__(kRvThreads) void k_velocity_robust(
     v[2] += w * u;
     if (loss == RSL_LOSS_HUBER ? a <= tc : (a < tc || (tc == 0.0 && a == 0.0))) v[3] += w;
   });
-  rv_reduce7<kRvThreads>(v, red, mom);
+  wg_sums<kRvWaves>(v, red, mom);
+  __syncthreads();
   if (t == 0) {
     double* o = out + f * 8;
     o[0] = vx;

@@ -316,7 +316,9 @@ __global__ __launch_bounds__(1024) void k_wrapped_best(const double* __restrict_
   }
 }
 
-// Data Hessian 2 k^2 sum J J^T (fp64), one block.
+// Data Hessian 2 k^2 sum J J^T (fp64), one block.  Its sums are not rsl_reduce.h's on purpose: here 21 threads add the
+// 256 per-thread values of part in thread order, another order of additions than the wave tree.  Moving it would
+// change the last bits of Hd, and with them possibly the basin a wrapped search ends in.
 __global__ __launch_bounds__(256) void k_wrapped_hess(const double* __restrict__ J, long n, double k,
                                                       double* __restrict__ Hd) {
   __shared__ double part[256][21];

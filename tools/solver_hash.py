@@ -1,5 +1,6 @@
 """SHA-256 of the raw output bytes of the phase-model solvers (rsl_associate, rsl_phase_model, rsl_bvls,
-rsl_wrapped_solve, rsl_wrapped_search; rows a25-a31) on the inputs of tests/golden/golden_wrapped.npz, under the
+rsl_wrapped_solve, rsl_wrapped_search; rows a25-a31) on the inputs of tests/golden/golden_wrapped.npz, and of the pose
+evaluation (rsl_eval.hip: align / APE / RTE through the drop-in PoseErrorEvaluator, two seeded trajectories), under the
 library RSL_LIBRARY: equal hashes across two libraries = bit-identical solvers.  The two wrapped calls are made on the
 library itself, so that all 8 output doubles {x[6], cost, start index} are hashed.
 GPU box:  RSL_LIBRARY=... python tools/solver_hash.py"""
@@ -23,6 +24,30 @@ SIX = ctypes.c_double * 6
 
 def sha(*arrays):
     return hashlib.sha256(b''.join(np.ascontiguousarray(a).tobytes() for a in arrays)).hexdigest()[:12]
+
+
+def pose_eval(N):
+    """Every output of align_trajectories, compute_ape and compute_rte (segment lengths 1, 10, 100) on one seeded
+    trajectory of N poses: a random-walk heading, the estimate rotated, shifted and noisy.  513 = two blocks of the
+    256-thread eval kernels and one thread of a third."""
+    from evaluation.compute_pose_error import PoseErrorEvaluator
+    rs = np.random.RandomState(N)
+    yaw = np.cumsum(0.01 * rs.randn(N))
+    gt_p = np.cumsum(np.column_stack([np.cos(yaw), np.sin(yaw), 0.05 * rs.randn(N)]), axis=0)
+    gt_q = np.column_stack([np.zeros(N), np.zeros(N), np.sin(yaw / 2), np.cos(yaw / 2)])  # scalar last
+    c, s = np.cos(0.4), np.sin(0.4)
+    est_p = gt_p @ np.array([[c, s, 0], [-s, c, 0], [0, 0, 1.0]]) + [3, -1, 0.5] + 0.3 * rs.randn(N, 3)
+    est_q = gt_q + 0.03 * rs.randn(N, 4)  # not unit: the device normalises, as Rotation.from_quat does
+    est, gt = np.column_stack([est_p, est_q]), np.column_stack([gt_p, gt_q])
+    ev = PoseErrorEvaluator(rte_segment_lengths=[1, 10, 100])
+    al, T, info = ev.align_trajectories(est, gt)
+    parts = [al, T] + [np.float64(info[k]) for k in sorted(info)]
+    ape = ev.compute_ape(est, gt)
+    parts += [np.float64(ape[k]) for k in sorted(ape) if k != 'alignment_info']
+    rte = ev.compute_rte(est, gt)
+    for key in sorted(rte):
+        parts += [np.float64(rte[key][k]) for k in ('errors', 'rmse', 'mean', 'std', 'max', 'num_segments')]
+    return sha(*parts)
 
 
 def main():
@@ -73,6 +98,8 @@ def main():
     for mode in (0, 1):
         out[f'search_m{mode}'] = wrapped(ctx.lib.rsl_wrapped_search, mode, 6, dprev if mode else None, lo, hi,
                                          (SIX(0, 0, 0, 0, 0, 0), spacing, 64), nbytes)
+    for N in (513, 1000):
+        out[f'pose_eval_n{N}'] = pose_eval(N)
     print(json.dumps(out), flush=True)
 
 
