@@ -337,7 +337,8 @@ int rsl_range_azimuth(rsl_handle h, const void* cov, long long n, int A, const v
 
 /* a11, a15, a26  normalised signature (c64 [n, A], nullable), ESPRIT closed form (f64 deg, nullable;
  *     angle_estimation.py:178-225 with esprit_scale = lambda / (2 pi d)), spatial phase
- *     angle(s1 conj(s0)) (f64, nullable; velocity_solver.py:136), az_out = az_table[gidx] (f64, nullable). */
+ *     angle(s1 conj(s0)) (f64, nullable; velocity_solver.py:136; exactly 0.0 where s0 or s1 is 0), az_out =
+ *     az_table[gidx] (f64, nullable).  2 <= A <= 32 (RSL_ERR_INVALID otherwise: the phase needs two antennas). */
 int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
                     const void* ncell_dev, long long ncell, double esprit_scale, const void* gidx,
                     const void* az_table, void* sig_out, void* esprit_deg, void* phase, void* az_out);
@@ -348,7 +349,14 @@ int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const vo
  *     (device), spec f64 [n][G] = 1/den or 0 (den <= 1e-12), deg f64 [n] (0.0 where the reference's ESPRIT
  *     raises, NaN where it returns NaN).  The reference's noise / null-space bases for 2 <= K < M come from LAPACK
  *     round-off; these use a fixed Householder completion (rsl_subspace.hip), so only K = 1, K >= M (MUSIC),
- *     K <= 0 (ESPRIT) and zero signatures are reference-determined. */
+ *     K <= 0 (ESPRIT) and zero signatures are reference-determined.
+ *     rsl_esprit_subspace by kk = the column count of U[:, :num_sources] (U is (M-1) x (M-1)): kk = 0 or M <= 2: 0.0
+ *     (empty Phi); kk = 1: the closed form; kk = 2: one of the reference's two eigenvalues; kk = M - 1: 0.0 (Phi is
+ *     nilpotent, every eigenvalue is 0, and the reference's value there is round-off); 3 <= kk < M - 1: Phi on the
+ *     span [s[:-1], s[1:], e_0 .. e_{kk-3}] has two non-zero eigenvalues and a zero one of multiplicity kk - 2; the
+ *     value is the first diagonal entry of Phi's Schur form among the two of largest modulus (the first entry as it
+ *     is would be a numerically zero eigenvalue, whose argument is round-off, on about 1 % of random signatures and
+ *     up to 2 % at kk = M - 2). */
 int rsl_music_subspace(rsl_handle h, const void* sigs, long long n, int M, int num_sources, const void* steer_c128,
                        int G, void* spec);
 int rsl_esprit_subspace(rsl_handle h, const void* sigs, long long n, int M, int num_sources, double esprit_scale,

@@ -625,6 +625,7 @@ int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const vo
                     const void* az_table, void* sig_out, void* esprit_deg, void* phase, void* az_out) {
   if (!h) return RSL_ERR_INVALID;
   if (A <= 0 || A > 32 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_cell_extras: bad shape");
+  if (A < 2) return fail(h, RSL_ERR_INVALID, "rsl_cell_extras: needs at least 2 antennas");  // phase reads s0 and s1
   if (!rds || !c_frame || !c_rc) return fail(h, RSL_ERR_INVALID, "rsl_cell_extras: null pointer");
   if (az_out && (!gidx || !az_table)) return fail(h, RSL_ERR_INVALID, "rsl_cell_extras: az_out needs gidx+table");
   if (ncell <= 0) return RSL_OK;  // ncell is the launch bound (capacity) when ncell_dev is given

@@ -464,7 +464,9 @@ __global__ __launch_bounds__(256) void k_cell_extras(CellList cl, double esprit_
     // s1 * conj(s0)
     const double re = sr[1] * sr[0] + si[1] * si[0];
     const double im = si[1] * sr[0] - sr[1] * si[0];
-    phase[c] = atan2(im, re);
+    // s0 or s1 exactly 0: angle(0) = 0 as in the fused extras (atan2_fast), not the pi that atan2(+0, -0) returns when
+    // the products of a zero with negative components sum to -0
+    phase[c] = (re == 0.0 && im == 0.0) ? 0.0 : atan2(im, re);
   }
   if (az_out && gidx) az_out[c] = az_table[gidx[c]];
   if (esprit_deg) {

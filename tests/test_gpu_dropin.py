@@ -5,6 +5,7 @@ import pytest
 
 import parity as P
 import radar_oracle as O
+from angle_ref import music_den as _householder_den
 
 pytestmark = pytest.mark.gpu
 
@@ -236,21 +237,6 @@ def test_robust_sequence_vs_golden(golden):
     st = rob.get_target_statistics()
     assert st['total_targets_tracked'] == int(z['stats'][0]) and st['active_targets'] == int(z['stats'][1])
     assert abs(st['average_confidence'] - z['stats'][2]) < 1e-5
-
-
-def _householder_den(s, a, K):
-    """numpy restatement of rsl_subspace.hip's basis: V = [s/|s|, Householder completion], den = sum_{noise j}
-    |(P a)_j|^2 (test side; the reference's null-space columns for 2 <= K < M are LAPACK round-off, parity unpinned)."""
-    M = len(s)
-    lo = (K if K < M else M) if K >= 0 else max(M + K, 0)
-    nx = np.linalg.norm(s)
-    if nx == 0:
-        return sum(abs(a[M - 1 - j]) ** 2 for j in range(lo, M))
-    ph = s[0] / abs(s[0]) if abs(s[0]) > 0 else 1.0
-    w = s.astype(complex).copy()
-    w[0] -= -ph * nx
-    pa = a - 2 * w * (np.vdot(w, a) / np.vdot(w, w).real)
-    return float(np.sum(np.abs(pa[lo:]) ** 2))
 
 
 def test_music_num_sources_general(ctx):
