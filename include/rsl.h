@@ -343,6 +343,49 @@ int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const vo
                     const void* ncell_dev, long long ncell, double esprit_scale, const void* gidx,
                     const void* az_table, void* sig_out, void* esprit_deg, void* phase, void* az_out);
 
+/* Point cloud: sub-bin range, Doppler and azimuth and the position of every detected cell (rsl_refine.hip; the
+ *     reference project has no counterpart, this comment is the specification).  Cells and n as in rsl_doa:
+ *     n = min(*ncell_dev, ncell); slots beyond n are not written; ncell = 0 launches nothing.  rds c64 [*, A, S, C],
+ *     2 <= A <= 32; power f32 [*, S, C] (nullable), the map of rsl_power_integrate; gidx i32 [n], the scan's argmax;
+ *     az_table f64 [G] radians, strictly increasing inside [-pi/2, pi/2]; steer_c64 device c64 [G][A], any array's
+ *     steering matrix rounded to c64; axes4 (host) = {r0, r_step, d0, d_step}.
+ *     1. Five powers of cell (f, i, j): P0 = P[f,i,j], Pr+- = P[f,i+-1,j], Pd+- = P[f,i,(j+-1) mod C] (the Doppler axis
+ *        wraps, the range axis truncates, as in the CFAR family).  Read from power when given; otherwise each is
+ *        formed from rds as rsl_power_integrate defines it (fmaf(re, re, im im) per antenna, added in antenna order
+ *        in fp32), so both ways are bit-identical.
+ *     2. Offsets dr, dd in [-0.5, 0.5], one estimator per axis, in fp64 from the axis' fp32 powers (pm, p0, pp); every
+ *        comparison is on the fp32 values:
+ *          RSL_REFINE_NONE  0
+ *          RSL_REFINE_LOG   0 if any of the three is <= 0; else with den = ln pm - 2 ln p0 + ln pp: 0 if den >= 0,
+ *                           else clamp(0.5 (ln pm - ln pp) / den, -0.5, 0.5)    (log-parabola: Hamming, Blackman)
+ *          RSL_REFINE_RECT  0 if p0 <= 0 or pm == pp; else q = max(pm, pp), r = sqrt(q / p0), s = +1 if pp > pm
+ *                           else -1: s min(0.5, r / (1 + r))                    (amplitude ratio, no window)
+ *          RSL_REFINE_HANN  as RECT with s clamp((2 r - 1) / (r + 1), 0, 0.5)   (amplitude ratio, Hann window)
+ *        At i = 0 and i = S - 1, dr = 0.
+ *     3. Azimuth, g = gidx[c].  g outside [0, G): az, x and y are NaN, the rest is written as usual.  Otherwise
+ *        B_k = |a_k^H z|^2 for k = g-1, g, g+1 in fp64 (z the cell's fp32 signature, a_k the row of steer_c64, both
+ *        promoted; z is not normalised, the vertex is scale-free), u_k = sin(az_table[k]),
+ *        d01 = (B_g - B_{g-1}) / (u_g - u_{g-1}), d12 likewise, c = (d12 - d01) / (u_{g+1} - u_{g-1}).  If g is 0 or
+ *        G - 1, or c >= 0, or c is not finite: az = az_table[g].  Otherwise u* = (u_{g-1} + u_g) / 2 - d01 / (2 c)
+ *        clamped to [(u_{g-1} + u_g) / 2, (u_g + u_{g+1}) / 2] and az = asin(u*).  MUSIC's rank-1 spectrum
+ *        1 / (M - B) has the same argmax, so the rule serves both methods.
+ *     4. out_az f64 [n] (nullable) = az.  out_points f32 [n][8] (nullable; 32-byte rows, 16-byte aligned), each row
+ *        computed in fp64 and rounded once: with range = r0 + r_step (i + dr), doppler = d0 + d_step (j + dd) (the
+ *        product and the sum each rounded, not fused: a label that cancels to nearly 0 is the same everywhere):
+ *          {range, doppler, az, x = range cos az, y = range sin az, 10 log10(P0 + 1e-12), dr, dd}
+ *        No wrap is applied to the Doppler label: bin C - 1 with dd > 0 reads slightly past the axis end.
+ *     RSL_ERR_INVALID: A outside [2, 32]; S, C or G <= 0; an unknown mode; a step that is not finite; both outputs
+ *     null; out_points not 16-byte aligned; null rds, lists, gidx, az_table, steer_c64 or axes4 with ncell > 0.
+ *     Timed under RSL_K_CELL_EXTRAS. */
+#define RSL_REFINE_NONE 0
+#define RSL_REFINE_LOG 1
+#define RSL_REFINE_RECT 2
+#define RSL_REFINE_HANN 3
+int rsl_cell_refine(rsl_handle h, const void* rds, const void* power, int A, int S, int C, const void* c_frame,
+                    const void* c_rc, const void* ncell_dev, long long ncell, const void* gidx, const void* az_table,
+                    const void* steer_c64, int G, int range_mode, int doppler_mode, const double* axes4,
+                    void* out_points, void* out_az);
+
 /* a13-a15 with num_sources != 1  music_spectrum / estimate_angle_music / estimate_angle_esprit
  *     (angle_estimation.py:109-225) for any num_sources (Python slicing semantics for K <= 0 and K >= M), fp64:
  *     sigs c128 [n][M] (device, the signatures as given; MUSIC normalises them), steer_c128 f64 [G][M][2]

@@ -637,6 +637,33 @@ int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const vo
                    "cell_extras");
 }
 
+int rsl_cell_refine(rsl_handle h, const void* rds, const void* power, int A, int S, int C, const void* c_frame,
+                    const void* c_rc, const void* ncell_dev, long long ncell, const void* gidx, const void* az_table,
+                    const void* steer_c64, int G, int range_mode, int doppler_mode, const double* axes4,
+                    void* out_points, void* out_az) {
+  if (!h) return RSL_ERR_INVALID;
+  if (A < 2 || A > 32) return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: antennas outside [2, 32]");
+  if (S <= 0 || C <= 0 || G <= 0) return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: bad shape");
+  for (int mode : {range_mode, doppler_mode})
+    if (mode < RSL_REFINE_NONE || mode > RSL_REFINE_HANN)
+      return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: unknown RSL_REFINE_* mode");
+  if (axes4 && !(std::isfinite(axes4[1]) && std::isfinite(axes4[3])))
+    return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: an axis step is not finite");
+  if (!out_points && !out_az) return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: both outputs null");
+  if (reinterpret_cast<size_t>(out_points) & 15)
+    return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: out_points is not 16-byte aligned");
+  if (ncell <= 0) return RSL_OK;  // ncell is the launch bound (capacity) when ncell_dev is given
+  if (!rds || !c_frame || !c_rc || !gidx || !az_table || !steer_c64 || !axes4)
+    return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: null pointer");
+  Scope sc(h, RSL_K_CELL_EXTRAS);
+  return hip_check(h,
+                   rsl::launch_cell_refine(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell),
+                                           (const float*)power, (const int*)gidx, (const double*)az_table,
+                                           (const float2*)steer_c64, G, range_mode, doppler_mode, axes4,
+                                           (float*)out_points, (double*)out_az),
+                   "cell_refine");
+}
+
 int rsl_confidence(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
                    long long n, const void* gidx, const void* steer_c128, const void* steer_phase, void* conf) {
   if (!h) return RSL_ERR_INVALID;

@@ -139,6 +139,12 @@ int toep_table_build(const double* steer_c128, int G, int M, uint16_t* out);
 hipError_t launch_cell_extras(hipStream_t st, CellList cl, double esprit_scale, const int* gidx,
                               const double* az_table, float2* sig_out, double* esprit_deg, double* phase,
                               double* az_out);
+// Point cloud (rsl_refine.hip; the contract is rsl_cell_refine's in rsl.h): sub-bin range / Doppler offsets from the
+// five powers around each cell (power f32 [*, S, C], or null: formed from the RDS), azimuth at the parabola vertex of
+// the beamforming values around gidx over steer c64 [G][A] -> out_points f32 [n][8] (16-B aligned), out_az f64 [n].
+hipError_t launch_cell_refine(hipStream_t st, CellList cl, const float* power, const int* gidx, const double* az_table,
+                              const float2* steer, int G, int range_mode, int doppler_mode, const double* axes4,
+                              float* out_points, double* out_az);
 // K7: robust confidence for (cell, grid index) pairs (fp64).
 hipError_t launch_confidence(hipStream_t st, CellList cl, const int* gidx, const double* steer_c128,
                              const double* steer_phase, double* conf_out);

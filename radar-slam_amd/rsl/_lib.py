@@ -26,6 +26,8 @@ RA_BARTLETT, RA_CAPON = 0, 1  # RSL_RA_*: the method of rsl_range_azimuth
 RA_IDS = {'bartlett': RA_BARTLETT, 'capon': RA_CAPON}
 RA_MAX_A = 16  # RSL_RA_MAX_A: the most antennas of rsl_range_cov / rsl_range_azimuth
 RA_MIN_LOADING = 1e-4  # RSL_RA_MIN_LOADING: the least diagonal loading of the Capon map
+REFINE_NONE, REFINE_LOG, REFINE_RECT, REFINE_HANN = 0, 1, 2, 3  # RSL_REFINE_*: the offset estimators of rsl_cell_refine
+REFINE_IDS = {'none': REFINE_NONE, 'log': REFINE_LOG, 'rect': REFINE_RECT, 'hann': REFINE_HANN}
 LOSS_HUBER, LOSS_TUKEY = 1, 2
 LOSS_IDS = {'huber': LOSS_HUBER, 'tukey': LOSS_TUKEY}
 LOSS_DEFAULT_C = {LOSS_HUBER: 1.345, LOSS_TUKEY: 4.685}  # 95 % efficiency at the normal distribution
@@ -77,6 +79,8 @@ SIGNATURES = {
     'rsl_range_azimuth': (c_int, [_P, _P, c_longlong, c_int, _P, c_int, c_int, c_double, _P, _P]),
     'rsl_cell_extras': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_longlong, c_double, _P, _P, _P, _P,
                                 _P, _P]),
+    'rsl_cell_refine': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_longlong, _P, _P, _P, c_int, c_int, c_int,
+                                POINTER(c_double), _P, _P]),
     'rsl_confidence': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_longlong, _P, _P, _P, _P]),
     'rsl_velocity': (c_int, _VEL + [_P, _P, _P]),
     'rsl_velocity_robust': (c_int, _VEL + [c_int, c_double, c_double, c_int, c_double, _P, _P, _P]),

@@ -99,8 +99,26 @@ class ChainConfig:
                                                # None: nothing is allocated or launched
     ra_doppler: Optional[tuple] = None         # Doppler window (c0, c1) of the covariance; None: all num_chirps bins
     ra_loading: float = 1e-2                   # Capon's diagonal loading, in [_lib.RA_MIN_LOADING, 1]
+    point_cloud: bool = False                  # also refine every cell below the bin and grid spacing
+                                               # (rsl_cell_refine, after the DoA scan): results()['points'] f32
+                                               # [cells, 8] = {range, doppler, az, x, y, power_db, range offset,
+                                               # doppler offset} and ['az_refined']; the range estimator follows
+                                               # window_type (tables.refine_mode_for_window), the Doppler axis takes
+                                               # 'rect'; False: nothing is allocated or launched
+    pc_velocity: bool = False                  # label the points' Doppler column in metres per second
+                                               # (tables.point_axes(velocity=True)) instead of the reference's hertz
+    velocity_az: str = 'grid'                  # 'grid': the solvers read az_table[gidx]; 'refined': the refined
+                                               # azimuths of the point cloud (needs point_cloud)
 
     def __post_init__(self):
+        if self.velocity_az not in ('grid', 'refined'):
+            raise ValueError(f"velocity_az must be 'grid' or 'refined', not {self.velocity_az!r}")
+        if self.velocity_az == 'refined' and not self.point_cloud:
+            raise ValueError("velocity_az='refined' needs point_cloud=True")
+        if self.point_cloud:
+            if not 2 <= int(self.num_antennas) <= 32:
+                raise ValueError(f'point_cloud needs 2 to 32 antennas, not {self.num_antennas}')
+            tables.refine_mode_for_window(self.window_type)  # ValueError for a window without an estimator
         if self.ra_map is not None and self.ra_map not in _lib.RA_IDS:
             raise ValueError(f"ra_map must be None, 'bartlett' or 'capon', not {self.ra_map!r}")
         if self.ra_doppler is not None:
@@ -250,6 +268,14 @@ class RadarChain:
             self.ra_win = (0, C) if cfg.ra_doppler is None else (int(cfg.ra_doppler[0]), int(cfg.ra_doppler[1]))
             self.ra_cov = e((F, S, A, A), torch.complex64)
             self.ra = dict(map=e((F, S, len(self.grid)), torch.float32), arg=e((F, S), torch.int32))
+        self.pc = None
+        if cfg.point_cloud:  # point cloud: one row and one refined azimuth per cell, from the antenna-summed power
+            self.pc_steer = ctx.steering_c64(steer_c128)
+            self.pc_modes = (tables.refine_mode_for_window(cfg.window_type), 'rect')
+            self.pc_axes = tables.point_axes(cfg, S, C, velocity=cfg.pc_velocity)
+            if self.power is None:  # detect_on='antenna': no summed map yet, run_back integrates it
+                self.power = e((F, S, C), torch.float32)
+            self.pc = dict(points=e((cc, 8), torch.float32), az=e((cc,), torch.float64))
         # one signature gather for DoA + ESPRIT + phase when the Toeplitz path applies (uniform linear array)
         self.fused_doa = bool(self.steer['toeplitz']) and A >= 2 and not cfg.spectrum
         self.spec = None
@@ -359,12 +385,20 @@ class RadarChain:
         if self.ra is not None:
             ctx.range_cov(self.rds, self.ra_win, out=self.ra_cov)
             ctx.range_azimuth(self.ra_cov, self.ra_steer, cfg.ra_map, loading=cfg.ra_loading, out=self.ra)
+        if self.pc is not None:
+            if not self.sum:
+                ctx.integrate_power(self.rds, out=self.power)
+            ctx.cell_refine(self.rds, L['c_frame'], L['c_rc'], self.gidx, self.az_table, self.pc_steer,
+                            n=self.cell_cap, n_dev=self.ncell_dev, power=self.power, range_mode=self.pc_modes[0],
+                            doppler_mode=self.pc_modes[1], axes=self.pc_axes, out=self.pc)
         if not velocity:
             return
         # the problem the three solvers share: the chain's own lists, on the grid-index path
         prob = dict(az=None, y=self.ext['phase'], seg=self.offs['cell_base'], k=self.k, ridge=cfg.ridge,
                     bounds=cfg.bounds, amask=L['c_amask'], out=self.vel, gidx=self.gidx, az_table=self.az_table,
                     n=self.cell_cap)
+        if cfg.velocity_az == 'refined':  # the point cloud's azimuths in place of the grid's
+            prob.update(az=self.pc['az'], gidx=None, az_table=None)
         if cfg.velocity_loss == 'consensus':
             # vel columns 2-7 become {cost, rmse_in, n_in, n, best_h, n_valid} (include/rsl.h)
             ctx.velocity_consensus(**prob, scale=cfg.velocity_scale, c=cfg.velocity_c, hyps=cfg.velocity_hyps,
@@ -395,6 +429,8 @@ class RadarChain:
                          ss_den=h(self.ss['den'], nc).astype(np.float64))
         if self.ra is not None:  # f32 [F, S, G] and i32 [F, S]: every range bin of every frame
             extra.update(ra_map=self.ra['map'].cpu().numpy(), ra_arg=self.ra['arg'].cpu().numpy())
+        if self.pc is not None:
+            extra.update(points=h(self.pc['points'], nc), az_refined=h(self.pc['az'], nc))
         return dict(entry_base=self.offs['entry_base'].cpu().numpy(), cell_base=self.offs['cell_base'].cpu().numpy(),
                     **dict(zip(('e_ant', 'e_rbin', 'e_dbin'), unpack_coord(h(L['e_coord'], ne)))),
                     e_cell=h(L['e_cell'], ne), e_pdb=h(L['e_pdb'], ne).astype(np.float64), c_frame=h(L['c_frame'], nc),

@@ -404,6 +404,46 @@ def cell_extras(*, sigs=None, rds=None, rbins=None, dbins=None, esprit_scale=1 /
             to_host(ph[:N]) if want_phase else None)
 
 
+POINT_COLUMNS = ('range', 'doppler', 'az', 'x', 'y', 'power_db', 'range_offset', 'doppler_offset')
+
+
+def refine_cells(steer_c128: np.ndarray, az_deg_grid, *, rds, rbins, dbins, gidx=None, power=None, method='music',
+                 range_mode='hann', doppler_mode='rect', axes=(0.0, 1.0, 0.0, 1.0), ctx: Optional[Context] = None):
+    """The point cloud of the cells (rbins, dbins) of an RDS [A, S, C] (rsl_cell_refine, specified in include/rsl.h):
+    sub-bin range and Doppler offsets, the azimuth refined below the grid spacing, the position.  steer_c128 [G, A]
+    and az_deg_grid [G] describe the scan's grid; gidx=None runs ops.doa(method) first.  power: the antenna-summed map
+    [S, C] (ops.integrate_power) or None: formed from the RDS.  axes = (r0, r_step, d0, d_step)
+    (tables.point_axes).  Returns a dict of host arrays: the f32 columns POINT_COLUMNS of the row (az in radians),
+    'points' f32 [N, 8] (the rows as written), 'az_refined' f64 [N] (radians), 'azimuth_deg' f64 [N] and 'gidx'."""
+    c = _ctx(ctx)
+    st = np.asarray(steer_c128)
+    grid = np.asarray(az_deg_grid, np.float64)
+    if st.ndim != 2 or grid.shape != (st.shape[0],):
+        raise ValueError('refine_cells: steer_c128 [G, A] and az_deg_grid [G] expected')
+    d, fr, rc, N = _rds_cells(c, rds, rbins, dbins)
+    if d.shape[1] != st.shape[1]:
+        raise ValueError(f'refine_cells: RDS of {d.shape[1]} antennas, steering matrix of {st.shape[1]}')
+    if gidx is None:
+        gidx, _ = doa(method, st, rds=d, rbins=rbins, dbins=dbins, ctx=c)
+    gi = np.asarray(gidx, dtype=np.int32)
+    if gi.shape != (N,):
+        raise ValueError(f'refine_cells: gidx must have one entry per cell ({N})')
+    if N == 0:
+        res = {k: np.zeros(0, np.float32) for k in POINT_COLUMNS}
+        res.update(points=np.zeros((0, 8), np.float32), az_refined=np.zeros(0), azimuth_deg=np.zeros(0), gidx=gi)
+        return res
+    pw = None
+    if power is not None:
+        pw = power if _is_dev(power) else c.to_dev(np.asarray(power, dtype=np.float32))
+        pw = pw.reshape(-1, pw.shape[-2], pw.shape[-1]).contiguous()
+    pts, az = c.cell_refine(d, fr, rc, c.to_dev(gi), c.to_dev(np.radians(grid)), c.steering_c64(st), n=N, power=pw,
+                            range_mode=range_mode, doppler_mode=doppler_mode, axes=axes)
+    pts, az = to_host(pts[:N]), to_host(az[:N])
+    res = {k: pts[:, i] for i, k in enumerate(POINT_COLUMNS)}
+    res.update(points=pts, az_refined=az, azimuth_deg=np.degrees(az), gidx=gi)
+    return res
+
+
 def confidence(sigs, az_deg: Sequence[float], antenna_positions, lambda_c, ctx: Optional[Context] = None):
     """compute_angle_confidence for N (signature, angle) pairs (robust_angle_estimation.py:88-138)."""
     c = _ctx(ctx)

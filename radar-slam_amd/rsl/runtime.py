@@ -502,6 +502,45 @@ class Context:
                                             _ptr(esp), _ptr(ph), _ptr(az)), 'rsl_cell_extras')
         return sig, esp, ph, az
 
+    def cell_refine(self, rds, c_frame, c_rc, gidx, az_table, steer_c64, *, n: Optional[int] = None, n_dev=None,
+                    power=None, range_mode='hann', doppler_mode='rect', axes=(0.0, 1.0, 0.0, 1.0),
+                    want_points: bool = True, want_az: bool = True, out=None):
+        """The point cloud of a cell list (rsl_cell_refine; specified in include/rsl.h): sub-bin range and Doppler
+        offsets from the five powers around each cell, the azimuth at the parabola vertex around gidx, the position.
+        gidx i32 [n]; az_table f64 [G] radians; steer_c64 device c64 [G, A] (steering_c64); power f32 [F, S, C]
+        (integrate_power) or None: the powers are then formed from rds.  range_mode / doppler_mode: 'none' | 'log' |
+        'rect' | 'hann' or the _lib.REFINE_* id; axes = (r0, r_step, d0, d_step) (tables.point_axes).  out: optional
+        dict of preallocated points f32 [cap, 8] / az f64 [cap].  Returns (points, az), None where not requested; slots
+        beyond n = min(*n_dev, cap) are left as they were."""
+        torch = self.torch
+        _, A, S, C = rds.shape
+
+        def mode_id(m, what):
+            if isinstance(m, str):
+                if m not in _lib.REFINE_IDS:
+                    raise ValueError(f"cell_refine: {what} must be 'none', 'log', 'rect' or 'hann', not {m!r}")
+                return _lib.REFINE_IDS[m]
+            return int(m)
+        rm, dm = mode_id(range_mode, 'range_mode'), mode_id(doppler_mode, 'doppler_mode')
+        if steer_c64 is not None and (steer_c64.dim() != 2 or steer_c64.dtype != torch.complex64 or
+                                      int(steer_c64.shape[1]) != A):
+            raise ValueError(f'cell_refine: steer_c64 must be complex64 [G, {A}]')
+        G = int(steer_c64.shape[0]) if steer_c64 is not None else 0
+        if az_table is not None and int(az_table.shape[0]) != G:
+            raise ValueError(f'cell_refine: az_table must have the steering table\'s {G} entries')
+        if power is not None and (power.dtype != torch.float32 or tuple(power.shape[-2:]) != (S, C)):
+            raise ValueError('cell_refine: power must be float32 [F, S, C]')
+        cap = int(c_frame.shape[0]) if n is None else int(n)
+        rows = max(cap, 1)
+        pts = self._buf(out, 'points', (rows, 8), torch.float32) if want_points else (out or {}).get('points')
+        az = self._buf(out, 'az', (rows,), torch.float64) if want_az else (out or {}).get('az')
+        a4 = (c_double * 4)(*[float(x) for x in axes])
+        self._bind()
+        self.check(self.lib.rsl_cell_refine(self.h, _ptr(rds), _ptr(power), A, S, C, _ptr(c_frame), _ptr(c_rc),
+                                            _ptr(n_dev), cap, _ptr(gidx), _ptr(az_table), _ptr(steer_c64), G, rm, dm,
+                                            a4, _ptr(pts), _ptr(az)), 'rsl_cell_refine')
+        return pts, az
+
     def confidence(self, rds, c_frame, c_rc, gidx, steer, n: int):
         torch = self.torch
         _, A, S, C = rds.shape

@@ -65,6 +65,34 @@ def range_gate(bandwidth, S, min_range, max_range):
     return int(ok[0]), int(ok[-1])
 
 
+def refine_mode_for_window(window_type: str) -> str:
+    """The range-axis offset estimator of rsl_cell_refine that suits a fast-time window: the amplitude ratio for
+    'hann' (its main lobe has the closed form), the log-parabola for 'hamming' and 'blackman'.  The Doppler axis is
+    unwindowed (dechirp.py:143-166 windows fast time only) and takes 'rect'."""
+    if window_type == 'hann':
+        return 'hann'
+    if window_type in ('hamming', 'blackman'):
+        return 'log'
+    raise ValueError(f"Unknown window type: {window_type}")
+
+
+def point_axes(cfg, S: int, C: int, velocity: bool = False):
+    """(r0, r_step, d0, d_step) of rsl_cell_refine for a configuration with ``bandwidth`` and ``sampling_rate`` (a
+    ChainConfig, or anything with these attributes).  The default reproduces the reference's labels at integer bins
+    (dechirp.py:241-242: linspace(0, rr S, S) and linspace(-fs / 2, fs / 2, C)).  velocity=True labels the Doppler
+    axis in metres per second instead, from ``fc`` and ``pri``: bin C // 2 is 0 and one bin is lambda / (2 C pri)."""
+    S, C = int(S), int(C)
+    rr = C_LIGHT / (2 * cfg.bandwidth)
+    r_step = rr * S / (S - 1) if S > 1 else rr
+    if velocity:
+        d_step = (C_LIGHT / cfg.fc) / (2.0 * C * cfg.pri)
+        d0 = -(C // 2) * d_step
+    else:
+        d_step = cfg.sampling_rate / (C - 1) if C > 1 else cfg.sampling_rate
+        d0 = -cfg.sampling_rate / 2
+    return (0.0, float(r_step), float(d0), float(d_step))
+
+
 def power_threshold(threshold_db: float) -> float:
     return float(10.0 ** (threshold_db / 10.0) - 1e-12)
 

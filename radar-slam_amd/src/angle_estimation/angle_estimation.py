@@ -126,6 +126,39 @@ class AngleEstimator:
         logger.info(f"Processed {len(targets)} targets using {method}")
         return targets
 
+    def process_targets_refined(self, rds: np.ndarray, peak_info: Dict, method: str = 'music',
+                                window_type: str = 'hann') -> List[Dict]:
+        """process_targets plus the point cloud (ops.refine_cells): every target dict gains 'range_m_refined',
+        'doppler_hz_refined', 'azimuth_deg_refined', 'x_m', 'y_m', 'range_offset' and 'doppler_offset', refined below
+        the bin and grid spacing from the antenna-summed power around the cell and the beamforming values around the
+        scan's argmax.  The labels continue the targets' own axes: one range (Doppler) bin is the spacing of the
+        peaks' 'range_m' ('doppler_hz') labels, taken from peak_info['range_bins_m'] / ['doppler_bins_hz'] (the
+        axes extract_range_doppler_peaks returns) where given, else the columns count bins.  window_type: the fast-time window the RDS was formed with (it selects the range estimator).
+        method 'esprit' has no grid index; its targets are refined around the MUSIC argmax."""
+        targets = self.process_targets(rds, peak_info, method)
+        if not targets:
+            return targets
+        A, S, C = rds.shape
+        rb = np.array([t['range_bin'] % S for t in targets], dtype=np.int64)
+        db = np.array([t['doppler_bin'] % C for t in targets], dtype=np.int64)
+
+        def axis(name, n):  # (origin, step) of a label axis: the peak dictionary's own where it carries one
+            ax = peak_info.get(name) if hasattr(peak_info, 'get') else None
+            if ax is not None and len(ax) == n and n > 1:
+                return float(ax[0]), float(ax[-1] - ax[0]) / (n - 1)
+            return 0.0, 1.0
+        r0, r_step = axis('range_bins_m', S)
+        d0, d_step = axis('doppler_bins_hz', C)
+        res = ops.refine_cells(self._steer, self.azimuth_grid, rds=rds, rbins=rb, dbins=db,
+                               method='beamforming' if method == 'beamforming' else 'music',
+                               range_mode=tables.refine_mode_for_window(window_type), doppler_mode='rect',
+                               axes=(r0, r_step, d0, d_step))
+        for n, t in enumerate(targets):
+            t.update(range_m_refined=float(res['range'][n]), doppler_hz_refined=float(res['doppler'][n]),
+                     azimuth_deg_refined=float(res['azimuth_deg'][n]), x_m=float(res['x'][n]), y_m=float(res['y'][n]),
+                     range_offset=float(res['range_offset'][n]), doppler_offset=float(res['doppler_offset'][n]))
+        return targets
+
     def process_targets_smoothed(self, rds: np.ndarray, peaks: Dict, num_sources: int = 0, sub_len: Optional[int] = None,
                                  rel: float = 0.05, max_sources: int = 3) -> List[Dict]:
         """process_targets with the forward-backward spatially smoothed MUSIC (ops.doa_smoothed): several angles per
