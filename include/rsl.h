@@ -501,6 +501,55 @@ int rsl_velocity_consensus(rsl_handle h, const void* az, const void* gidx, const
                            int refine, unsigned long long seed, long long frame0,
                            void* out, void* weight, void* resid);
 
+/* Scan registration: the yaw increment and the displacement between the point clouds of consecutive frames
+ *     (rsl_register.hip, k_scan_register; the reference project has no counterpart, this comment is the
+ *     specification).  The Doppler solve of one radar observes only (v_x, v_y); this supplies the rotation.
+ *     Inputs (device unless marked host): points f32 [n][8], the rows of rsl_cell_refine (columns 3, 4 = x, y);
+ *     seg i64 [F + 1] (cell_base), both ends of every frame clamped to [0, n] as the velocity solvers do; weight f32 [n]
+ *     (nullable = 1): a point with a non-finite x or y, or a weight that is not > 0, has weight 0; rc i32 [n]
+ *     (nullable) with C and axes4 (host) = {r0, r_step, ., .} as in rsl_cell_refine, used for culling only (below);
+ *     prev_points / prev_weight / prev_rc (nullable): the cloud frame 0 is registered against, its length
+ *     min(prev_n, *prev_n_dev) (prev_n_dev i64 [1], nullable); init f64 [F][3] (nullable = zeros), the start
+ *     (theta, t_x, t_y) of every frame, a component that is not finite counting as 0.
+ *     Frame pairs: frame f >= 1 is the current cloud P (p_i, w_i), frame f - 1 the reference cloud Q (q_j, u_j);
+ *     frame 0 uses prev_*, and without prev_points gets the row {0, 0, 0, 0, 0, 0, 0, 2}.
+ *     Unknown: T = (theta, t), p' = R(theta) p + t, which maps current sensor coordinates into the previous frame's:
+ *     theta is the yaw increment, t the displacement expressed in the previous body frame.
+ *     Kernel: a_ij(T, h) = max(0, 1 - |R(theta) p_i + t - q_j|^2 (1 / h^2)), the biweight kernel: support of radius h,
+ *     continuous at the cut-off, no transcendental.
+ *     Coarse stage (yaw only, the translation trusted to the start t0): theta_k = theta0 + k dtheta, |k| <= K,
+ *     S_k = sum_ij w_i u_j a_ij((theta_k, t0), h_coarse)^3; the first maximum wins and theta starts there.  If every
+ *     S_k is 0 (an empty cloud among them): the row is {theta0, t0_x, t0_y, 0, 0, 0, 0, 1}, no fine stage.
+ *     Fine stage, steps it = 0 .. iters - 1 (MM / IRLS): h_it = max(h, h_coarse shrink^it), the power formed by
+ *     repeated multiplication; g_ij = w_i u_j a_ij(T, h_it)^2; W = sum g, S_p = sum g p_i, S_q = sum g q_j,
+ *     D = sum g (p_i . q_j), X = sum g (p_ix q_jy - p_iy q_jx), E = sum g d_ij^2 (d the residual at T).  If
+ *     W <= w_min (or NaN): flag 1, T kept, stop.  Otherwise D_c = D - (S_p . S_q) / W, X_c = X - (S_p x S_q) / W,
+ *     theta <- atan2(X_c, D_c), t <- S_q / W - R(theta) S_p / W; stop once h_it == h and the largest change of the
+ *     three components is below tol.  This is the weighted 2-D Procrustes solution under Tukey's biweight loss summed
+ *     over all pairs; the loss is concave in d^2, so at a fixed h no step decreases sum w u a^3.
+ *     All sums are fp64 (per thread in a fixed order, then rsl_reduce.h), the pair arithmetic fp64 from the fp32
+ *     coordinates: the centred moments cancel many digits at 100 m.  No atomics: rows are run-to-run bit-identical.
+ *     out f64 [F][8] = {theta, t_x, t_y, W, rms = sqrt(E / W), S_best / sum_k S_k, updates applied, flag}; W and E are
+ *     those of the last step evaluated, i.e. at the T before the last update (0 when iters = 0; rms 0 when W = 0).
+ *     omega f64 [F][3] (nullable): frame f's theta goes as {0, 0, theta_f / dt} into row f - 1 (rsl_traj_scan's
+ *     convention R_i = R_{i-1} exp(omega_{i-1} dt)), for every flag; row F - 1 is 0.
+ *     Culling is implementation, not result: with rc, the partners of a transformed point at range rho' are searched
+ *     in the range rows i whose label interval r0 + r_step (i -+ 0.5) meets [rho' - h_it, rho' + h_it], one more row on
+ *     each side for the fp32 rounding of the labels (coarse stage: all rho' the candidates can give), found by binary
+ *     search on rc inside the reference's segment (rc ascends inside a frame).  Without rc every pair is tested.
+ *     One workgroup per frame pair, the whole loop inside the kernel: a call with F = 2 uses one CU.
+ *     RSL_ERR_INVALID: h, h_coarse, dtheta, dt or w_min not finite, or h, h_coarse, dtheta, dt <= 0, or w_min < 0;
+ *     tol NaN; h_coarse < h; K outside 0 .. RSL_REG_MAX_K; iters outside 0 .. RSL_REG_MAX_ITERS; shrink outside (0, 1];
+ *     F, n or prev_n < 0; null points, seg or out with F > 0; rc or prev_rc given with null axes4, C <= 0, or an
+ *     r_step that is not finite and > 0.  F = 0 launches nothing.  Timed under RSL_K_AUX. */
+#define RSL_REG_MAX_K 64
+#define RSL_REG_MAX_ITERS 100
+int rsl_scan_register(rsl_handle h, const void* points, const void* seg, int F, long long n, const void* weight,
+                      const void* rc, int C, const double* axes4, const void* prev_points, const void* prev_weight,
+                      const void* prev_rc, long long prev_n, const void* prev_n_dev, const void* init, double h_fine,
+                      double h_coarse, double dtheta, int K, int iters, double shrink, double tol, double w_min,
+                      double dt, void* out, void* omega);
+
 /* a3-a6  SignalPreprocessor.dechirp_signal / apply_window / remove_dc / process_chirp (dechirp.py:85-166):
  *     out[r, s] = in[r, s] * table[s], then (dc != 0) minus the row's complex mean.  in/out c64 [rows, S]. */
 int rsl_preprocess_rows(rsl_handle h, const void* in, long long rows, int S, const void* table, int dc, void* out);

@@ -754,6 +754,42 @@ int rsl_velocity_consensus(rsl_handle h, const void* az, const void* gidx, const
                    "velocity_consensus");
 }
 
+int rsl_scan_register(rsl_handle h, const void* points, const void* seg, int F, long long n, const void* weight,
+                      const void* rc, int C, const double* axes4, const void* prev_points, const void* prev_weight,
+                      const void* prev_rc, long long prev_n, const void* prev_n_dev, const void* init, double h_fine,
+                      double h_coarse, double dtheta, int K, int iters, double shrink, double tol, double w_min,
+                      double dt, void* out, void* omega) {
+  if (!h) return RSL_ERR_INVALID;
+  auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+  const bool cull = rc || prev_rc;
+  const char* why = !(pos(h_fine) && pos(h_coarse) && pos(dtheta) && pos(dt))
+                        ? "h, h_coarse, dtheta and dt must be finite, > 0"
+                    : !(std::isfinite(w_min) && w_min >= 0.0)                ? "w_min must be finite, >= 0"
+                    : std::isnan(tol)                                        ? "tol is NaN"
+                    : h_coarse < h_fine                                      ? "h_coarse < h"
+                    : (K < 0 || K > RSL_REG_MAX_K)                           ? "K outside 0..RSL_REG_MAX_K"
+                    : (iters < 0 || iters > RSL_REG_MAX_ITERS)               ? "iters outside 0..RSL_REG_MAX_ITERS"
+                    : !(shrink > 0.0 && shrink <= 1.0)                       ? "shrink outside (0, 1]"
+                    : (F < 0 || n < 0 || prev_n < 0)                         ? "negative count"
+                    : (cull && (!axes4 || C <= 0 || !pos(axes4[1]) || !std::isfinite(axes4[0])))
+                        ? "rc needs C > 0 and axes4 with a finite r0 and a finite r_step > 0"
+                    : (F > 0 && (!points || !seg || !out)) ? "null points, seg or out"
+                                                           : nullptr;
+  if (why) {
+    const std::string msg = std::string("rsl_scan_register: ") + why;
+    return fail(h, RSL_ERR_INVALID, msg.c_str());
+  }
+  if (F == 0) return RSL_OK;
+  const rsl::RegProblem p{(const float*)points, (const long long*)seg, n, F, (const float*)weight, (const int*)rc,
+                          cull ? C : 1, cull ? axes4[0] : 0.0, cull ? 1.0 / axes4[1] : 0.0,
+                          (const float*)prev_points, prev_points ? (const float*)prev_weight : nullptr,
+                          prev_points ? (const int*)prev_rc : nullptr, prev_points ? prev_n : 0,
+                          prev_points ? (const long long*)prev_n_dev : nullptr, (const double*)init, h_fine, h_coarse,
+                          dtheta, K, iters, shrink, tol, w_min, dt};
+  Scope sc(h, RSL_K_AUX);
+  return hip_check(h, rsl::launch_scan_register(h->stream, p, (double*)out, (double*)omega), "scan_register");
+}
+
 int rsl_preprocess_rows(rsl_handle h, const void* in, long long rows, int S, const void* table, int dc, void* out) {
   if (!h) return RSL_ERR_INVALID;
   if (rows < 0 || S <= 0 || !in || !table || !out) return fail(h, RSL_ERR_INVALID, "rsl_preprocess_rows: bad argument");

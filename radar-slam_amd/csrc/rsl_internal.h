@@ -173,6 +173,29 @@ hipError_t launch_velocity_consensus(hipStream_t st, const VelProblem& p, double
                                      double min_det, int refine, unsigned long long seed, long long frame0, double* out,
                                      float* weight, double* resid);
 
+// Scan registration (rsl_register.hip; the contract is rsl_scan_register's in rsl.h), checked and typed by
+// rsl_scan_register (rsl_api.hip).  Passed to the kernel by value.  inv_step = 1 / axes4[1], 0 without axes.
+struct RegProblem {
+  const float* points;
+  const long long* seg;
+  long long n;
+  int F;
+  const float* weight;
+  const int* rc;
+  int C;
+  double r0, inv_step;
+  const float* prev_points;
+  const float* prev_weight;
+  const int* prev_rc;
+  long long prev_n;
+  const long long* prev_n_dev;
+  const double* init;
+  double h, h_coarse, dtheta;
+  int K, iters;
+  double shrink, tol, w_min, dt;
+};
+hipError_t launch_scan_register(hipStream_t st, const RegProblem& p, double* out, double* omega);
+
 // K9: greedy association and wrapped-phase multi-start solve (rsl_wrap.hip).
 // configs[3] pattern (rsl_scene.hip): per-cube top-k peak selection and the analyser's nearest association.
 hipError_t launch_topk_entries(hipStream_t st, const long long* entry_base, long long entry_cap, int ncube,

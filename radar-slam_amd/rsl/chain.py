@@ -109,8 +109,41 @@ class ChainConfig:
                                                # (tables.point_axes(velocity=True)) instead of the reference's hertz
     velocity_az: str = 'grid'                  # 'grid': the solvers read az_table[gidx]; 'refined': the refined
                                                # azimuths of the point cloud (needs point_cloud)
+    registration: bool = False                 # also register every frame's point cloud against the frame before it
+                                               # (rsl_scan_register, after the velocity solve; needs point_cloud):
+                                               # results()['registration'] f64 [F, 8] = {theta, t_x, t_y, W, rms,
+                                               # S_best / sum S, updates, flag} and chain.omega f64 [F, 3] for
+                                               # TrajectoryReducer.step(chain.vel, ..., omega=chain.omega).  The start
+                                               # is (0, v_x dt, v_y dt) from the velocity rows; a robust or consensus
+                                               # solver's vel_weight keeps the movers from voting; the chain's last
+                                               # frame is kept as the next run's reference (reset_registration()).
+                                               # False: nothing is allocated or launched
+    reg_h: float = 0.5                         # the kernel's final radius, metres
+    reg_h_coarse: float = 1.0                  # the radius of the yaw search and of the first step
+    reg_dtheta: float = math.radians(0.25)     # the yaw search's step, radians
+    reg_k: int = 20                            # candidates on each side of the start yaw, 0 .. _lib.REG_MAX_K
+    reg_iters: int = 10                        # MM / IRLS steps, 0 .. _lib.REG_MAX_ITERS
+    reg_shrink: float = 0.7                    # the radius' factor per step, (0, 1]
+    reg_tol: float = 1e-9                      # stop below this change of (theta, t_x, t_y)
+    reg_w_min: float = 3.0                     # the least kernel weight a step needs
 
     def __post_init__(self):
+        if self.registration:
+            if not self.point_cloud:
+                raise ValueError('registration=True needs point_cloud=True')
+            pos = lambda v: math.isfinite(float(v)) and float(v) > 0.0
+            if not (pos(self.reg_h) and pos(self.reg_h_coarse) and pos(self.reg_dtheta) and pos(self.dt)):
+                raise ValueError('registration needs reg_h, reg_h_coarse, reg_dtheta and dt finite and > 0')
+            if float(self.reg_h_coarse) < float(self.reg_h):
+                raise ValueError(f'reg_h_coarse {self.reg_h_coarse!r} is below reg_h {self.reg_h!r}')
+            if not 0 <= int(self.reg_k) <= _lib.REG_MAX_K:
+                raise ValueError(f'reg_k must lie in [0, {_lib.REG_MAX_K}], not {self.reg_k!r}')
+            if not 0 <= int(self.reg_iters) <= _lib.REG_MAX_ITERS:
+                raise ValueError(f'reg_iters must lie in [0, {_lib.REG_MAX_ITERS}], not {self.reg_iters!r}')
+            if not 0.0 < float(self.reg_shrink) <= 1.0:
+                raise ValueError(f'reg_shrink must lie in (0, 1], not {self.reg_shrink!r}')
+            if not (math.isfinite(float(self.reg_w_min)) and float(self.reg_w_min) >= 0.0):
+                raise ValueError(f'reg_w_min must be finite and >= 0, not {self.reg_w_min!r}')
         if self.velocity_az not in ('grid', 'refined'):
             raise ValueError(f"velocity_az must be 'grid' or 'refined', not {self.velocity_az!r}")
         if self.velocity_az == 'refined' and not self.point_cloud:
@@ -276,6 +309,17 @@ class RadarChain:
             if self.power is None:  # detect_on='antenna': no summed map yet, run_back integrates it
                 self.power = e((F, S, C), torch.float32)
             self.pc = dict(points=e((cc, 8), torch.float32), az=e((cc,), torch.float64))
+        self.reg = None
+        self.omega = None
+        if cfg.registration:  # scan registration: one row per frame, and the last frame's cloud kept for the next run
+            fc = S * C  # the most cells of one frame
+            self.reg = dict(rows=e((F, 8), torch.float64), omega=e((F, 3), torch.float64))
+            self.omega = self.reg['omega']
+            self.reg_init = e((F, 3), torch.float64)
+            self.reg_keep = dict(points=e((fc, 8), torch.float32), rc=e((fc,), torch.int32), n_dev=e((1,), torch.int64),
+                                 weight=e((fc,), torch.float32) if self.vel_weight is not None else None)
+            self.reg_prev = None  # reg_keep once a run has filled it
+            self.reg_idx = torch.arange(fc, dtype=torch.int64, device=ctx.device)
         # one signature gather for DoA + ESPRIT + phase when the Toeplitz path applies (uniform linear array)
         self.fused_doa = bool(self.steer['toeplitz']) and A >= 2 and not cfg.spectrum
         self.spec = None
@@ -410,6 +454,36 @@ class RadarChain:
                                 iters=cfg.velocity_iters, tol=cfg.velocity_tol, want_weight=self.vel_weight)
         else:
             ctx.velocity(**prob)
+        if self.reg is not None:
+            self._register()
+
+    def _register(self):
+        """Scan registration of the batch (after the velocity solve), then the batch's last frame into reg_keep."""
+        ctx, cfg, torch = self.ctx, self.cfg, self.ctx.torch
+        init = self.reg_init
+        init[:, 0] = 0.0
+        torch.mul(self.vel[:, :2], float(cfg.dt), out=init[:, 1:])  # the Doppler displacement v dt
+        ctx.scan_register(self.pc['points'], self.offs['cell_base'], weight=self.vel_weight, rc=self.lists['c_rc'],
+                          C=self.C, axes=self.pc_axes, prev=self.reg_prev, init=init, h=cfg.reg_h,
+                          h_coarse=cfg.reg_h_coarse, dtheta=cfg.reg_dtheta, k=cfg.reg_k, iters=cfg.reg_iters,
+                          shrink=cfg.reg_shrink, tol=cfg.reg_tol, w_min=cfg.reg_w_min, dt=cfg.dt, n=self.cell_cap,
+                          out=self.reg)
+        # the last frame's rows, by device-side indices (no host synchronisation): rows past the frame's end are
+        # copies of the list's last slot and lie beyond n_dev
+        base = self.offs['cell_base'].clamp(0, self.cell_cap)
+        keep = self.reg_keep
+        idx = (self.reg_idx + base[self.F - 1]).clamp_(max=self.cell_cap - 1)
+        torch.index_select(self.pc['points'], 0, idx, out=keep['points'])
+        torch.index_select(self.lists['c_rc'], 0, idx, out=keep['rc'])
+        if keep['weight'] is not None:
+            torch.index_select(self.vel_weight, 0, idx, out=keep['weight'])
+        torch.sub(base[self.F:self.F + 1], base[self.F - 1:self.F], out=keep['n_dev'])
+        self.reg_prev = keep
+
+    def reset_registration(self):
+        """Forget the cloud kept from the last run: the next run's frame 0 has no reference (flag 2)."""
+        if self.reg is not None:
+            self.reg_prev = None
 
     def totals(self):
         eb = self.offs['entry_base'][self.F].item()
@@ -429,6 +503,8 @@ class RadarChain:
                          ss_den=h(self.ss['den'], nc).astype(np.float64))
         if self.ra is not None:  # f32 [F, S, G] and i32 [F, S]: every range bin of every frame
             extra.update(ra_map=self.ra['map'].cpu().numpy(), ra_arg=self.ra['arg'].cpu().numpy())
+        if self.reg is not None:
+            extra.update(registration=self.reg['rows'].cpu().numpy())
         if self.pc is not None:
             extra.update(points=h(self.pc['points'], nc), az_refined=h(self.pc['az'], nc))
         return dict(entry_base=self.offs['entry_base'].cpu().numpy(), cell_base=self.offs['cell_base'].cpu().numpy(),

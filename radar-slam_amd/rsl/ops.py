@@ -444,6 +444,52 @@ def refine_cells(steer_c128: np.ndarray, az_deg_grid, *, rds, rbins, dbins, gidx
     return res
 
 
+REGISTRATION_COLUMNS = ('theta', 't_x', 't_y', 'support', 'rms', 'peak_ratio', 'updates', 'flag')
+
+
+def register_scans(points, seg, *, weight=None, rc=None, C: int = 0, axes=None, prev=None, init=None,
+                   ctx: Optional[Context] = None, **params):
+    """Scan registration of F point clouds, each against the one before it (rsl_scan_register, specified in
+    include/rsl.h): points f32 [N, 8] (the rows of refine_cells / the chain's 'points'; columns 3 and 4 are x and y),
+    seg [F + 1] the frames' first rows (the chain's cell_base), weight [N] or None (the static / moving labels:
+    'vel_weight'), rc i32 [N] with C and axes (tables.point_axes) to cull the pair search by range rows, prev: None or
+    dict(points, weight, rc) of the cloud frame 0 is registered against, init f64 [F, 3] = (theta, t_x, t_y) start
+    values (the Doppler displacement v dt).  params: h, h_coarse, dtheta, k, iters, shrink, tol, w_min, dt
+    (Context.scan_register).  Host arrays or device tensors.  Returns a dict of host arrays: 'rows' f64 [F, 8] =
+    REGISTRATION_COLUMNS, each column under its name, and 'omega' f64 [F, 3] for rsl_traj_scan
+    (omega[f - 1] = {0, 0, theta_f / dt})."""
+    c = _ctx(ctx)
+    torch = c.torch
+
+    def dev(x, dtype, npdtype):
+        if x is None:
+            return None
+        if _is_dev(x):
+            return (x if x.dtype == dtype else x.to(dtype)).contiguous()
+        return c.to_dev(np.ascontiguousarray(np.asarray(x, dtype=npdtype)))
+    pts = dev(points, torch.float32, np.float32)
+    if pts.dim() != 2 or int(pts.shape[1]) != 8:
+        raise ValueError('register_scans: points [N, 8] expected')
+    sg = dev(seg, torch.int64, np.int64)
+    if sg.dim() != 1 or int(sg.shape[0]) < 1:
+        raise ValueError('register_scans: seg [F + 1] expected')
+    pv = None
+    if prev is not None and prev.get('points') is not None:
+        pv = dict(points=dev(prev['points'], torch.float32, np.float32).reshape(-1, 8),
+                  weight=dev(prev.get('weight'), torch.float32, np.float32),
+                  rc=dev(prev.get('rc'), torch.int32, np.int32), n=prev.get('n'), n_dev=prev.get('n_dev'))
+    F = int(sg.shape[0]) - 1
+    it = dev(init, torch.float64, np.float64)
+    if it is not None:
+        it = it.reshape(F, 3)
+    rows, om = c.scan_register(pts, sg, weight=dev(weight, torch.float32, np.float32),
+                               rc=dev(rc, torch.int32, np.int32), C=C, axes=axes, prev=pv, init=it, **params)
+    rows, om = to_host(rows[:F]), to_host(om[:F])
+    res = {k: rows[:, i] for i, k in enumerate(REGISTRATION_COLUMNS)}
+    res.update(rows=rows, omega=om)
+    return res
+
+
 def confidence(sigs, az_deg: Sequence[float], antenna_positions, lambda_c, ctx: Optional[Context] = None):
     """compute_angle_confidence for N (signature, angle) pairs (robust_angle_estimation.py:88-138)."""
     c = _ctx(ctx)

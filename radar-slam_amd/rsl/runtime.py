@@ -541,6 +541,56 @@ class Context:
                                             a4, _ptr(pts), _ptr(az)), 'rsl_cell_refine')
         return pts, az
 
+    def scan_register(self, points, seg, *, weight=None, rc=None, C: int = 0, axes=None, prev=None, init=None,
+                      h: float = 0.5, h_coarse: float = 1.0, dtheta: float = math.radians(0.25), k: int = 20,
+                      iters: int = 10, shrink: float = 0.7, tol: float = 1e-9, w_min: float = 3.0, dt: float = 0.1,
+                      n: Optional[int] = None, want_omega: bool = True, out=None):
+        """Scan registration (rsl_scan_register; the estimator is specified in include/rsl.h): the yaw increment and
+        the displacement of every frame's point cloud against the frame before it.  points f32 [N, 8] (the rows of
+        cell_refine), seg i64 [F + 1] (cell_base; clamped to n, default N), weight f32 [N] or None, rc i32 [N] or None
+        with C and axes = (r0, r_step, ...) (tables.point_axes) for the culling, init f64 [F, 3] or None.  prev: None,
+        or a dict of the cloud frame 0 is registered against: points f32 [M, 8], and optionally weight f32 [M], rc i32
+        [M], n (rows in use, default M) and n_dev (device i64 [1], the rows in use where only the device knows them).
+        out: optional dict of preallocated rows f64 [F, 8] / omega f64 [F, 3].  Returns (rows, omega or None):
+        rows = {theta, t_x, t_y, W, rms, S_best / sum S, updates, flag}, omega[f - 1] = {0, 0, theta_f / dt}."""
+        torch = self.torch
+        F = int(seg.shape[0]) - 1
+        if points.dim() != 2 or int(points.shape[1]) != 8 or points.dtype != torch.float32 or not points.is_contiguous():
+            raise ValueError('scan_register: points must be contiguous float32 [N, 8]')
+        N = int(points.shape[0]) if n is None else min(int(n), int(points.shape[0]))
+        if int(points.shape[0]) == 0:  # an empty tensor has no address; the function wants one
+            points = self.empty((1, 8), torch.float32)
+
+        def per_point(t, dtype, rows, what):
+            if t is not None and (t.dtype != dtype or t.dim() != 1 or int(t.shape[0]) < rows):
+                raise ValueError(f'scan_register: {what} must be {dtype} with one entry per point')
+        per_point(weight, torch.float32, N, 'weight')
+        per_point(rc, torch.int32, N, 'rc')
+        pv = dict(prev) if prev else {}
+        pp = pv.get('points')
+        M = 0
+        if pp is not None:
+            if pp.dim() != 2 or int(pp.shape[1]) != 8 or pp.dtype != torch.float32 or not pp.is_contiguous():
+                raise ValueError('scan_register: prev points must be contiguous float32 [M, 8]')
+            M = int(pp.shape[0]) if pv.get('n') is None else min(int(pv['n']), int(pp.shape[0]))
+            if int(pp.shape[0]) == 0:  # an empty reference is still a reference (flag 1, not 2)
+                pp = self.empty((1, 8), torch.float32)
+            per_point(pv.get('weight'), torch.float32, M, 'prev weight')
+            per_point(pv.get('rc'), torch.int32, M, 'prev rc')
+        if init is not None and (init.dtype != torch.float64 or tuple(init.shape) != (F, 3) or
+                                 not init.is_contiguous()):
+            raise ValueError(f'scan_register: init must be contiguous float64 [{F}, 3]')
+        rows = self._buf(out, 'rows', (max(F, 1), 8), torch.float64)
+        om = self._buf(out, 'omega', (max(F, 1), 3), torch.float64) if want_omega else None
+        a4 = (c_double * 4)(*[float(x) for x in axes]) if axes is not None else None
+        self._bind()
+        self.check(self.lib.rsl_scan_register(
+            self.h, _ptr(points), _ptr(seg), F, N, _ptr(weight), _ptr(rc), int(C), a4, _ptr(pp),
+            _ptr(pv.get('weight')), _ptr(pv.get('rc')), M, _ptr(pv.get('n_dev')), _ptr(init), float(h),
+            float(h_coarse), float(dtheta), int(k), int(iters), float(shrink), float(tol), float(w_min), float(dt),
+            _ptr(rows), _ptr(om)), 'rsl_scan_register')
+        return rows, om
+
     def confidence(self, rds, c_frame, c_rc, gidx, steer, n: int):
         torch = self.torch
         _, A, S, C = rds.shape

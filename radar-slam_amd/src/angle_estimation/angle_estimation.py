@@ -159,6 +159,27 @@ class AngleEstimator:
                      range_offset=float(res['range_offset'][n]), doppler_offset=float(res['doppler_offset'][n]))
         return targets
 
+    def register_scans(self, prev_targets: List[Dict], cur_targets: List[Dict], init=None, **params) -> Dict:
+        """The rigid motion between two scans of process_targets_refined (ops.register_scans, specified in
+        include/rsl.h as rsl_scan_register): the yaw increment and the displacement that map the current targets'
+        ('x_m', 'y_m') onto the previous scan's, p' = R(theta) p + t.  A target dict's optional 'weight' (0: a mover)
+        is its vote.  init = (theta, t_x, t_y) start values, e.g. (0, v_x dt, v_y dt) from the velocity solve;
+        params: h, h_coarse, dtheta, k, iters, shrink, tol, w_min.  Returns dict(theta_rad, theta_deg, t_x, t_y,
+        support, rms, peak_ratio, updates, flag); flag 1: too little overlap, the start values are returned."""
+        def rows(targets):
+            pts = np.zeros((len(targets), 8), np.float32)
+            for n, t in enumerate(targets):
+                pts[n, 3], pts[n, 4] = t['x_m'], t['y_m']
+            return pts, np.array([t.get('weight', 1.0) for t in targets], np.float32)
+        (pp, pw), (cp, cw) = rows(prev_targets), rows(cur_targets)
+        res = ops.register_scans(cp, np.array([0, len(cp)], np.int64), weight=cw, prev=dict(points=pp, weight=pw),
+                                 init=None if init is None else np.asarray(init, np.float64).reshape(1, 3), **params)
+        out = {k: float(res[k][0]) for k in ops.REGISTRATION_COLUMNS}
+        out['theta_rad'] = out.pop('theta')
+        out['theta_deg'] = float(np.degrees(out['theta_rad']))
+        out['updates'], out['flag'] = int(out['updates']), int(out['flag'])
+        return out
+
     def process_targets_smoothed(self, rds: np.ndarray, peaks: Dict, num_sources: int = 0, sub_len: Optional[int] = None,
                                  rel: float = 0.05, max_sources: int = 3) -> List[Dict]:
         """process_targets with the forward-backward spatially smoothed MUSIC (ops.doa_smoothed): several angles per
