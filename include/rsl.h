@@ -19,6 +19,8 @@
  *     K1 on two streams concurrently (the replays would share the captured queue);
  *   - F = 0 (an empty batch) is valid: nothing is launched (rsl_peak_offsets zeroes the two bases), and
  *     buffers sized by F may be null;
+ *   - a problem that needs more workgroups than a grid holds (2^31 - 1) is refused (RSL_ERR_HIP, "invalid argument"),
+ *     never cut down to the part that fits: that launch does not run, nor any after it in the same call;
  *   - capacity-sized lists (entries, cells) never overflow in memory: items past the capacity are dropped,
  *     the bases keep the true counts, and the list consumers stop at the capacity.
  */

@@ -82,7 +82,10 @@ float2* twiddles(rsl_context* h, int n) {
   }
   float2* d = nullptr;
   if (hipMalloc(&d, sizeof(float2) * n) != hipSuccess) return nullptr;
-  if (hipMemcpy(d, t.data(), sizeof(float2) * n, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+  if (hipMemcpy(d, t.data(), sizeof(float2) * n, hipMemcpyHostToDevice) != hipSuccess) {
+    hipFree(d);
+    return nullptr;
+  }
   h->tw[n] = d;
   return d;
 }
@@ -518,7 +521,6 @@ int rsl_doa(rsl_handle h, const void* rds, int A, int S, int C, const void* c_fr
   const SteerView tab = steer_view(steer_tab, G, A);
   const rsl::CellList cl = cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell);
   if (!ncell_dev && ncell <= 0) return RSL_OK;
-  hipSetDevice(h->device);
   Scope sc(h, RSL_K_DOA_SCAN);
   // the Toeplitz f16-MFMA scan: argmax only, or with the whole spectrum in the cell-blocked layout (no gmax there)
   const bool toep_spec = out_spec && (method & RSL_DOA_SPEC_BLOCKED) && !out_gmax;
@@ -553,7 +555,6 @@ int rsl_doa_extras(rsl_handle h, const void* rds, int A, int S, int C, const voi
   if (!tab.lay.toep_fits)
     return fail(h, RSL_ERR_UNSUPPORTED, "rsl_doa_extras: grid too large for the Toeplitz path (use rsl_doa)");
   if (!ncell_dev && ncell <= 0) return RSL_OK;
-  hipSetDevice(h->device);
   Scope sc(h, RSL_K_DOA_SCAN);
   return hip_check(h,
                    rsl::launch_doa_toep(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell), tab.toep,
@@ -578,7 +579,6 @@ int rsl_doa_smoothed(rsl_handle h, const void* rds, int A, int S, int C, const v
   if (!rds || !c_frame || !c_rc || !steer_sub_c64 || !out_nsrc || !out_idx)
     return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: null pointer");
   if (ncell <= 0) return RSL_OK;  // ncell is the launch bound (capacity) when ncell_dev is given
-  hipSetDevice(h->device);
   Scope sc(h, RSL_K_DOA_SCAN);
   return hip_check(h,
                    rsl::launch_doa_smoothed(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell),
@@ -844,7 +844,6 @@ int rsl_peak_topk(rsl_handle h, const void* entry_base, long long entry_cap, int
   if (ncube == 0) return RSL_OK;
   if (!entry_base || !sel_entry || !sel_frame || !sel_rc || !sel_n || (entry_cap > 0 && (!e_coord || !e_pdb)))
     return fail(h, RSL_ERR_INVALID, "rsl_peak_topk: null pointer");
-  hipSetDevice(h->device);
   Scope sc(h, RSL_K_AUX);
   // the reference compares float64 power_db > thr_db; the entries' power_db is f32, so compare against the largest
   // float <= thr_db (identical decisions for every f32 value)
@@ -863,7 +862,6 @@ int rsl_associate_nearest(rsl_handle h, const void* range_m, const void* az_rad,
   if (nframes == 0 || ntargets == 0) return RSL_OK;
   if (!range_m || !az_rad || !s0 || !off || !match || !dist || !phase)
     return fail(h, RSL_ERR_INVALID, "rsl_associate_nearest: null pointer");
-  hipSetDevice(h->device);
   Scope sc(h, RSL_K_AUX);
   return hip_check(h,
                    rsl::launch_associate_nearest(h->stream, (const double*)range_m, (const double*)az_rad,

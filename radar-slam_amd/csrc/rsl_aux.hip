@@ -48,8 +48,7 @@ __global__ __launch_bounds__(256) void k_preprocess_rows(const float2* __restric
 hipError_t launch_preprocess_rows(hipStream_t st, const float2* in, long rows, int S, const float2* table, int dc,
                                   float2* out) {
   if (rows <= 0 || S <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_preprocess_rows, dim3((unsigned)rows), dim3(256), 0, st, in, S, table, dc, out);
-  return hipGetLastError();
+  return launch(st, k_preprocess_rows, rows, 256, 0, in, S, table, dc, out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -86,8 +85,7 @@ __global__ __launch_bounds__(256) void k_phase_model(const double* __restrict__ 
 
 hipError_t launch_phase_model(hipStream_t st, const double* pos, const double* ang, long n, const double* x, double k,
                               const double* y, int wrap, double ridge, double* pred, double* resid, double* cost) {
-  hipLaunchKernelGGL(k_phase_model, dim3(1), dim3(256), 0, st, pos, ang, n, x, k, y, wrap, ridge, pred, resid, cost);
-  return hipGetLastError();
+  return launch(st, k_phase_model, 1, 256, 0, pos, ang, n, x, k, y, wrap, ridge, pred, resid, cost);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -261,8 +259,7 @@ __global__ __launch_bounds__(256) void k_bvls(const double* __restrict__ pos, co
 
 hipError_t launch_bvls(hipStream_t st, const double* pos, const double* ang, long n, const double* y, double k, int nv,
                        double ridge, const double* lo, const double* hi, double* out) {
-  hipLaunchKernelGGL(k_bvls, dim3(1), dim3(256), 0, st, pos, ang, n, y, k, nv, ridge, lo, hi, out);
-  return hipGetLastError();
+  return launch(st, k_bvls, 1, 256, 0, pos, ang, n, y, k, nv, ridge, lo, hi, out);
 }
 
 }  // namespace rsl

@@ -98,17 +98,10 @@ hipError_t launch_cfar_strips(hipStream_t st, void (*kernel)(KArgs...), size_t (
   else if (lds_bytes(C, win, 8) <= 48 * 1024) RB = 8;
   const size_t lds = lds_bytes(C, win, RB);
   if (lds > kCfarLdsMax) return hipErrorInvalidValue;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
   const int R = cfar_strip_rows(F, A, S);
   const long long nblk = (long long)F * A * ((S + R - 1) / R);
-  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), lds, st, rds, S, C, W, win, extra...,
-                     threshold_as_float(d.thr_p), d.i_lo, d.i_hi, R, RB, d.mask, d.row_count, d.dbmap, d.pk_pow);
-  return hipGetLastError();
+  return launch(st, kernel, nblk, 256, lds, rds, S, C, W, win, extra..., threshold_as_float(d.thr_p), d.i_lo, d.i_hi, R,
+                RB, d.mask, d.row_count, d.dbmap, d.pk_pow);
 }
 
 }  // namespace rsl

@@ -493,17 +493,15 @@ hipError_t launch_emit_compact(hipStream_t st, const unsigned long long* mask, c
   if (A > 32) return hipErrorInvalidValue;
   const int W = (C + 63) / 64;
   const int nbf = (S * W + kCellWords - 1) / kCellWords;
-  const unsigned nbe = (unsigned)(((long long)F * A * S * W + 255) / 256);
+  const long long nbe = ((long long)F * A * S * W + 255) / 256;
   return with_int<1, 2, 4, 8, 16, 32, 64>(W, [&](auto w) {
     constexpr int WW = decltype(w)::value;
-    hipLaunchKernelGGL((A <= 8 ? k_emit_cells<WW, 8> : A <= 16 ? k_emit_cells<WW, 16> : k_emit_cells<WW, 32>),
-                       dim3((unsigned)F * nbf), dim3(256), 0, st, mask, umask, nbf, A, S, C, cell_row_off, cell_base,
-                       cell_cap, c_frame, c_rc, c_amask);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_emit_entries<WW>, dim3(nbe), dim3(256), 0, st, mask, umask, pk_pow, pk_group, (long long)F, A,
-                       S, C, entry_row_off, cell_row_off, entry_base, cell_base, entry_cap, e_coord, e_cell, e_pdb);
-    return hipGetLastError();
+    const auto cells = A <= 8 ? k_emit_cells<WW, 8> : A <= 16 ? k_emit_cells<WW, 16> : k_emit_cells<WW, 32>;
+    if (hipError_t e = launch(st, cells, (long long)F * nbf, 256, 0, mask, umask, nbf, A, S, C, cell_row_off, cell_base,
+                              cell_cap, c_frame, c_rc, c_amask))
+      return e;
+    return launch(st, k_emit_entries<WW>, nbe, 256, 0, mask, umask, pk_pow, pk_group, (long long)F, A, S, C,
+                  entry_row_off, cell_row_off, entry_base, cell_base, entry_cap, e_coord, e_cell, e_pdb);
   });
 }
 
@@ -523,9 +521,8 @@ static hipError_t launch_detect_maps(hipStream_t st, const T* maps, int F, int A
   if (!rows) return hipErrorInvalidValue;
   const long nblk = (long)F * A * ((S + rows - 1) / rows);
   const size_t lds = sizeof(float) * (rows + 2) * (size_t)C;
-  hipLaunchKernelGGL(k_detect<T>, dim3((unsigned)nblk), dim3(256), lds, st, maps, S, C, W, rows,
-                     threshold_as_float(d.thr_p), d.i_lo, d.i_hi, d.mask, d.row_count, d.dbmap, d.pk_pow);
-  return hipGetLastError();
+  return launch(st, k_detect<T>, nblk, 256, lds, maps, S, C, W, rows, threshold_as_float(d.thr_p), d.i_lo, d.i_hi,
+                d.mask, d.row_count, d.dbmap, d.pk_pow);
 }
 
 hipError_t launch_detect(hipStream_t st, const float2* rds, int F, int A, int S, int C, const DetectArgs& d) {
@@ -542,12 +539,10 @@ hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const 
   if (F <= 0) return hipSuccess;
   const int W = (C + 63) / 64;
   // 256-thread blocks: 1024-thread ones waited for a whole CU to drain behind the other batch's DoA blocks
-  hipLaunchKernelGGL(k_offsets<256>, dim3(F), dim3(256), 0, st, mask, row_count, A, S, W, entry_row_off, cell_row_off,
-                     cell_row_cnt, frame_counts, umask);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_frame_scan<256>, dim3(1), dim3(256), 0, st, frame_counts, F, entry_base, cell_base);
-  return hipGetLastError();
+  if (hipError_t e = launch(st, k_offsets<256>, F, 256, 0, mask, row_count, A, S, W, entry_row_off, cell_row_off,
+                            cell_row_cnt, frame_counts, umask))
+    return e;
+  return launch(st, k_frame_scan<256>, 1, 256, 0, frame_counts, F, entry_base, cell_base);
 }
 
 hipError_t launch_emit_rows(hipStream_t st, const float2* rds, const unsigned long long* mask, int F, int A, int S,
@@ -557,10 +552,8 @@ hipError_t launch_emit_rows(hipStream_t st, const float2* rds, const unsigned lo
   if (F <= 0) return hipSuccess;
   const int W = (C + 63) / 64;
   const long rows = (long)F * S;
-  hipLaunchKernelGGL(k_emit, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rds, mask, F, A, S, C, W,
-                     entry_row_off, cell_row_off, entry_base, cell_base, entry_cap, cell_cap, e_coord,
-                     e_cell, e_pdb, c_frame, c_rc, c_amask);
-  return hipGetLastError();
+  return launch(st, k_emit, (rows + 3) / 4, 256, 0, rds, mask, F, A, S, C, W, entry_row_off, cell_row_off, entry_base,
+                cell_base, entry_cap, cell_cap, e_coord, e_cell, e_pdb, c_frame, c_rc, c_amask);
 }
 
 }  // namespace rsl

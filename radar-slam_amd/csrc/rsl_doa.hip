@@ -352,24 +352,16 @@ __global__ __launch_bounds__(256) void k_doa_argmax(CellList cl, const float4* _
   }
 }
 
-// Grid of a grid-striding scan kernel: the resident workgroups (occupancy x CUs; occ caches this kernel instance's
-// occupancy query), or the workgroups that cover the cells where the host knows their count and that is fewer.
+// Grid of a grid-striding scan kernel: the resident workgroups, or the workgroups that cover the cells where the host
+// knows their count and that is fewer.
 template <class K>
-static unsigned resident_blocks(K kern, size_t lds, int& occ, const CellList& cl, int cells_per_block) {
-  if (occ < 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
-    occ = nb;
-  }
-  int dev = 0, ncu = 256;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  long long blocks = (long long)occ * ncu;
+static long long scan_blocks(K kern, size_t lds, const CellList& cl, int cells_per_block) {
+  long long blocks = resident_blocks(kern, 256, lds);
   if (!cl.n_dev) {
     const long long need = (cl.n_host + cells_per_block - 1) / cells_per_block;
     if (blocks > need) blocks = need;
   }
-  return (unsigned)(blocks < 1 ? 1 : blocks);
+  return blocks < 1 ? 1 : blocks;
 }
 
 hipError_t launch_doa_scan(hipStream_t st, CellList cl, const float* steer_tab, int G, int music, int* out_idx,
@@ -388,21 +380,17 @@ hipError_t launch_doa_scan(hipStream_t st, CellList cl, const float* steer_tab, 
         return with_bool(out_gmax != nullptr, [&](auto gm) {
           constexpr int KS = decltype(ks)::value;
           constexpr bool FAST = decltype(fa)::value, MUSIC = decltype(mu)::value, GMAX = decltype(gm)::value;
-          static int per_cu[2][2] = {{-1, -1}, {-1, -1}};  // occupancy per CU: [argmax / scan][no LDS / LDS table]
           if constexpr (FAST && KS % 2 != 0) {
             return hipErrorInvalidValue;  // never: fast has KS even
           } else if (!out_spec) {  // argmax only
             constexpr int NCT = 4;
             auto kern = k_doa_argmax<KS, FAST, NCT, MUSIC, GMAX>;
-            const unsigned blocks = resident_blocks(kern, lds, per_cu[0][use_lds], cl, 4 * 16 * NCT);
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, st, cl, stp, ntiles, G, use_lds, out_idx, out_gmax);
-            return hipGetLastError();
+            return launch(st, kern, scan_blocks(kern, lds, cl, 4 * 16 * NCT), 256, lds, cl, stp, ntiles, G, use_lds,
+                          out_idx, out_gmax);
           } else {
             auto kern = k_doa_scan<KS, FAST, MUSIC, GMAX>;
-            const unsigned blocks = resident_blocks(kern, lds, per_cu[1][use_lds], cl, 4 * 32);
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, st, cl, stp, ntiles, G, use_lds, out_idx, out_gmax,
-                               out_spec, spec_ld);
-            return hipGetLastError();
+            return launch(st, kern, scan_blocks(kern, lds, cl, 4 * 32), 256, lds, cl, stp, ntiles, G, use_lds, out_idx,
+                          out_gmax, out_spec, spec_ld);
           }
         });
       });
@@ -484,9 +472,8 @@ hipError_t launch_cell_extras(hipStream_t st, CellList cl, double esprit_scale, 
   if (cl.n_host <= 0) return hipSuccess;
   const long long nb = (cl.n_host + 255) / 256;
   auto go = [&](auto na) {
-    hipLaunchKernelGGL(k_cell_extras<decltype(na)::value>, dim3((unsigned)nb), dim3(256), 0, st, cl, esprit_scale,
-                       gidx, az_table, sig_out, esprit_deg, phase, az_out);
-    return hipGetLastError();
+    return launch(st, k_cell_extras<decltype(na)::value>, nb, 256, 0, cl, esprit_scale, gidx, az_table, sig_out,
+                  esprit_deg, phase, az_out);
   };
   const bool fixed = cl.A == 4 || cl.A == 8 || cl.A == 16;  // antenna counts with an instance of their own
   return with_int<0, 4, 8, 16>(fixed ? cl.A : 0, go);
@@ -568,9 +555,7 @@ hipError_t launch_confidence(hipStream_t st, CellList cl, const int* gidx, const
                              const double* steer_phase, double* conf_out) {
   if (cl.A > kMaxA) return hipErrorInvalidValue;
   if (cl.n_host <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_confidence, dim3((unsigned)((cl.n_host + 255) / 256)), dim3(256), 0, st, cl, gidx, steer_c128,
-                     steer_phase, conf_out);
-  return hipGetLastError();
+  return launch(st, k_confidence, (cl.n_host + 255) / 256, 256, 0, cl, gidx, steer_c128, steer_phase, conf_out);
 }
 
 }  // namespace rsl

@@ -835,9 +835,8 @@ hipError_t launch_doa_fixup(hipStream_t st, CellList cl, int G, int music, const
   // steerT = the transposed fp64 table [A][G], built once with the steering tables (rsl_steer_table_build)
   return with_int<8, 16>(cl.A <= 8 ? 8 : 16, [&](auto ma) {
     return with_bool(music != 0, [&](auto mu) {
-      hipLaunchKernelGGL((k_doa_fixup<decltype(ma)::value, decltype(mu)::value>), dim3((unsigned)fb), dim3(256), 0, st,
-                         cl, G, reinterpret_cast<const double2*>(steerT), out_idx, out_gmax);
-      return hipGetLastError();
+      return launch(st, k_doa_fixup<decltype(ma)::value, decltype(mu)::value>, fb, 256, 0, cl, G,
+                    reinterpret_cast<const double2*>(steerT), out_idx, out_gmax);
     });
   });
 }
@@ -901,9 +900,9 @@ static hipError_t launch_toep_t(hipStream_t st, CellList cl, const uint4* tab, c
   // (|angle| <= pi) and only the fp32 rounding of pi * scale can; for d < lambda / 2, |x| > 1 gives NaN as in the
   // reference
   const int clamp = esprit_scale * 3.14159265358979323846 <= 1.0 + 1e-9;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, cl, tab, ntiles, G, out_idx, out_gmax,
-                     (float)esprit_scale, clamp, out_esprit, out_phase, out_spec);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (hipError_t e = launch(st, kern, blocks, 256, lds, cl, tab, ntiles, G, out_idx, out_gmax, (float)esprit_scale,
+                            clamp, out_esprit, out_phase, out_spec))
+    return e;
   // the exact re-scan of the marked cells
   return launch_doa_fixup(st, cl, G, MUSIC, steerT, out_idx, out_gmax);
 }

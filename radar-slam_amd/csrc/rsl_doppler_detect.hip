@@ -685,9 +685,8 @@ static hipError_t launch_k2d_packed(hipStream_t st, const float2* work, int F, i
   const size_t lds = P::kRows2 + (size_t)P::KB * (C / 64) * 16;
   const K2Fn kern = P::k2();
   *pk_group = P::KB;  // tile-compact peak powers (dd_tile_compute_reg)
-  hipLaunchKernelGGL(kern, dim3((unsigned)ntile), dim3(P::NT2), lds, st, work, rds, threshold_as_float(d.thr_p), d.i_lo,
-                     d.i_hi, d.mask, d.row_count, d.dbmap, d.pk_pow);
-  return hipGetLastError();
+  return launch(st, kern, ntile, P::NT2, lds, work, rds, threshold_as_float(d.thr_p), d.i_lo, d.i_hi, d.mask,
+                d.row_count, d.dbmap, d.pk_pow);
 }
 
 template <int C, int KB>
@@ -710,9 +709,8 @@ static hipError_t launch_k2d_kb(hipStream_t st, const float2* work, int F, int A
 #endif
   // tile-compact peak powers from the register tile body (KB rows per group), row-compact from the general body
   *pk_group = dd_reg_ok<C, KB, NT>() ? KB : 1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)ntile), dim3(NT), lds, st, work, S, tw, rds, threshold_as_float(d.thr_p),
-                     d.i_lo, d.i_hi, d.mask, d.row_count, d.dbmap, d.pk_pow);
-  return hipGetLastError();
+  return launch(st, kern, ntile, NT, lds, work, S, tw, rds, threshold_as_float(d.thr_p), d.i_lo, d.i_hi, d.mask,
+                d.row_count, d.dbmap, d.pk_pow);
 }
 
 // range bins per Doppler/detect tile: ~20 KiB tiles (KB 16 at C = 128: 2.42 ms vs KB 32: 3.23 ms per 1000 cfg2

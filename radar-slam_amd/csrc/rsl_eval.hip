@@ -497,17 +497,16 @@ hipError_t launch_pose_align(hipStream_t st, const double* est, const double* gt
   double* p1 = scratch;
   double* p2 = p1 + 256 * 6;
   double* ps = p2 + 256 * 19;
-  hipLaunchKernelGGL(k_pe_sums, dim3(nb), dim3(kPeThreads), 0, st, est, gt, n, p1);
-  hipLaunchKernelGGL(k_pe_moments, dim3(nb), dim3(kPeThreads), 0, st, est, gt, n, p1, nb, p2);
-  hipLaunchKernelGGL(k_pe_solve, dim3(1), dim3(64), 0, st, p1, p2, nb, n, align);
-  hipLaunchKernelGGL(k_pe_apply, dim3((unsigned)((n + kPeThreads - 1) / kPeThreads)), dim3(kPeThreads), 0, st, est,
-                     gt, n, align, aligned, ape_err);
-  if (ape_stats) {
-    hipLaunchKernelGGL(k_pe_stats1, dim3(nb, 3), dim3(kPeThreads), 0, st, ape_err, n, n, nullptr, ps);
-    hipLaunchKernelGGL(k_pe_stats2, dim3(nb, 3), dim3(kPeThreads), 0, st, ape_err, n, n, nullptr, ps);
-    hipLaunchKernelGGL(k_pe_stats3, dim3(1), dim3(3), 0, st, ps, nb, n, nullptr, ape_stats);
-  }
-  return hipGetLastError();
+  const int T = kPeThreads;
+  hipError_t e = launch(st, k_pe_sums, nb, T, 0, est, gt, n, p1);
+  if (!e) e = launch(st, k_pe_moments, nb, T, 0, est, gt, n, p1, nb, p2);
+  if (!e) e = launch(st, k_pe_solve, 1, 64, 0, p1, p2, nb, n, align);
+  if (!e) e = launch(st, k_pe_apply, (n + T - 1) / T, T, 0, est, gt, n, align, aligned, ape_err);
+  if (!ape_stats) return e;
+  if (!e) e = launch(st, k_pe_stats1, GridXY{nb, 3}, T, 0, ape_err, n, n, nullptr, ps);
+  if (!e) e = launch(st, k_pe_stats2, GridXY{nb, 3}, T, 0, ape_err, n, n, nullptr, ps);
+  if (!e) e = launch(st, k_pe_stats3, 1, 3, 0, ps, nb, n, nullptr, ape_stats);
+  return e;
 }
 
 hipError_t launch_pose_rte(hipStream_t st, const double* aligned, const double* gt, long n, const double* len,
@@ -515,14 +514,14 @@ hipError_t launch_pose_rte(hipStream_t st, const double* aligned, const double* 
   const int nb = pe_blocks(n);
   double* ps = scratch + 256 * 6 + 256 * 19;
   double* d = ps + 256 * 4 * (nlen > 3 ? nlen : 3);
-  hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * nlen, st);
-  hipLaunchKernelGGL(k_pe_distance, dim3(1), dim3(1024), 0, st, aligned, n, d);
-  hipLaunchKernelGGL(k_pe_rte, dim3((unsigned)((n + kPeThreads - 1) / kPeThreads), nlen), dim3(kPeThreads), 0, st,
-                     aligned, gt, n, d, len, err, cnt);
-  hipLaunchKernelGGL(k_pe_stats1, dim3(nb, nlen), dim3(kPeThreads), 0, st, err, n, n, cnt, ps);
-  hipLaunchKernelGGL(k_pe_stats2, dim3(nb, nlen), dim3(kPeThreads), 0, st, err, n, n, cnt, ps);
-  hipLaunchKernelGGL(k_pe_stats3, dim3(1), dim3(nlen), 0, st, ps, nb, n, cnt, stats);
-  return hipGetLastError();
+  const int T = kPeThreads;
+  hipError_t e = hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * nlen, st);
+  if (!e) e = launch(st, k_pe_distance, 1, 1024, 0, aligned, n, d);
+  if (!e) e = launch(st, k_pe_rte, GridXY{(n + T - 1) / T, nlen}, T, 0, aligned, gt, n, d, len, err, cnt);
+  if (!e) e = launch(st, k_pe_stats1, GridXY{nb, nlen}, T, 0, err, n, n, cnt, ps);
+  if (!e) e = launch(st, k_pe_stats2, GridXY{nb, nlen}, T, 0, err, n, n, cnt, ps);
+  if (!e) e = launch(st, k_pe_stats3, 1, nlen, 0, ps, nb, n, cnt, stats);
+  return e;
 }
 
 }  // namespace rsl

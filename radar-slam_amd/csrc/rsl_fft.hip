@@ -7,6 +7,7 @@
 // DC removal is folded into the range FFT: FFT(y - mean y)[k] = FFT(y)[k] for k != 0 and 0 for k = 0,
 // so the kernel zeroes range bin 0 instead of reducing a mean (exact in real arithmetic).
 // conj(ref)*w is precomputed on the host in fp64 (the chirp phase reaches 2.5e7 rad) and passed as a c64 table.
+#include <algorithm>
 #include <cstdlib>
 #include <mutex>
 #include <unordered_map>
@@ -88,17 +89,6 @@ static hipError_t rf_queue(RfQueues* s, hipStream_t st, unsigned** out) {
   s->q.emplace(st, q);
   *out = q;
   return hipSuccess;
-}
-
-// Grid of a persistent kernel: resident workgroups only (occupancy x CUs), at most ntile.
-static long resident_grid(const void* kern, size_t lds, long ntile, int nt = kThreads) {
-  int nb = 0, dev = 0, ncu = 256;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, nt, lds) != hipSuccess || nb < 1) nb = 1;
-  if (nb > 8) nb = 8;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  const long g = (long)nb * ncu;
-  return g < ntile ? g : (ntile > 0 ? ntile : 1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -747,14 +737,14 @@ struct PackedK1<64> {  // cfg1
   }
 };
 
-// K1's grid: the resident workgroups; RSL_K1_WG_PER_CU (development builds) caps them per CU (room for the other
-// stream).
-static long k1_grid(const void* kern, size_t lds, long ntile, int nt) {
-  long nblk = resident_grid(kern, lds, ntile, nt);
-  if (const int per_cu = dev_knob("RSL_K1_WG_PER_CU")) {
-    int dev = 0, ncu = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+// K1's grid, that of a persistent kernel: the resident workgroups (at most 8 per CU), at most ntile.  wg_knob:
+// RSL_K1_WG_PER_CU (development builds) caps them per CU (room for the other stream).
+template <class K>
+static long k1_grid(K kern, size_t lds, long ntile, int nt, bool wg_knob = true) {
+  const int ncu = cu_count();
+  long nblk = (long)std::min(occupancy(kern, nt, lds), 8) * ncu;
+  nblk = nblk < ntile ? nblk : (ntile > 0 ? ntile : 1);
+  if (const int per_cu = wg_knob ? dev_knob("RSL_K1_WG_PER_CU") : 0) {
     const long cap = (long)per_cu * ncu;
     if (cap >= 8 && cap < nblk) nblk = cap;
   }
@@ -779,13 +769,11 @@ static hipError_t launch_k1_packed(hipStream_t st, const float2* cube, int F, in
   const long ntile = (long)F * A * (C / 8);
   const K1Fn kern = P::k1();
   // RSL_K1_WG_PER_CU (k1_grid) acts on the S = 512 kernel only, as before the launchers were merged
-  const long nblk = S == 512 ? k1_grid(reinterpret_cast<const void*>(kern), 0, ntile, P::NT1)
-                             : resident_grid(reinterpret_cast<const void*>(kern), 0, ntile, P::NT1);
+  const long nblk = k1_grid(kern, 0, ntile, P::NT1, S == 512);
   if (nblk < 8 || !k1_tiles_fit(ntile, nblk)) return hipErrorInvalidValue;
   unsigned* rfq = nullptr;
   if (hipError_t qe = rf_queue(qs, st, &rfq)) return qe;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(P::NT1), 0, st, cube, Ct, c0, ntile, table, tw, dc, work, rfq);
-  return hipGetLastError();
+  return launch(st, kern, nblk, P::NT1, 0, cube, Ct, c0, ntile, table, tw, dc, work, rfq);
 }
 
 template <int S>
@@ -808,7 +796,7 @@ static hipError_t launch_k1(hipStream_t st, const float2* cube, int F, int A, in
       case 3: kern = k_range_fft_p<S, CB, true, 3>; break;
     }
 #endif
-    const long nblk = k1_grid(reinterpret_cast<const void*>(kern), lds, ntile, kThreads);
+    const long nblk = k1_grid(kern, lds, ntile, kThreads);
     if (!k1_tiles_fit(ntile, nblk)) return hipErrorInvalidValue;
     unsigned* rfq = nullptr;
     if (nblk >= 8) {  // the per-XCD dequeue needs a workgroup on every XCD
@@ -816,15 +804,11 @@ static hipError_t launch_k1(hipStream_t st, const float2* cube, int F, int A, in
     } else {
       kern = k_range_fft_p<S, CB, false>;  // fewer than 8 workgroups: a tiny batch
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kThreads), lds, st, cube, Ct, c0, C, ntile, table, tw, dc, work,
-                       rfq);
-    return hipGetLastError();
+    return launch(st, kern, nblk, kThreads, lds, cube, Ct, c0, C, ntile, table, tw, dc, work, rfq);
   }
   const long nblk = (long)F * A * ((C + CB - 1) / CB);
   const size_t lds = sizeof(float2) * (S + (size_t)CB * lp_row(S));
-  hipLaunchKernelGGL(k_range_fft<S>, dim3((unsigned)nblk), dim3(kThreads), lds, st, cube, Ct, c0, C, table, tw, dc,
-                     work);
-  return hipGetLastError();
+  return launch(st, k_range_fft<S>, nblk, kThreads, lds, cube, Ct, c0, C, table, tw, dc, work);
 }
 
 template <int C>
@@ -833,8 +817,7 @@ static hipError_t launch_k2(hipStream_t st, const float2* work, int F, int A, in
   constexpr int KB = rows_for(C);
   const long nblk = (long)F * A * ((S + KB - 1) / KB);
   const size_t lds = sizeof(float2) * (C + (size_t)KB * (lp_row(C) | 1));
-  hipLaunchKernelGGL(k_doppler_fft<C>, dim3((unsigned)nblk), dim3(kThreads), lds, st, work, S, tw, rds);
-  return hipGetLastError();
+  return launch(st, k_doppler_fft<C>, nblk, kThreads, lds, work, S, tw, rds);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -904,17 +887,14 @@ __global__ __launch_bounds__(kThreads) void k_doppler_dft(const float2* __restri
 hipError_t launch_range_dft(hipStream_t st, const float2* cube, int F, int A, int Ct, int c0, int C, int S,
                             const float2* table, const float2* tw, int dc, float2* work) {
   const long nblk = (long)F * A * C;
-  hipLaunchKernelGGL(k_range_dft, dim3((unsigned)nblk), dim3(kThreads), sizeof(float2) * 2 * (size_t)S, st, cube, Ct,
-                     c0, C, S, table, tw, dc, work);
-  return hipGetLastError();
+  return launch(st, k_range_dft, nblk, kThreads, sizeof(float2) * 2 * (size_t)S, cube, Ct, c0, C, S, table, tw, dc,
+                work);
 }
 
 hipError_t launch_doppler_dft(hipStream_t st, const float2* work, int F, int A, int C, int S, const float2* tw,
                               float2* rds) {
   const long nblk = (long)F * A * S;
-  hipLaunchKernelGGL(k_doppler_dft, dim3((unsigned)nblk), dim3(kThreads), sizeof(float2) * 2 * (size_t)C, st, work, C,
-                     S, tw, rds);
-  return hipGetLastError();
+  return launch(st, k_doppler_dft, nblk, kThreads, sizeof(float2) * 2 * (size_t)C, work, C, S, tw, rds);
 }
 
 hipError_t launch_range_fft(hipStream_t st, const float2* cube, int F, int A, int Ct, int chirp0, int C, int S,

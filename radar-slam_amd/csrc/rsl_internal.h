@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rsl_launch.h"  // what every launcher launches with
+
 namespace rsl {
 
 // Cell count of a capacity-sized list: the device count (written by the emit stage) clamped to the list capacity,

@@ -95,13 +95,8 @@ hipError_t launch_power_integrate(hipStream_t st, const float2* rds, int F, int 
   const bool vec = N % 4 == 0 && ((reinterpret_cast<size_t>(rds) | reinterpret_cast<size_t>(power)) & 15) == 0;
   const size_t per = vec ? 4 * 256 : 256;
   const size_t nb = (N + per - 1) / per;
-  if (nb * (size_t)F > 0x7fffffffull) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)(nb * (size_t)F));
-  if (vec)
-    hipLaunchKernelGGL(k_power_integrate<4>, grid, dim3(256), 0, st, rds, A, N, (unsigned)nb, power);
-  else
-    hipLaunchKernelGGL(k_power_integrate<1>, grid, dim3(256), 0, st, rds, A, N, (unsigned)nb, power);
-  return hipGetLastError();
+  return launch(st, vec ? k_power_integrate<4> : k_power_integrate<1>, (long long)(nb * (size_t)F), 256, 0, rds, A, N,
+                (unsigned)nb, power);
 }
 
 }  // namespace rsl

@@ -152,15 +152,9 @@ hipError_t launch_range_cov(hipStream_t st, const float2* rds, int F, int A, int
   if (F <= 0 || S <= 0) return hipSuccess;
   const long long rows = (long long)F * S;
   const long long blocks = (rows + kCovWaves - 1) / kCovWaves;
-  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
   const int vec = C % 2 == 0 && (reinterpret_cast<size_t>(rds) & 15) == 0;
-  if (A <= 8)
-    hipLaunchKernelGGL(k_range_cov<16>, dim3((unsigned)blocks), dim3(64 * kCovWaves), 0, st, rds, rows, A, S, C, c0,
-                       c1, vec, cov);
-  else
-    hipLaunchKernelGGL(k_range_cov<32>, dim3((unsigned)blocks), dim3(64 * kCovWaves), 0, st, rds, rows, A, S, C, c0,
-                       c1, vec, cov);
-  return hipGetLastError();
+  return launch(st, A <= 8 ? k_range_cov<16> : k_range_cov<32>, blocks, 64 * kCovWaves, 0, rds, rows, A, S, C, c0, c1,
+                vec, cov);
 }
 
 // cov c64 [n][A][A] -> map f32 [n][G], arg i32 [n] (nullable).  One wave per workgroup (so __syncthreads is one wave's
@@ -317,13 +311,8 @@ hipError_t launch_range_azimuth(hipStream_t st, const float2* cov, long long n, 
                                 int capon, float loading, float* map, int* arg) {
   if (n <= 0) return hipSuccess;
   const long long blocks = n < 65536 ? n : 65536;  // one wave per row; more rows are walked with the grid's stride
-  if (A <= 8)
-    hipLaunchKernelGGL(k_range_azimuth<8>, dim3((unsigned)blocks), dim3(64), 0, st, cov, n, A, steer, G, capon, loading,
-                       map, arg);
-  else
-    hipLaunchKernelGGL(k_range_azimuth<16>, dim3((unsigned)blocks), dim3(64), 0, st, cov, n, A, steer, G, capon,
-                       loading, map, arg);
-  return hipGetLastError();
+  return launch(st, A <= 8 ? k_range_azimuth<8> : k_range_azimuth<16>, blocks, 64, 0, cov, n, A, steer, G, capon,
+                loading, map, arg);
 }
 
 }  // namespace rsl

@@ -174,13 +174,10 @@ hipError_t launch_cell_refine(hipStream_t st, CellList cl, const float* power, c
   if (cl.A > kRefineMaxA || cl.A < 2) return hipErrorInvalidValue;
   if (cl.n_host <= 0) return hipSuccess;
   const long long nb = (cl.n_host + 255) / 256;
-  if (nb > 0x7fffffffll) return hipErrorInvalidValue;
   const double r0 = axes4[0], r_step = axes4[1], d0 = axes4[2], d_step = axes4[3];
   auto go = [&](auto na) {
-    hipLaunchKernelGGL(k_cell_refine<decltype(na)::value>, dim3((unsigned)nb), dim3(256), 0, st, cl, power, gidx,
-                       az_table, steer, G, range_mode, doppler_mode, r0, r_step, d0, d_step,
-                       reinterpret_cast<float4*>(out_points), out_az);
-    return hipGetLastError();
+    return launch(st, k_cell_refine<decltype(na)::value>, nb, 256, 0, cl, power, gidx, az_table, steer, G, range_mode,
+                  doppler_mode, r0, r_step, d0, d_step, reinterpret_cast<float4*>(out_points), out_az);
   };
   const bool fixed = cl.A == 4 || cl.A == 8 || cl.A == 16;  // antenna counts with an instance of their own
   return with_int<0, 4, 8, 16>(fixed ? cl.A : 0, go);

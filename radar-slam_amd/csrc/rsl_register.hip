@@ -349,8 +349,7 @@ __global__ __launch_bounds__(kRegThreads) void k_scan_register(RegProblem p, dou
 
 hipError_t launch_scan_register(hipStream_t st, const RegProblem& p, double* out, double* omega) {
   if (p.F <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_scan_register, dim3((unsigned)p.F), dim3(kRegThreads), 0, st, p, out, omega);
-  return hipGetLastError();
+  return launch(st, k_scan_register, p.F, kRegThreads, 0, p, out, omega);
 }
 
 }  // namespace rsl

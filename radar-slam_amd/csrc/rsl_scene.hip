@@ -176,9 +176,8 @@ hipError_t launch_topk_entries(hipStream_t st, const long long* entry_base, long
                                int* sel_entry, int* sel_frame, int* sel_rc, int* sel_n) {
   if (ncube <= 0) return hipSuccess;
   if (kmax < 1 || kmax > kTopkMax) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_topk_entries, dim3((unsigned)ncube), dim3(kTopkThreads), 0, st, entry_base, entry_cap, e_coord,
-                     e_pdb, thr_db, kmax, C, sel_entry, sel_frame, sel_rc, sel_n);
-  return hipGetLastError();
+  return launch(st, k_topk_entries, ncube, kTopkThreads, 0, entry_base, entry_cap, e_coord, e_pdb, thr_db, kmax, C,
+                sel_entry, sel_frame, sel_rc, sel_n);
 }
 
 // a * b + c * d and a * b - c * d with each product and the sum rounded on its own, as numpy evaluates them.  The pragma
@@ -246,9 +245,7 @@ hipError_t launch_associate_nearest(hipStream_t st, const double* range_m, const
                                     double* dist, double* phase) {
   if (nframes <= 0 || ntargets <= 0) return hipSuccess;
   const long long nb = (ntargets + 255) / 256;
-  hipLaunchKernelGGL(k_associate_nearest, dim3((unsigned)nb), dim3(256), 0, st, range_m, az_rad, s0, off, nframes,
-                     thr, match, dist, phase);
-  return hipGetLastError();
+  return launch(st, k_associate_nearest, nb, 256, 0, range_m, az_rad, s0, off, nframes, thr, match, dist, phase);
 }
 
 }  // namespace rsl

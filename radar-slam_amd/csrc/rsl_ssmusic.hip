@@ -373,9 +373,8 @@ hipError_t launch_doa_smoothed(hipStream_t st, CellList cl, const float2* steer,
   long long blocks = (cl.n_host + kSsCells - 1) / kSsCells;
   if (blocks > 8192) blocks = 8192;
   return with_int<2, 3, 4, 5, 6, 7, 8>(L, [&](auto l) {
-    hipLaunchKernelGGL(k_doa_smoothed<decltype(l)::value>, dim3((unsigned)blocks), dim3(64), 0, st, cl, steer, G, nmax,
-                       num_sources, rel, out_nsrc, out_idx, out_den, out_eig, out_spec);
-    return hipGetLastError();
+    return launch(st, k_doa_smoothed<decltype(l)::value>, blocks, 64, 0, cl, steer, G, nmax, num_sources, rel, out_nsrc,
+                  out_idx, out_den, out_eig, out_spec);
   });
 }
 

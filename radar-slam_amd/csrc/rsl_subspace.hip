@@ -292,16 +292,12 @@ __global__ __launch_bounds__(64) void k_esprit_subspace(const double* __restrict
 hipError_t launch_music_subspace(hipStream_t st, const double* sigs, long n, int M, int K, const double* steer,
                                  int G, double* spec) {
   const long tot = n * (long)G;
-  hipLaunchKernelGGL(k_music_subspace, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, sigs, n, M, K, steer,
-                     G, spec);
-  return hipGetLastError();
+  return launch(st, k_music_subspace, (tot + 255) / 256, 256, 0, sigs, n, M, K, steer, G, spec);
 }
 
 hipError_t launch_esprit_subspace(hipStream_t st, const double* sigs, long n, int M, int K, double esprit_scale,
                                   double* deg) {
-  hipLaunchKernelGGL(k_esprit_subspace, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, sigs, n, M, K,
-                     esprit_scale, deg);
-  return hipGetLastError();
+  return launch(st, k_esprit_subspace, (n + 63) / 64, 64, 0, sigs, n, M, K, esprit_scale, deg);
 }
 
 }  // namespace rsl

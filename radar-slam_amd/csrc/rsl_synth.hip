@@ -95,25 +95,19 @@ hipError_t launch_synth_pattern(hipStream_t st, const double* sc, int n, int A, 
                                 double Tc, double d, double2* pattern) {
   const long tot = (long)A * S;
   if (tot <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_synth_pattern, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, sc, n, A, S, fc,
-                     bandwidth, Tc, d, pattern);
-  return hipGetLastError();
+  return launch(st, k_synth_pattern, (tot + 255) / 256, 256, 0, sc, n, A, S, fc, bandwidth, Tc, d, pattern);
 }
 
 hipError_t launch_synth_cube(hipStream_t st, const double2* pattern, int F, int A, int C, int S, double noise_power,
                              unsigned long long seed, long long frame0, float2* cube) {
   const long long npair = (long long)F * A * C * S / 2;
   if (npair <= 0) return hipSuccess;
-  int dev = 0, ncu = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  const long long cap = cu_count() * 16LL;
   long long nb = (npair + 255) / 256;
-  if (nb > (long long)ncu * 16) nb = (long long)ncu * 16;
+  if (nb > cap) nb = cap;
   const long long g0 = frame0 * (long long)A * C * S;
-  hipLaunchKernelGGL(k_synth_cube, dim3((unsigned)nb), dim3(256), 0, st, pattern, npair, A, C, S,
-                     (float)sqrt(noise_power), (unsigned)seed, (unsigned)(seed >> 32), g0,
-                     reinterpret_cast<float4*>(cube));
-  return hipGetLastError();
+  return launch(st, k_synth_cube, nb, 256, 0, pattern, npair, A, C, S, (float)sqrt(noise_power), (unsigned)seed,
+                (unsigned)(seed >> 32), g0, reinterpret_cast<float4*>(cube));
 }
 
 }  // namespace rsl

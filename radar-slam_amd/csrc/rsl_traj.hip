@@ -267,35 +267,27 @@ __global__ void k_traj_stitch(const double* __restrict__ summ, int R, int rank, 
 
 hipError_t launch_traj_stitch(hipStream_t st, const double* summ, int R, int rank, double dt, int method,
                               double* state, double* base) {
-  hipLaunchKernelGGL(k_traj_stitch, dim3(1), dim3(64), 0, st, summ, R, rank, dt, method, state, base);
-  return hipGetLastError();
+  return launch(st, k_traj_stitch, 1, 64, 0, summ, R, rank, dt, method, state, base);
 }
 
 hipError_t launch_traj_scan(hipStream_t st, const double* vel, int vstride, int nv, const double* om, int ostride,
                             const double* ts, double dt, long F, int method, double* pos, double* quat,
                             double* summary) {
   if (F <= 0) return hipSuccess;
-  if (F <= kTrajWaveMax) {
-    hipLaunchKernelGGL(k_traj_scan_wave, dim3(1), dim3(64), 0, st, vel, vstride, nv, om, ostride, ts, dt, F, method,
-                       pos, quat, summary);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(k_traj_scan, dim3(1), dim3(kTrajThreads), 0, st, vel, vstride, nv, om, ostride, ts, dt, F,
-                     method, pos, quat, summary);
-  return hipGetLastError();
+  if (F <= kTrajWaveMax)
+    return launch(st, k_traj_scan_wave, 1, 64, 0, vel, vstride, nv, om, ostride, ts, dt, F, method, pos, quat, summary);
+  return launch(st, k_traj_scan, 1, kTrajThreads, 0, vel, vstride, nv, om, ostride, ts, dt, F, method, pos, quat,
+                summary);
 }
 
 hipError_t launch_traj_apply(hipStream_t st, double* pos, double* quat, long F, const double* base) {
   if (F <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_traj_apply, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, pos, quat, F, base);
-  return hipGetLastError();
+  return launch(st, k_traj_apply, (F + 255) / 256, 256, 0, pos, quat, F, base);
 }
 
 hipError_t launch_traj_smooth(hipStream_t st, const double* x, long F, int ncol, int size, double* out) {
   if (F <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_traj_smooth, dim3((unsigned)((F * ncol + 255) / 256)), dim3(256), 0, st, x, F, ncol, size,
-                     out);
-  return hipGetLastError();
+  return launch(st, k_traj_smooth, (F * ncol + 255) / 256, 256, 0, x, F, ncol, size, out);
 }
 
 }  // namespace rsl

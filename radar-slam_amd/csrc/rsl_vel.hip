@@ -165,9 +165,8 @@ __global__ __launch_bounds__(kVelThreads) void k_velocity(
 hipError_t launch_velocity(hipStream_t st, const VelProblem& p, double* out, double* resid, double* pred) {
   if (p.F <= 0) return hipSuccess;
   const size_t lds = p.gidx ? sizeof(double) * 4 * (size_t)p.G : 0;
-  hipLaunchKernelGGL(k_velocity, dim3(p.F), dim3(kVelThreads), lds, st, p.az, p.gidx, p.az_table, p.G, p.y, p.amask,
-                     p.seg, p.n, p.k, p.ridge, p.lx, p.hx, p.ly, p.hy, out, resid, pred);
-  return hipGetLastError();
+  return launch(st, k_velocity, p.F, kVelThreads, lds, p.az, p.gidx, p.az_table, p.G, p.y, p.amask, p.seg, p.n, p.k,
+                p.ridge, p.lx, p.hx, p.ly, p.hy, out, resid, pred);
 }
 
 }  // namespace rsl

@@ -255,18 +255,14 @@ hipError_t launch_velocity_consensus(hipStream_t st, const VelProblem& p, double
   const size_t lds = sizeof(double) * ((p.gidx ? 2 * (size_t)p.G : 0) + kCvLds);
   const int per = (hyps + kCvThreads - 1) / kCvThreads;
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(p.F), dim3(kCvThreads), lds, st, p.az, p.gidx, p.az_table, p.G, p.y, p.amask, p.seg,
-                       p.n, p.k, p.ridge, p.lx, p.hx, p.ly, p.hy, c * scale, hyps, min_det, refine, (unsigned)seed,
-                       (unsigned)(seed >> 32), frame0, out, weight, resid);
+    return launch(st, kern, p.F, kCvThreads, lds, p.az, p.gidx, p.az_table, p.G, p.y, p.amask, p.seg, p.n, p.k, p.ridge,
+                  p.lx, p.hx, p.ly, p.hy, c * scale, hyps, min_det, refine, (unsigned)seed, (unsigned)(seed >> 32),
+                  frame0, out, weight, resid);
   };
   // hypotheses per thread, in registers: the smallest instantiation that holds hyps
-  if (per <= 1)
-    go(k_velocity_consensus<1>);
-  else if (per <= 4)
-    go(k_velocity_consensus<4>);
-  else
-    go(k_velocity_consensus<kCvMaxPer>);
-  return hipGetLastError();
+  if (per <= 1) return go(k_velocity_consensus<1>);
+  if (per <= 4) return go(k_velocity_consensus<4>);
+  return go(k_velocity_consensus<kCvMaxPer>);
 }
 
 }  // namespace rsl

@@ -226,10 +226,8 @@ hipError_t launch_velocity_robust(hipStream_t st, const VelProblem& p, int loss,
                                   double tol, double* out, float* weight, double* resid) {
   if (p.F <= 0) return hipSuccess;
   const size_t lds = sizeof(double) * ((p.gidx ? 2 * (size_t)p.G : 0) + kRvLds);
-  hipLaunchKernelGGL(k_velocity_robust, dim3(p.F), dim3(kRvThreads), lds, st, p.az, p.gidx, p.az_table, p.G, p.y,
-                     p.amask, p.seg, p.n, p.k, p.ridge, p.lx, p.hx, p.ly, p.hy, loss, c, scale, iters, tol, out, weight,
-                     resid);
-  return hipGetLastError();
+  return launch(st, k_velocity_robust, p.F, kRvThreads, lds, p.az, p.gidx, p.az_table, p.G, p.y, p.amask, p.seg, p.n,
+                p.k, p.ridge, p.lx, p.hx, p.ly, p.hy, loss, c, scale, iters, tol, out, weight, resid);
 }
 
 }  // namespace rsl

@@ -68,8 +68,7 @@ __global__ __launch_bounds__(256) void k_associate(const double* __restrict__ cu
 hipError_t launch_associate(hipStream_t st, const double* cur, int nc, const double* prev, int np, double thr,
                             unsigned* used_scratch, int* match, double* dist) {
   if (nc <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_associate, dim3(1), dim3(256), 0, st, cur, nc, prev, np, thr, used_scratch, match, dist);
-  return hipGetLastError();
+  return launch(st, k_associate, 1, 256, 0, cur, nc, prev, np, thr, used_scratch, match, dist);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -499,26 +498,25 @@ __global__ __launch_bounds__(1024) void k_wrapped_topk(double* __restrict__ blk,
   }
 }
 
-// The problem of one call, with its Jacobian J [6n] and data Hessian Hd [36] launched into the scratch sections given.
-static WrapProblem wrap_problem(hipStream_t st, const WrapArgs& a, double* J, double* Hd) {
-  hipLaunchKernelGGL(k_wrapped_jac, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, st, a.pos, a.ang, a.n, J);
-  hipLaunchKernelGGL(k_wrapped_hess, dim3(1), dim3(256), 0, st, J, a.n, a.k, Hd);
-  WrapProblem P = {J, a.y, a.n, a.k, a.mode, a.w, a.vmax, a.wmax, a.prev, {}, {}, a.nv};
+// The problem of one call into P, with its Jacobian J [6n] and data Hessian Hd [36] launched into the scratch sections
+// given.
+static hipError_t wrap_problem(hipStream_t st, const WrapArgs& a, double* J, double* Hd, WrapProblem& P) {
+  P = {J, a.y, a.n, a.k, a.mode, a.w, a.vmax, a.wmax, a.prev, {}, {}, a.nv};
   for (int c = 0; c < 6; ++c) {
     P.lo[c] = a.lo[c];
     P.hi[c] = a.hi[c];
   }
-  return P;
+  if (hipError_t e = launch(st, k_wrapped_jac, (a.n + 255) / 256, 256, 0, a.pos, a.ang, a.n, J)) return e;
+  return launch(st, k_wrapped_hess, 1, 256, 0, J, a.n, a.k, Hd);
 }
 
 // The nv-D descent from nstart = gn^2 + nextra starts into res [8 nstart], and the best of them into out [8].
 static hipError_t wrapped_descend(hipStream_t st, const WrapProblem& P, const double* Hd, int gn, const double* extra,
                                   long nextra, int iters, double* res, double* out) {
   const long nstart = (long)gn * gn + nextra;
-  hipLaunchKernelGGL(k_wrapped_ms, dim3((unsigned)((nstart + 255) / 256)), dim3(256), 0, st, P, Hd, gn, extra,
-                     (int)nextra, iters, res);
-  hipLaunchKernelGGL(k_wrapped_best, dim3(1), dim3(1024), 0, st, res, nstart, out);
-  return hipGetLastError();
+  if (hipError_t e = launch(st, k_wrapped_ms, (nstart + 255) / 256, 256, 0, P, Hd, gn, extra, (int)nextra, iters, res))
+    return e;
+  return launch(st, k_wrapped_best, 1, 1024, 0, res, nstart, out);
 }
 
 hipError_t launch_wrapped_search(hipStream_t st, const WrapArgs& a, const double* base6, long gx, long gy, int nbest,
@@ -527,25 +525,23 @@ hipError_t launch_wrapped_search(hipStream_t st, const WrapArgs& a, const double
   const WrappedSearchScratch S(scratch, n, gx * gy, nstart);
   Six b6;
   for (int c = 0; c < 6; ++c) b6.v[c] = fmin(fmax(base6[c], a.lo[c]), a.hi[c]);
-  hipLaunchKernelGGL(k_fill6, dim3(1), dim3(64), 0, st, S.base, b6);  // by value: no pageable host copy
-  if (a.nextra > 0) {
-    const hipError_t e = hipMemcpyAsync(S.starts + 6L * nbest, a.extra, 6 * sizeof(double) * a.nextra,
-                                        hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return e;
-  }
-  const WrapProblem P = wrap_problem(st, a, S.J, S.Hd);
-  hipLaunchKernelGGL(k_wrapped_prep2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S.J, a.y, n, a.k, S.base,
-                     S.T);
+  hipError_t e = launch(st, k_fill6, 1, 64, 0, S.base, b6);  // by value: no pageable host copy
+  if (!e && a.nextra > 0)
+    e = hipMemcpyAsync(S.starts + 6L * nbest, a.extra, 6 * sizeof(double) * a.nextra, hipMemcpyDeviceToDevice, st);
+  WrapProblem P;
+  if (!e) e = wrap_problem(st, a, S.J, S.Hd, P);
+  if (!e) e = launch(st, k_wrapped_prep2, (n + 255) / 256, 256, 0, S.J, a.y, n, a.k, S.base, S.T);
   const Grid2 Gd = {gx, gy, a.lo[0], a.lo[1], (a.hi[0] - a.lo[0]) / (double)gx, (a.hi[1] - a.lo[1]) / (double)gy};
-  hipLaunchKernelGGL(k_wrapped_grid2, dim3((unsigned)S.nblk), dim3(256), 0, st, P, S.T, S.Hd, S.base, Gd, a.iters,
-                     S.blk);
-  hipLaunchKernelGGL(k_wrapped_topk, dim3(1), dim3(1024), 0, st, S.blk, S.nblk, nbest, S.base, S.starts);
+  if (!e) e = launch(st, k_wrapped_grid2, S.nblk, 256, 0, P, S.T, S.Hd, S.base, Gd, a.iters, S.blk);
+  if (!e) e = launch(st, k_wrapped_topk, 1, 1024, 0, S.blk, S.nblk, nbest, S.base, S.starts);
+  if (e) return e;
   return wrapped_descend(st, P, S.Hd, 0, S.starts, nstart, a.iters, S.res, out);
 }
 
 hipError_t launch_wrapped_solve(hipStream_t st, const WrapArgs& a, int gn, double* scratch, double* out) {
   const WrappedSolveScratch S(scratch, a.n, (long)gn * gn + a.nextra);
-  const WrapProblem P = wrap_problem(st, a, S.J, S.Hd);
+  WrapProblem P;
+  if (hipError_t e = wrap_problem(st, a, S.J, S.Hd, P)) return e;
   return wrapped_descend(st, P, S.Hd, gn, a.extra, a.nextra, a.iters, S.res, out);
 }
 
