@@ -552,6 +552,57 @@ int rsl_scan_register(rsl_handle h, const void* points, const void* seg, int F, 
                       double h_coarse, double dtheta, int K, int iters, double shrink, double tol, double w_min,
                       double dt, void* out, void* omega);
 
+/* Grid map: per-scan hit and free-space counts in world coordinates from the frames' point clouds and poses
+ *     (rsl_map.hip, k_map_update; the reference project has no counterpart, this comment is the specification).
+ *     The map is two planes of unsigned integer counts, and every frame (scan) adds at most 1 to a cell's hit count or
+ *     to its free count: the classical per-scan binary update.  Several points in one cell, and the mostly-noise cells
+ *     of the threshold detector, do not multiply the evidence.  Integer adds commute, so the planes are bit-identical
+ *     from run to run and independent of the frame order and of how the frames are split over launches or ranks, and
+ *     rank maps merge by integer addition.  Clamped log-odds are derived from the counts at the end (rsl_map_logodds),
+ *     not clamped per update: a per-update clamp would make the map depend on the order of the frames.
+ *     Inputs (device unless marked host): points f32 [n][8], the rows of rsl_cell_refine (columns 3, 4 = x, y, column
+ *     5 = power_db; no other column is read); seg i64 [F + 1] (cell_base), both ends of every frame clamped to [0, n];
+ *     weight f32 [n] (nullable); poses f64 [F][7] = (p_x, p_y, p_z, q_w, q_x, q_y, q_z), the rows of the trajectory
+ *     reduction: the sensor frame is the body frame (no mounting offset); grid4 (host) = {x0, y0, cell, unused}: the
+ *     world position of the corner of cell (0, 0) and the cell size; hits, free_ u32 [ny][nx], both in / out: the call
+ *     adds to them and never clears them; free_ nullable: no ray is cast; stats i32 [F][4] (nullable).
+ *     Arithmetic: all fp64, every product and sum rounded once in the order written, no fused multiply-add.
+ *     inv = 1 / cell (one division, on the host), Rw = (int)ceil(r_max inv) + 1.
+ *     Per frame: r00 = 1 - 2 (q_y q_y + q_z q_z), r01 = 2 (q_x q_y - q_w q_z), r10 = 2 (q_x q_y + q_w q_z),
+ *     r11 = 1 - 2 (q_x q_x + q_z q_z): the quaternion as given, not normalised; only the planar 2 x 2 block is used and
+ *     p_z is ignored.  Origin cell: ox = floor((p_x - x0) inv), oy likewise.  If any of p_x, p_y, r00, r01, r10, r11 is
+ *     not finite, or |(p - x0) inv| >= 2^30 in x or y, the frame counts nothing and its stats row is {0, 0, 0, 1}.
+ *     Per point, x and y promoted to fp64, accepted iff (1) x and y are finite; (2) the weight is null or > 0 (a NaN
+ *     weight is not); (3) not (power_db < min_db), so -inf disables the floor; (4) r_min^2 <= x x + y y <= r_max^2, both
+ *     squares formed as products on the host; then X = (r00 x + r01 y) + p_x, Y = (r10 x + r11 y) + p_y,
+ *     hx = floor((X - x0) inv), hy likewise, and (5) 0 <= hx < nx and 0 <= hy < ny, compared as doubles before any
+ *     conversion; (6) |hx - ox| <= Rw and |hy - oy| <= Rw.  H_f is the set of the accepted points' cells.
+ *     Free set (only with free_): for every cell (hx, hy) of H_f, dx = |hx - ox|, dy = |hy - oy|, sx = +1 if hx >= ox
+ *     else -1, sy likewise, L = max(dx, dy), and for k = 0 .. L - 1 the cell
+ *         (ox + sx k, oy + sy ((2 k dy + dx) div (2 dx)))   if dx >= dy,
+ *         (ox + sx ((2 k dx + dy) div (2 dy)), oy + sy k)   otherwise:
+ *     the closed form of the integer line from the origin cell up to, not including, the hit cell (L distinct,
+ *     8-connected cells; the next step would be the hit cell).  Ray cells outside the map are dropped one by one (the
+ *     sensor stands outside the map).  Free_f = (the union of the rays' cells) \ H_f: a cell hit in this scan is not
+ *     free in this scan.
+ *     Update: hits[c] += 1 for c in H_f, free_[c] += 1 for c in Free_f; stats row = {accepted points, |H_f|, |Free_f|,
+ *     flag}.  One workgroup per frame with two bitmaps of the (2 Rw + 1)^2 window in LDS: Rw <= RSL_MAP_MAX_RW, two
+ *     bitmaps of 767^2 bits = 147,080 B of the CU's 160 KiB.
+ *     RSL_ERR_UNSUPPORTED: Rw > RSL_MAP_MAX_RW.  RSL_ERR_INVALID: cell, r_max, x0 or y0 not finite; cell <= 0;
+ *     r_min < 0 or NaN; r_max < r_min; min_db NaN or +inf; nx, ny <= 0 or nx ny >= 2^31; F or n < 0; null points, seg,
+ *     poses, grid4 or hits with F > 0.  F = 0 launches nothing.  Timed under RSL_K_AUX. */
+#define RSL_MAP_MAX_RW 383
+int rsl_map_update(rsl_handle h, const void* points, const void* seg, int F, long long n, const void* weight,
+                   const void* poses, const double* grid4, int nx, int ny, double r_min, double r_max,
+                   double min_db, void* hits, void* free_, void* stats);
+
+/* Log-odds of the grid map's counts (rsl_map.hip, k_map_logodds), elementwise:
+ *     out f32 [ncells] = clamp((double)hits l_occ - (double)free l_free, l_min, l_max); each operation rounded in
+ *     fp64, the result rounded to f32 once.  free_ nullable = 0.  RSL_ERR_INVALID: a parameter that is not finite;
+ *     l_min > l_max; ncells < 0; null hits or out with ncells > 0.  Timed under RSL_K_AUX. */
+int rsl_map_logodds(rsl_handle h, const void* hits, const void* free_, long long ncells, double l_occ, double l_free,
+                    double l_min, double l_max, void* out);
+
 /* a3-a6  SignalPreprocessor.dechirp_signal / apply_window / remove_dc / process_chirp (dechirp.py:85-166):
  *     out[r, s] = in[r, s] * table[s], then (dc != 0) minus the row's complex mean.  in/out c64 [rows, S]. */
 int rsl_preprocess_rows(rsl_handle h, const void* in, long long rows, int S, const void* table, int dc, void* out);

@@ -790,6 +790,53 @@ int rsl_scan_register(rsl_handle h, const void* points, const void* seg, int F, 
   return hip_check(h, rsl::launch_scan_register(h->stream, p, (double*)out, (double*)omega), "scan_register");
 }
 
+int rsl_map_update(rsl_handle h, const void* points, const void* seg, int F, long long n, const void* weight,
+                   const void* poses, const double* grid4, int nx, int ny, double r_min, double r_max, double min_db,
+                   void* hits, void* free_, void* stats) {
+  if (!h) return RSL_ERR_INVALID;
+  const bool grid_ok = grid4 && std::isfinite(grid4[0]) && std::isfinite(grid4[1]) && std::isfinite(grid4[2]) &&
+                       grid4[2] > 0.0;
+  const char* why = (F < 0 || n < 0)                                      ? "negative count"
+                    : (F > 0 && (!points || !seg || !poses || !grid4 || !hits)) ? "null points, seg, poses, grid4 or hits"
+                    : (grid4 && !grid_ok)                                 ? "x0, y0 and cell must be finite, cell > 0"
+                    : !(r_min >= 0.0)                                     ? "r_min must be >= 0"
+                    : !(std::isfinite(r_max) && r_max >= r_min)           ? "r_max must be finite, >= r_min"
+                    : (std::isnan(min_db) || min_db == INFINITY)          ? "min_db is NaN or +inf"
+                    : (nx <= 0 || ny <= 0 || (long long)nx * ny >= (1ll << 31)) ? "nx, ny must be > 0, nx ny < 2^31"
+                                                                          : nullptr;
+  if (why) {
+    const std::string msg = std::string("rsl_map_update: ") + why;
+    return fail(h, RSL_ERR_INVALID, msg.c_str());
+  }
+  if (!grid4) return RSL_OK;  // only with F = 0
+  const double inv = 1.0 / grid4[2], rw = std::ceil(r_max * inv) + 1.0;
+  if (!(rw <= (double)RSL_MAP_MAX_RW))
+    return fail(h, RSL_ERR_UNSUPPORTED, "rsl_map_update: ceil(r_max / cell) + 1 above RSL_MAP_MAX_RW");
+  if (F == 0) return RSL_OK;
+  const rsl::MapProblem p{(const float*)points, (const long long*)seg, n, F, (const float*)weight,
+                          (const double*)poses, grid4[0], grid4[1], inv, nx, ny, (int)rw,
+                          r_min * r_min, r_max * r_max, min_db};
+  Scope sc(h, RSL_K_AUX);
+  return hip_check(h, rsl::launch_map_update(h->stream, p, (unsigned*)hits, (unsigned*)free_, (int*)stats),
+                   "map_update");
+}
+
+int rsl_map_logodds(rsl_handle h, const void* hits, const void* free_, long long ncells, double l_occ, double l_free,
+                    double l_min, double l_max, void* out) {
+  if (!h) return RSL_ERR_INVALID;
+  if (!(std::isfinite(l_occ) && std::isfinite(l_free) && std::isfinite(l_min) && std::isfinite(l_max)))
+    return fail(h, RSL_ERR_INVALID, "rsl_map_logodds: l_occ, l_free, l_min and l_max must be finite");
+  if (l_min > l_max) return fail(h, RSL_ERR_INVALID, "rsl_map_logodds: l_min > l_max");
+  if (ncells < 0 || (ncells > 0 && (!hits || !out)))
+    return fail(h, RSL_ERR_INVALID, "rsl_map_logodds: negative count, or null hits or out");
+  if (ncells == 0) return RSL_OK;
+  Scope sc(h, RSL_K_AUX);
+  return hip_check(h,
+                   rsl::launch_map_logodds(h->stream, (const unsigned*)hits, (const unsigned*)free_, ncells, l_occ,
+                                           l_free, l_min, l_max, (float*)out),
+                   "map_logodds");
+}
+
 int rsl_preprocess_rows(rsl_handle h, const void* in, long long rows, int S, const void* table, int dc, void* out) {
   if (!h) return RSL_ERR_INVALID;
   if (rows < 0 || S <= 0 || !in || !table || !out) return fail(h, RSL_ERR_INVALID, "rsl_preprocess_rows: bad argument");

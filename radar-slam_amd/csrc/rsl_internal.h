@@ -198,6 +198,23 @@ struct RegProblem {
 };
 hipError_t launch_scan_register(hipStream_t st, const RegProblem& p, double* out, double* omega);
 
+// Grid map (rsl_map.hip; the contract is rsl_map_update's in rsl.h), checked and typed by rsl_map_update (rsl_api.hip).
+// Passed to the kernel by value.  inv = 1 / cell, Rw = (int)ceil(r_max inv) + 1, rmin2 / rmax2 the squared range gate.
+struct MapProblem {
+  const float* points;
+  const long long* seg;
+  long long n;
+  int F;
+  const float* weight;
+  const double* poses;
+  double x0, y0, inv;
+  int nx, ny, Rw;
+  double rmin2, rmax2, min_db;
+};
+hipError_t launch_map_update(hipStream_t st, const MapProblem& p, unsigned* hits, unsigned* free_, int* stats);
+hipError_t launch_map_logodds(hipStream_t st, const unsigned* hits, const unsigned* free_, long long ncells,
+                              double l_occ, double l_free, double l_min, double l_max, float* out);
+
 // K9: greedy association and wrapped-phase multi-start solve (rsl_wrap.hip).
 // configs[3] pattern (rsl_scene.hip): per-cube top-k peak selection and the analyser's nearest association.
 hipError_t launch_topk_entries(hipStream_t st, const long long* entry_base, long long entry_cap, int ncube,

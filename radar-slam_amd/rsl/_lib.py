@@ -29,6 +29,7 @@ RA_MIN_LOADING = 1e-4  # RSL_RA_MIN_LOADING: the least diagonal loading of the C
 REFINE_NONE, REFINE_LOG, REFINE_RECT, REFINE_HANN = 0, 1, 2, 3  # RSL_REFINE_*: the offset estimators of rsl_cell_refine
 REFINE_IDS = {'none': REFINE_NONE, 'log': REFINE_LOG, 'rect': REFINE_RECT, 'hann': REFINE_HANN}
 REG_MAX_K, REG_MAX_ITERS = 64, 100  # RSL_REG_MAX_K, RSL_REG_MAX_ITERS: the limits of rsl_scan_register
+MAP_MAX_RW = 383  # RSL_MAP_MAX_RW: the largest half window, in cells, of rsl_map_update
 LOSS_HUBER, LOSS_TUKEY = 1, 2
 LOSS_IDS = {'huber': LOSS_HUBER, 'tukey': LOSS_TUKEY}
 LOSS_DEFAULT_C = {LOSS_HUBER: 1.345, LOSS_TUKEY: 4.685}  # 95 % efficiency at the normal distribution
@@ -85,6 +86,9 @@ SIGNATURES = {
     'rsl_scan_register': (c_int, [_P, _P, _P, c_int, c_longlong, _P, _P, c_int, POINTER(c_double), _P, _P, _P, c_longlong,
                                   _P, _P, c_double, c_double, c_double, c_int, c_int, c_double, c_double, c_double,
                                   c_double, _P, _P]),
+    'rsl_map_update': (c_int, [_P, _P, _P, c_int, c_longlong, _P, _P, POINTER(c_double), c_int, c_int, c_double, c_double,
+                               c_double, _P, _P, _P]),
+    'rsl_map_logodds': (c_int, [_P, _P, _P, c_longlong, c_double, c_double, c_double, c_double, _P]),
     'rsl_confidence': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_longlong, _P, _P, _P, _P]),
     'rsl_velocity': (c_int, _VEL + [_P, _P, _P]),
     'rsl_velocity_robust': (c_int, _VEL + [c_int, c_double, c_double, c_int, c_double, _P, _P, _P]),

@@ -490,6 +490,42 @@ def register_scans(points, seg, *, weight=None, rc=None, C: int = 0, axes=None, 
     return res
 
 
+def grid_map(points, seg, poses, *, weight=None, free: bool = True, ctx: Optional[Context] = None, **params):
+    """The grid map of F point clouds seen from F poses (mapping.GridMap; rsl_map_update and rsl_map_logodds, specified
+    in include/rsl.h): points f32 [N, 8] (the rows of refine_cells / the chain's 'points'; columns 3, 4 and 5 are x, y
+    and power_db), seg [F + 1] the frames' first rows, poses f64 [F, 7] = (p_x, p_y, p_z, q_w, q_x, q_y, q_z), weight
+    [N] or None (the static / moving labels: 'vel_weight').  params: origin, shape = (ny, nx), cell, r_min, r_max,
+    min_db, l_occ, l_free, l_min, l_max (GridMap), checked before any device use.  Host arrays or device tensors.
+    Returns a dict of host arrays: hits u32 [ny, nx], free u32 [ny, nx] (None with free=False), logodds f32 [ny, nx],
+    stats i32 [F, 4] = {accepted points, hit cells, free cells, flag}."""
+    from . import mapping
+    mapping.check_params(**params)
+    points, seg, poses = (x if _is_dev(x) else np.asarray(x) for x in (points, seg, poses))
+    for name, x, cols in (('points', points, 8), ('poses', poses, 7)):
+        if len(x.shape) != 2 or int(x.shape[1]) != cols:
+            raise ValueError(f'grid_map: {name} [*, {cols}] expected')
+    F = int(seg.shape[0]) - 1
+    if len(seg.shape) != 1 or F < 0 or int(poses.shape[0]) != F:
+        raise ValueError('grid_map: seg [F + 1] and poses [F, 7] expected')
+    c = _ctx(ctx)
+    torch = c.torch
+
+    def dev(x, dtype, npdtype):
+        if x is None:
+            return None
+        if _is_dev(x):
+            return (x if x.dtype == dtype else x.to(dtype)).contiguous()
+        return c.to_dev(np.ascontiguousarray(np.asarray(x, dtype=npdtype)))
+    gm = mapping.GridMap(c, free=free, **params)
+    if F > 0:
+        gm.update(dev(points, torch.float32, np.float32), dev(seg, torch.int64, np.int64),
+                  dev(poses, torch.float64, np.float64), weight=dev(weight, torch.float32, np.float32))
+    res = gm.results()
+    if res['stats'] is None:
+        res['stats'] = np.zeros((0, 4), np.int32)
+    return res
+
+
 def confidence(sigs, az_deg: Sequence[float], antenna_positions, lambda_c, ctx: Optional[Context] = None):
     """compute_angle_confidence for N (signature, angle) pairs (robust_angle_estimation.py:88-138)."""
     c = _ctx(ctx)

@@ -591,6 +591,58 @@ class Context:
             _ptr(rows), _ptr(om)), 'rsl_scan_register')
         return rows, om
 
+    def map_update(self, points, seg, poses, hits, *, grid, free=None, weight=None, r_min: float = 0.5,
+                   r_max: float = 75.0, min_db: float = -math.inf, n: Optional[int] = None, want_stats: bool = True,
+                   out=None):
+        """Grid map update (rsl_map_update, specified in include/rsl.h): every frame adds 1 to the hit count of the
+        cells its accepted points fall into and, with `free`, 1 to the free count of the cells on the rays from the
+        sensor's cell to them.  points f32 [N, 8] (the rows of cell_refine), seg i64 [F + 1] (cell_base; clamped to n,
+        default N), poses f64 [F, 7] = (p, q) (TrajectoryReducer.poses), weight f32 [N] or None, grid = (x0, y0, cell);
+        hits / free: contiguous int32 (the bits are unsigned counts) [ny, nx], added to in place, free None: no rays.
+        out: optional dict of a preallocated stats i32 [F, 4].  Returns stats = {accepted points, hit cells, free
+        cells, flag (1: pose not finite or too far from the map)} per frame, or None."""
+        torch = self.torch
+        F = int(seg.shape[0]) - 1
+        if points.dim() != 2 or int(points.shape[1]) != 8 or points.dtype != torch.float32 or not points.is_contiguous():
+            raise ValueError('map_update: points must be contiguous float32 [N, 8]')
+        N = int(points.shape[0]) if n is None else min(int(n), int(points.shape[0]))
+        if int(points.shape[0]) == 0:  # an empty tensor has no address; the function wants one
+            points = self.empty((1, 8), torch.float32)
+        if seg.dtype != torch.int64 or seg.dim() != 1 or not seg.is_contiguous():
+            raise ValueError('map_update: seg must be contiguous int64 [F + 1]')
+        if poses.dtype != torch.float64 or poses.dim() != 2 or int(poses.shape[0]) < F or int(poses.shape[1]) != 7 or \
+                not poses.is_contiguous():
+            raise ValueError(f'map_update: poses must be contiguous float64 [{F}, 7]')
+        if weight is not None and (weight.dtype != torch.float32 or weight.dim() != 1 or int(weight.shape[0]) < N):
+            raise ValueError('map_update: weight must be float32 with one entry per point')
+        for name, t in (('hits', hits), ('free', free)):
+            if t is not None and (t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous()
+                                  or t.shape != hits.shape):
+                raise ValueError(f'map_update: {name} must be a contiguous int32 [ny, nx] plane')
+        ny, nx = int(hits.shape[0]), int(hits.shape[1])
+        stats = self._buf(out, 'stats', (max(F, 1), 4), torch.int32) if want_stats else None
+        g4 = (c_double * 4)(float(grid[0]), float(grid[1]), float(grid[2]), 0.0)
+        self._bind()
+        self.check(self.lib.rsl_map_update(self.h, _ptr(points), _ptr(seg), F, N, _ptr(weight), _ptr(poses), g4, nx, ny,
+                                           float(r_min), float(r_max), float(min_db), _ptr(hits), _ptr(free),
+                                           _ptr(stats)), 'rsl_map_update')
+        return stats
+
+    def map_logodds(self, hits, free=None, *, l_occ: float = 0.85, l_free: float = 0.4, l_min: float = -4.0,
+                    l_max: float = 4.0, out=None):
+        """Clamped log-odds of the grid map's counts (rsl_map_logodds): f32, shaped as hits,
+        clamp(hits l_occ - free l_free, l_min, l_max) in fp64, rounded to f32 once."""
+        torch = self.torch
+        for name, t in (('hits', hits), ('free', free)):
+            if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()
+                                  or t.shape != hits.shape):
+                raise ValueError(f'map_logodds: {name} must be a contiguous int32 plane')
+        lo = out if out is not None else self.empty(tuple(hits.shape), torch.float32)
+        self._bind()
+        self.check(self.lib.rsl_map_logodds(self.h, _ptr(hits), _ptr(free), hits.numel(), float(l_occ), float(l_free),
+                                            float(l_min), float(l_max), _ptr(lo)), 'rsl_map_logodds')
+        return lo
+
     def confidence(self, rds, c_frame, c_rc, gidx, steer, n: int):
         torch = self.torch
         _, A, S, C = rds.shape

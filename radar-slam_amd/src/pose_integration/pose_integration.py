@@ -113,6 +113,28 @@ class PoseIntegrator:
                 'total_distance': total_distance, 'total_rotation': total_rotation,
                 'duration': timestamps[-1] - timestamps[0], 'num_points': N}
 
+    def grid_map(self, scans, positions: np.ndarray, quaternions: np.ndarray, **params) -> Dict:
+        """The occupancy grid of a sequence of scans seen from a trajectory (rsl.ops.grid_map; rsl_map_update and
+        rsl_map_logodds, specified in include/rsl.h).  scans: one list per frame of the target dicts of
+        AngleEstimator.process_targets_refined ('x_m', 'y_m' in sensor coordinates; an optional 'weight', 0: a mover,
+        and 'power_db'); positions [F, 3] and quaternions [F, 4] = (w, x, y, z): the frames' world poses, e.g. of
+        integrate_translational_velocity and of the device quaternions.  params: origin, shape = (ny, nx), cell, r_min,
+        r_max, min_db, free, l_occ, l_free, l_min, l_max.  Returns dict(hits, free, logodds, stats) of host arrays."""
+        from rsl import ops
+        F = len(scans)
+        pos = np.asarray(positions, np.float64).reshape(-1, 3)
+        quat = np.asarray(quaternions, np.float64).reshape(-1, 4)
+        if len(pos) != F or len(quat) != F:
+            raise ValueError("scans, positions and quaternions must have the same length")
+        seg = np.concatenate([[0], np.cumsum([len(s) for s in scans])]).astype(np.int64)
+        pts = np.zeros((int(seg[-1]), 8), np.float32)
+        w = np.ones(int(seg[-1]), np.float32)
+        for f, targets in enumerate(scans):
+            for n, t in enumerate(targets, int(seg[f])):
+                pts[n, 3], pts[n, 4], pts[n, 5] = t['x_m'], t['y_m'], t.get('power_db', 0.0)
+                w[n] = t.get('weight', 1.0)
+        return ops.grid_map(pts, seg, np.concatenate([pos, quat], axis=1), weight=w, **params)
+
     def transform_to_world_frame(self, trajectory: Dict, initial_world_pose: Optional[Dict] = None) -> Dict:
         if initial_world_pose is None:
             initial_world_pose = {'position': np.array([0, 0, 0]), 'orientation': np.array([0, 0, 0])}
