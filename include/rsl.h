@@ -345,6 +345,21 @@ int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const vo
                     const void* ncell_dev, long long ncell, double esprit_scale, const void* gidx,
                     const void* az_table, void* sig_out, void* esprit_deg, void* phase, void* az_out);
 
+/* The point cloud: what rsl_cell_refine writes and rsl_scan_register and rsl_map_update read (device side:
+ *     rsl_cloud.h).  points f32 [n][RSL_POINT_COLS]: 32-byte rows, the columns in the order of the ids below.
+ *     seg i64 [F + 1] (cell_base): frame f owns the rows [clamp(seg[f], 0, n), clamp(seg[f + 1], 0, n)), none when the
+ *     segment descends; n is the number of rows in use.  weight f32 [n] (nullable = 1).  A point counts with its
+ *     weight when x and y are finite and the weight is > 0, and with 0 otherwise (a NaN weight is not > 0). */
+#define RSL_POINT_COLS 8
+#define RSL_POINT_RANGE 0
+#define RSL_POINT_DOPPLER 1
+#define RSL_POINT_AZ 2
+#define RSL_POINT_X 3
+#define RSL_POINT_Y 4
+#define RSL_POINT_POWER_DB 5
+#define RSL_POINT_RANGE_OFFSET 6
+#define RSL_POINT_DOPPLER_OFFSET 7
+
 /* Point cloud: sub-bin range, Doppler and azimuth and the position of every detected cell (rsl_refine.hip; the
  *     reference project has no counterpart, this comment is the specification).  Cells and n as in rsl_doa:
  *     n = min(*ncell_dev, ncell); slots beyond n are not written; ncell = 0 launches nothing.  rds c64 [*, A, S, C],
@@ -371,10 +386,11 @@ int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const vo
  *        G - 1, or c >= 0, or c is not finite: az = az_table[g].  Otherwise u* = (u_{g-1} + u_g) / 2 - d01 / (2 c)
  *        clamped to [(u_{g-1} + u_g) / 2, (u_g + u_{g+1}) / 2] and az = asin(u*).  MUSIC's rank-1 spectrum
  *        1 / (M - B) has the same argmax, so the rule serves both methods.
- *     4. out_az f64 [n] (nullable) = az.  out_points f32 [n][8] (nullable; 32-byte rows, 16-byte aligned), each row
- *        computed in fp64 and rounded once: with range = r0 + r_step (i + dr), doppler = d0 + d_step (j + dd) (the
- *        product and the sum each rounded, not fused: a label that cancels to nearly 0 is the same everywhere):
- *          {range, doppler, az, x = range cos az, y = range sin az, 10 log10(P0 + 1e-12), dr, dd}
+ *     4. out_az f64 [n] (nullable) = az.  out_points (nullable; 16-byte aligned): the rows of the point cloud above,
+ *        each value computed in fp64 and rounded once: range = r0 + r_step (i + dr), doppler = d0 + d_step (j + dd)
+ *        (the product and the sum each rounded, not fused: a label that cancels to nearly 0 is the same everywhere),
+ *        az, x = range cos az, y = range sin az, power_db = 10 log10(P0 + 1e-12), range_offset = dr,
+ *        doppler_offset = dd.
  *        No wrap is applied to the Doppler label: bin C - 1 with dd > 0 reads slightly past the axis end.
  *     RSL_ERR_INVALID: A outside [2, 32]; S, C or G <= 0; an unknown mode; a step that is not finite; both outputs
  *     null; out_points not 16-byte aligned; null rds, lists, gidx, az_table, steer_c64 or axes4 with ncell > 0.
@@ -506,10 +522,9 @@ int rsl_velocity_consensus(rsl_handle h, const void* az, const void* gidx, const
 /* Scan registration: the yaw increment and the displacement between the point clouds of consecutive frames
  *     (rsl_register.hip, k_scan_register; the reference project has no counterpart, this comment is the
  *     specification).  The Doppler solve of one radar observes only (v_x, v_y); this supplies the rotation.
- *     Inputs (device unless marked host): points f32 [n][8], the rows of rsl_cell_refine (columns 3, 4 = x, y);
- *     seg i64 [F + 1] (cell_base), both ends of every frame clamped to [0, n] as the velocity solvers do; weight f32 [n]
- *     (nullable = 1): a point with a non-finite x or y, or a weight that is not > 0, has weight 0; rc i32 [n]
- *     (nullable) with C and axes4 (host) = {r0, r_step, ., .} as in rsl_cell_refine, used for culling only (below);
+ *     Inputs (device unless marked host): points, seg, n and weight: the point cloud above, of which x, y and the
+ *     weight each point counts with are read; rc i32 [n] (nullable) with C and axes4 (host) = {r0, r_step, ., .} as in
+ *     rsl_cell_refine, used for culling only (below);
  *     prev_points / prev_weight / prev_rc (nullable): the cloud frame 0 is registered against, its length
  *     min(prev_n, *prev_n_dev) (prev_n_dev i64 [1], nullable); init f64 [F][3] (nullable = zeros), the start
  *     (theta, t_x, t_y) of every frame, a component that is not finite counting as 0.
@@ -560,9 +575,8 @@ int rsl_scan_register(rsl_handle h, const void* points, const void* seg, int F, 
  *     from run to run and independent of the frame order and of how the frames are split over launches or ranks, and
  *     rank maps merge by integer addition.  Clamped log-odds are derived from the counts at the end (rsl_map_logodds),
  *     not clamped per update: a per-update clamp would make the map depend on the order of the frames.
- *     Inputs (device unless marked host): points f32 [n][8], the rows of rsl_cell_refine (columns 3, 4 = x, y, column
- *     5 = power_db; no other column is read); seg i64 [F + 1] (cell_base), both ends of every frame clamped to [0, n];
- *     weight f32 [n] (nullable); poses f64 [F][7] = (p_x, p_y, p_z, q_w, q_x, q_y, q_z), the rows of the trajectory
+ *     Inputs (device unless marked host): points, seg, n and weight: the point cloud above, of which x, y, power_db
+ *     and the weight are read; poses f64 [F][7] = (p_x, p_y, p_z, q_w, q_x, q_y, q_z), the rows of the trajectory
  *     reduction: the sensor frame is the body frame (no mounting offset); grid4 (host) = {x0, y0, cell, unused}: the
  *     world position of the corner of cell (0, 0) and the cell size; hits, free_ u32 [ny][nx], both in / out: the call
  *     adds to them and never clears them; free_ nullable: no ray is cast; stats i32 [F][4] (nullable).
@@ -572,9 +586,9 @@ int rsl_scan_register(rsl_handle h, const void* points, const void* seg, int F, 
  *     r11 = 1 - 2 (q_x q_x + q_z q_z): the quaternion as given, not normalised; only the planar 2 x 2 block is used and
  *     p_z is ignored.  Origin cell: ox = floor((p_x - x0) inv), oy likewise.  If any of p_x, p_y, r00, r01, r10, r11 is
  *     not finite, or |(p - x0) inv| >= 2^30 in x or y, the frame counts nothing and its stats row is {0, 0, 0, 1}.
- *     Per point, x and y promoted to fp64, accepted iff (1) x and y are finite; (2) the weight is null or > 0 (a NaN
- *     weight is not); (3) not (power_db < min_db), so -inf disables the floor; (4) r_min^2 <= x x + y y <= r_max^2, both
- *     squares formed as products on the host; then X = (r00 x + r01 y) + p_x, Y = (r10 x + r11 y) + p_y,
+ *     Per point, x and y promoted to fp64, accepted iff (1), (2) it counts in the point cloud above (x and y finite,
+ *     the weight null or > 0); (3) not (power_db < min_db), so -inf disables the floor; (4) r_min^2 <= x x + y y <=
+ *     r_max^2, both squares formed as products on the host; then X = (r00 x + r01 y) + p_x, Y = (r10 x + r11 y) + p_y,
  *     hx = floor((X - x0) inv), hy likewise, and (5) 0 <= hx < nx and 0 <= hy < ny, compared as doubles before any
  *     conversion; (6) |hx - ox| <= Rw and |hy - oy| <= Rw.  H_f is the set of the accepted points' cells.
  *     Free set (only with free_): for every cell (hx, hy) of H_f, dx = |hx - ox|, dy = |hy - oy|, sx = +1 if hx >= ox

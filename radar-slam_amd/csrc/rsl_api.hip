@@ -121,6 +121,11 @@ rsl::CellList cell_list(const void* rds, int A, int S, int C, const void* c_fram
   return {(const float2*)rds, A, S, C, (const int*)c_frame, (const int*)c_rc, (const long long*)ncell_dev, ncell};
 }
 
+// The point cloud of a registration or map entry point from its untyped arguments (rsl_cloud.h).
+rsl::CloudView cloud_view(const void* points, const void* seg, long long n, int F, const void* weight) {
+  return {(const float*)points, (const long long*)seg, n, F, (const float*)weight};
+}
+
 // The sections of a steering table that rsl_steer_table_build(G, M) wrote (rsl_doa_common.h SteerLayout).
 struct SteerView {
   rsl::SteerLayout lay;
@@ -780,8 +785,8 @@ int rsl_scan_register(rsl_handle h, const void* points, const void* seg, int F, 
     return fail(h, RSL_ERR_INVALID, msg.c_str());
   }
   if (F == 0) return RSL_OK;
-  const rsl::RegProblem p{(const float*)points, (const long long*)seg, n, F, (const float*)weight, (const int*)rc,
-                          cull ? C : 1, cull ? axes4[0] : 0.0, cull ? 1.0 / axes4[1] : 0.0,
+  const rsl::RegProblem p{cloud_view(points, seg, n, F, weight), (const int*)rc, cull ? C : 1,
+                          cull ? axes4[0] : 0.0, cull ? 1.0 / axes4[1] : 0.0,
                           (const float*)prev_points, prev_points ? (const float*)prev_weight : nullptr,
                           prev_points ? (const int*)prev_rc : nullptr, prev_points ? prev_n : 0,
                           prev_points ? (const long long*)prev_n_dev : nullptr, (const double*)init, h_fine, h_coarse,
@@ -813,9 +818,8 @@ int rsl_map_update(rsl_handle h, const void* points, const void* seg, int F, lon
   if (!(rw <= (double)RSL_MAP_MAX_RW))
     return fail(h, RSL_ERR_UNSUPPORTED, "rsl_map_update: ceil(r_max / cell) + 1 above RSL_MAP_MAX_RW");
   if (F == 0) return RSL_OK;
-  const rsl::MapProblem p{(const float*)points, (const long long*)seg, n, F, (const float*)weight,
-                          (const double*)poses, grid4[0], grid4[1], inv, nx, ny, (int)rw,
-                          r_min * r_min, r_max * r_max, min_db};
+  const rsl::MapProblem p{cloud_view(points, seg, n, F, weight), (const double*)poses, grid4[0], grid4[1], inv, nx, ny,
+                          (int)rw, r_min * r_min, r_max * r_max, min_db};
   Scope sc(h, RSL_K_AUX);
   return hip_check(h, rsl::launch_map_update(h->stream, p, (unsigned*)hits, (unsigned*)free_, (int*)stats),
                    "map_update");

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rsl_cloud.h"   // CloudView, the point cloud of the registration and map problems
 #include "rsl_launch.h"  // what every launcher launches with
 
 namespace rsl {
@@ -143,7 +144,7 @@ hipError_t launch_cell_extras(hipStream_t st, CellList cl, double esprit_scale, 
                               double* az_out);
 // Point cloud (rsl_refine.hip; the contract is rsl_cell_refine's in rsl.h): sub-bin range / Doppler offsets from the
 // five powers around each cell (power f32 [*, S, C], or null: formed from the RDS), azimuth at the parabola vertex of
-// the beamforming values around gidx over steer c64 [G][A] -> out_points f32 [n][8] (16-B aligned), out_az f64 [n].
+// the beamforming values around gidx over steer c64 [G][A] -> out_points, the rows of rsl_cloud.h (16-B aligned), out_az f64 [n].
 hipError_t launch_cell_refine(hipStream_t st, CellList cl, const float* power, const int* gidx, const double* az_table,
                               const float2* steer, int G, int range_mode, int doppler_mode, const double* axes4,
                               float* out_points, double* out_az);
@@ -178,11 +179,7 @@ hipError_t launch_velocity_consensus(hipStream_t st, const VelProblem& p, double
 // Scan registration (rsl_register.hip; the contract is rsl_scan_register's in rsl.h), checked and typed by
 // rsl_scan_register (rsl_api.hip).  Passed to the kernel by value.  inv_step = 1 / axes4[1], 0 without axes.
 struct RegProblem {
-  const float* points;
-  const long long* seg;
-  long long n;
-  int F;
-  const float* weight;
+  CloudView cloud;
   const int* rc;
   int C;
   double r0, inv_step;
@@ -201,11 +198,7 @@ hipError_t launch_scan_register(hipStream_t st, const RegProblem& p, double* out
 // Grid map (rsl_map.hip; the contract is rsl_map_update's in rsl.h), checked and typed by rsl_map_update (rsl_api.hip).
 // Passed to the kernel by value.  inv = 1 / cell, Rw = (int)ceil(r_max inv) + 1, rmin2 / rmax2 the squared range gate.
 struct MapProblem {
-  const float* points;
-  const long long* seg;
-  long long n;
-  int F;
-  const float* weight;
+  CloudView cloud;
   const double* poses;
   double x0, y0, inv;
   int nx, ny, Rw;

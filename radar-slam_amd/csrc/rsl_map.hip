@@ -30,8 +30,6 @@ constexpr int kMapThreads = 1024;
 constexpr int kMapWaves = kMapThreads / 64;
 constexpr int kLogoddsThreads = 256;
 
-RSL_DEV long long map_clamp(long long v, long long n) { return v < 0 ? 0 : (v > n ? n : v); }
-
 }  // namespace
 
 __global__ __launch_bounds__(kMapThreads) void k_map_update(MapProblem p, unsigned* __restrict__ hits,
@@ -68,13 +66,13 @@ __global__ __launch_bounds__(kMapThreads) void k_map_update(MapProblem p, unsign
   __syncthreads();
 
   // 1. hits
-  const long long b = map_clamp(p.seg[f], p.n), e = map_clamp(p.seg[f + 1], p.n);
+  long long b, e;
+  cloud_frame(p.cloud, f, b, e);
   int acc = 0;
   for (long long i = b + t; i < e; i += kMapThreads) {
-    const float* row = p.points + i * 8;
-    const float xf = row[3], yf = row[4], pw = row[5];
-    if (!(isfinite(xf) && isfinite(yf))) continue;
-    if (p.weight && !(p.weight[i] > 0.f)) continue;
+    const float pw = p.cloud.points[i * RSL_POINT_COLS + RSL_POINT_POWER_DB];  // first: one 12-byte load with x, y
+    float xf, yf;
+    if (!(cloud_point(p.cloud.points, p.cloud.weight, i, xf, yf) > 0.f)) continue;
     if ((double)pw < p.min_db) continue;
     const double x = (double)xf, y = (double)yf;
     const double r2 = x * x + y * y;
@@ -164,7 +162,7 @@ __global__ __launch_bounds__(kLogoddsThreads) void k_map_logodds(const unsigned*
 
 hipError_t launch_map_update(hipStream_t st, const MapProblem& p, unsigned* hits, unsigned* free_, int* stats) {
   const long long W = 2ll * p.Rw + 1, nw = (W * W + 31) / 32;
-  return launch(st, k_map_update, p.F, kMapThreads, (size_t)nw * 4 * (free_ ? 2 : 1), p, hits, free_, stats);
+  return launch(st, k_map_update, p.cloud.F, kMapThreads, (size_t)nw * 4 * (free_ ? 2 : 1), p, hits, free_, stats);
 }
 
 hipError_t launch_map_logodds(hipStream_t st, const unsigned* hits, const unsigned* free_, long long ncells,

@@ -162,6 +162,9 @@ __global__ __launch_bounds__(256) void k_cell_refine(CellList cl, const float* _
     const double dop = axis_label(d0, d_step, (double)j + dd);
     const double x = range * cos(az), y = range * sin(az);
     const double db = 10.0 * log10((double)p0 + 1e-12);
+    static_assert(RSL_POINT_COLS == 8 && RSL_POINT_RANGE == 0 && RSL_POINT_DOPPLER == 1 && RSL_POINT_AZ == 2 &&
+                      RSL_POINT_X == 3 && RSL_POINT_Y == 4 && RSL_POINT_POWER_DB == 5 && RSL_POINT_RANGE_OFFSET == 6 &&
+                      RSL_POINT_DOPPLER_OFFSET == 7, "the two 16-byte stores below write the row in this order");
     float4* row = out_points + (size_t)c * 2;
     row[0] = make_float4((float)range, (float)dop, (float)az, (float)x);
     row[1] = make_float4((float)y, (float)db, (float)dr, (float)dd);

@@ -33,19 +33,19 @@ constexpr int kRegRows = 4096;                     // range rows the LDS row tab
 constexpr int kRegScore = (kRegCand + kRegChunk - 1) / kRegChunk * kRegChunk;
 
 struct RegCloud {
-  const float* pts;  // [*][8]
+  const float* pts;  // rows of rsl_cloud.h
   const float* w;    // nullable
   const int* rc;     // nullable
   long long b, e;    // the cloud's rows, inside the arrays
 };
 
-// Point i of a cloud: coordinates promoted to fp64, and the weight the specification gives it.
+// Point i of a cloud: cloud_point's coordinates and weight promoted to fp64.
 RSL_DEV double reg_point(const RegCloud& c, long long i, double& x, double& y) {
-  const float xf = c.pts[i * 8 + 3], yf = c.pts[i * 8 + 4];
-  const float wf = c.w ? c.w[i] : 1.f;
+  float xf, yf;
+  const float wf = cloud_point(c.pts, c.w, i, xf, yf);
   x = (double)xf;
   y = (double)yf;
-  return (isfinite(xf) && isfinite(yf) && wf > 0.f) ? (double)wf : 0.0;
+  return (double)wf;
 }
 
 // First index of [b, e) whose rc is >= key (rc ascends inside a frame); e if there is none.
@@ -92,8 +92,6 @@ RSL_DEV void reg_load(const RegCloud& q, long long j0, long long e, double (&x)[
   }
 }
 
-RSL_DEV long long reg_clamp(long long v, long long n) { return v < 0 ? 0 : (v > n ? n : v); }
-
 }  // namespace
 
 __global__ __launch_bounds__(kRegThreads) void k_scan_register(RegProblem p, double* __restrict__ out,
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(kRegThreads) void k_scan_register(RegProblem p, dou
   double* o = out + f * 8;
 
   if (t == 0 && omega && f == 0) {  // the last row has no successor in this call
-    double* w = omega + (size_t)(p.F - 1) * 3;
+    double* w = omega + (size_t)(p.cloud.F - 1) * 3;
     w[0] = w[1] = w[2] = 0.0;
   }
   const bool has_prev = p.prev_points != nullptr;
@@ -119,16 +117,16 @@ __global__ __launch_bounds__(kRegThreads) void k_scan_register(RegProblem p, dou
     return;
   }
 
-  RegCloud P{p.points, p.weight, p.rc, reg_clamp(p.seg[f], p.n), reg_clamp(p.seg[f + 1], p.n)};
-  if (P.e < P.b) P.e = P.b;
+  RegCloud P{p.cloud.points, p.cloud.weight, p.rc, 0, 0};
+  cloud_frame(p.cloud, f, P.b, P.e);
   RegCloud Q;
   if (f == 0) {
     long long m = p.prev_n;
     if (p.prev_n_dev && *p.prev_n_dev < m) m = *p.prev_n_dev;
     Q = RegCloud{p.prev_points, p.prev_weight, p.prev_rc, 0, m < 0 ? 0 : m};
   } else {
-    Q = RegCloud{p.points, p.weight, p.rc, reg_clamp(p.seg[f - 1], p.n), P.b};
-    if (Q.b > Q.e) Q.b = Q.e;
+    Q = P;  // the same arrays, the rows of the frame before
+    cloud_frame(p.cloud, f - 1, Q.b, Q.e);
   }
 
   // the reference's range rows -> first point, once per workgroup (every thread computes the same bounds)
@@ -348,8 +346,8 @@ __global__ __launch_bounds__(kRegThreads) void k_scan_register(RegProblem p, dou
 }
 
 hipError_t launch_scan_register(hipStream_t st, const RegProblem& p, double* out, double* omega) {
-  if (p.F <= 0) return hipSuccess;
-  return launch(st, k_scan_register, p.F, kRegThreads, 0, p, out, omega);
+  if (p.cloud.F <= 0) return hipSuccess;
+  return launch(st, k_scan_register, p.cloud.F, kRegThreads, 0, p, out, omega);
 }
 
 }  // namespace rsl

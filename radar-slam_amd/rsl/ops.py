@@ -14,7 +14,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, tables
-from .runtime import Context, _ptr, emit_compact_supported, get_context, unpack_coord
+from .runtime import POINT_COLUMNS, Context, _ptr, emit_compact_supported, get_context, unpack_coord
 
 
 def _ctx(ctx: Optional[Context]) -> Context:
@@ -33,6 +33,15 @@ def as_dev_c64(ctx: Context, x):
     if not np.iscomplexobj(a):
         a = a.astype(np.complex128)
     return ctx.to_dev(a.astype(np.complex64))
+
+
+def dev(ctx: Context, x, dtype, npdtype):
+    """x (None, a host array or a device tensor) as a contiguous device tensor of `dtype` (npdtype on the host)."""
+    if x is None:
+        return None
+    if _is_dev(x):
+        return (x if x.dtype == dtype else x.to(dtype)).contiguous()
+    return ctx.to_dev(np.ascontiguousarray(np.asarray(x, dtype=npdtype)))
 
 
 def to_host(t, dtype=None):
@@ -404,9 +413,6 @@ def cell_extras(*, sigs=None, rds=None, rbins=None, dbins=None, esprit_scale=1 /
             to_host(ph[:N]) if want_phase else None)
 
 
-POINT_COLUMNS = ('range', 'doppler', 'az', 'x', 'y', 'power_db', 'range_offset', 'doppler_offset')
-
-
 def refine_cells(steer_c128: np.ndarray, az_deg_grid, *, rds, rbins, dbins, gidx=None, power=None, method='music',
                  range_mode='hann', doppler_mode='rect', axes=(0.0, 1.0, 0.0, 1.0), ctx: Optional[Context] = None):
     """The point cloud of the cells (rbins, dbins) of an RDS [A, S, C] (rsl_cell_refine, specified in include/rsl.h):
@@ -450,7 +456,7 @@ REGISTRATION_COLUMNS = ('theta', 't_x', 't_y', 'support', 'rms', 'peak_ratio', '
 def register_scans(points, seg, *, weight=None, rc=None, C: int = 0, axes=None, prev=None, init=None,
                    ctx: Optional[Context] = None, **params):
     """Scan registration of F point clouds, each against the one before it (rsl_scan_register, specified in
-    include/rsl.h): points f32 [N, 8] (the rows of refine_cells / the chain's 'points'; columns 3 and 4 are x and y),
+    include/rsl.h): points f32 [N, 8] (the rows of refine_cells / the chain's 'points': POINT_COLUMNS; x and y are read),
     seg [F + 1] the frames' first rows (the chain's cell_base), weight [N] or None (the static / moving labels:
     'vel_weight'), rc i32 [N] with C and axes (tables.point_axes) to cull the pair search by range rows, prev: None or
     dict(points, weight, rc) of the cloud frame 0 is registered against, init f64 [F, 3] = (theta, t_x, t_y) start
@@ -459,31 +465,24 @@ def register_scans(points, seg, *, weight=None, rc=None, C: int = 0, axes=None, 
     REGISTRATION_COLUMNS, each column under its name, and 'omega' f64 [F, 3] for rsl_traj_scan
     (omega[f - 1] = {0, 0, theta_f / dt})."""
     c = _ctx(ctx)
-    torch = c.torch
-
-    def dev(x, dtype, npdtype):
-        if x is None:
-            return None
-        if _is_dev(x):
-            return (x if x.dtype == dtype else x.to(dtype)).contiguous()
-        return c.to_dev(np.ascontiguousarray(np.asarray(x, dtype=npdtype)))
-    pts = dev(points, torch.float32, np.float32)
-    if pts.dim() != 2 or int(pts.shape[1]) != 8:
-        raise ValueError('register_scans: points [N, 8] expected')
-    sg = dev(seg, torch.int64, np.int64)
+    f32, i32 = (c.torch.float32, np.float32), (c.torch.int32, np.int32)
+    cols = len(POINT_COLUMNS)
+    pts = dev(c, points, *f32)
+    if pts.dim() != 2 or int(pts.shape[1]) != cols:
+        raise ValueError(f'register_scans: points [N, {cols}] expected')
+    sg = dev(c, seg, c.torch.int64, np.int64)
     if sg.dim() != 1 or int(sg.shape[0]) < 1:
         raise ValueError('register_scans: seg [F + 1] expected')
     pv = None
     if prev is not None and prev.get('points') is not None:
-        pv = dict(points=dev(prev['points'], torch.float32, np.float32).reshape(-1, 8),
-                  weight=dev(prev.get('weight'), torch.float32, np.float32),
-                  rc=dev(prev.get('rc'), torch.int32, np.int32), n=prev.get('n'), n_dev=prev.get('n_dev'))
+        pv = dict(points=dev(c, prev['points'], *f32).reshape(-1, cols), weight=dev(c, prev.get('weight'), *f32),
+                  rc=dev(c, prev.get('rc'), *i32), n=prev.get('n'), n_dev=prev.get('n_dev'))
     F = int(sg.shape[0]) - 1
-    it = dev(init, torch.float64, np.float64)
+    it = dev(c, init, c.torch.float64, np.float64)
     if it is not None:
         it = it.reshape(F, 3)
-    rows, om = c.scan_register(pts, sg, weight=dev(weight, torch.float32, np.float32),
-                               rc=dev(rc, torch.int32, np.int32), C=C, axes=axes, prev=pv, init=it, **params)
+    rows, om = c.scan_register(pts, sg, weight=dev(c, weight, *f32), rc=dev(c, rc, *i32), C=C, axes=axes, prev=pv,
+                               init=it, **params)
     rows, om = to_host(rows[:F]), to_host(om[:F])
     res = {k: rows[:, i] for i, k in enumerate(REGISTRATION_COLUMNS)}
     res.update(rows=rows, omega=om)
@@ -492,8 +491,8 @@ def register_scans(points, seg, *, weight=None, rc=None, C: int = 0, axes=None, 
 
 def grid_map(points, seg, poses, *, weight=None, free: bool = True, ctx: Optional[Context] = None, **params):
     """The grid map of F point clouds seen from F poses (mapping.GridMap; rsl_map_update and rsl_map_logodds, specified
-    in include/rsl.h): points f32 [N, 8] (the rows of refine_cells / the chain's 'points'; columns 3, 4 and 5 are x, y
-    and power_db), seg [F + 1] the frames' first rows, poses f64 [F, 7] = (p_x, p_y, p_z, q_w, q_x, q_y, q_z), weight
+    in include/rsl.h): points f32 [N, 8] (the rows of refine_cells / the chain's 'points': POINT_COLUMNS; x, y and
+    power_db are read), seg [F + 1] the frames' first rows, poses f64 [F, 7] = (p_x, p_y, p_z, q_w, q_x, q_y, q_z), weight
     [N] or None (the static / moving labels: 'vel_weight').  params: origin, shape = (ny, nx), cell, r_min, r_max,
     min_db, l_occ, l_free, l_min, l_max (GridMap), checked before any device use.  Host arrays or device tensors.
     Returns a dict of host arrays: hits u32 [ny, nx], free u32 [ny, nx] (None with free=False), logodds f32 [ny, nx],
@@ -501,7 +500,7 @@ def grid_map(points, seg, poses, *, weight=None, free: bool = True, ctx: Optiona
     from . import mapping
     mapping.check_params(**params)
     points, seg, poses = (x if _is_dev(x) else np.asarray(x) for x in (points, seg, poses))
-    for name, x, cols in (('points', points, 8), ('poses', poses, 7)):
+    for name, x, cols in (('points', points, len(POINT_COLUMNS)), ('poses', poses, 7)):
         if len(x.shape) != 2 or int(x.shape[1]) != cols:
             raise ValueError(f'grid_map: {name} [*, {cols}] expected')
     F = int(seg.shape[0]) - 1
@@ -509,17 +508,10 @@ def grid_map(points, seg, poses, *, weight=None, free: bool = True, ctx: Optiona
         raise ValueError('grid_map: seg [F + 1] and poses [F, 7] expected')
     c = _ctx(ctx)
     torch = c.torch
-
-    def dev(x, dtype, npdtype):
-        if x is None:
-            return None
-        if _is_dev(x):
-            return (x if x.dtype == dtype else x.to(dtype)).contiguous()
-        return c.to_dev(np.ascontiguousarray(np.asarray(x, dtype=npdtype)))
     gm = mapping.GridMap(c, free=free, **params)
     if F > 0:
-        gm.update(dev(points, torch.float32, np.float32), dev(seg, torch.int64, np.int64),
-                  dev(poses, torch.float64, np.float64), weight=dev(weight, torch.float32, np.float32))
+        gm.update(dev(c, points, torch.float32, np.float32), dev(c, seg, torch.int64, np.int64),
+                  dev(c, poses, torch.float64, np.float64), weight=dev(c, weight, torch.float32, np.float32))
     res = gm.results()
     if res['stats'] is None:
         res['stats'] = np.zeros((0, 4), np.int32)

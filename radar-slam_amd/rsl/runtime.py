@@ -32,6 +32,36 @@ def emit_compact_supported(C: int, union_mask: bool, peak_pow: bool, want_pdb: b
     return bool(union_mask and (peak_pow or not want_pdb) and not W & (W - 1) and W <= 64)
 
 
+# The columns of a point-cloud row, in order: RSL_POINT_* in include/rsl.h, which also states what a cloud is.
+POINT_COLUMNS = ('range', 'doppler', 'az', 'x', 'y', 'power_db', 'range_offset', 'doppler_offset')
+
+
+def _per_point(fn, t, dtype, rows, what):
+    """A per-point array (weight, rc) of fn's cloud: None, or one axis of `dtype` with at least `rows` entries."""
+    if t is not None and (t.dtype != dtype or t.dim() != 1 or int(t.shape[0]) < rows):
+        raise ValueError(f"{fn}: {what} must be {str(dtype).replace('torch.', '')} with one entry per point")
+
+
+def check_cloud(fn, points, seg, n, weight, empty, what=''):
+    """The one check of a point cloud (include/rsl.h) before fn hands it to the library: points contiguous float32
+    [rows, 8]; seg contiguous int64 [F + 1] (None: a cloud without segments, scan_register's prev, what='prev ');
+    weight None or float32 with an entry for each of the N = min(n, rows) rows in use.  Shapes and dtypes only, so CPU
+    tensors serve; the one allocation, empty((1, 8), float32), stands in for empty points (an empty tensor has no
+    address; the functions want one).  Returns (points, N)."""
+    import torch
+    cols = len(POINT_COLUMNS)
+    if points.dim() != 2 or int(points.shape[1]) != cols or points.dtype != torch.float32 or not points.is_contiguous():
+        raise ValueError(f"{fn}: {what}points must be contiguous float32 [{'M' if what else 'N'}, {cols}]")
+    N = int(points.shape[0]) if n is None else min(int(n), int(points.shape[0]))
+    if int(points.shape[0]) == 0:
+        points = empty((1, cols), torch.float32)
+    if seg is not None and (seg.dtype != torch.int64 or seg.dim() != 1 or int(seg.shape[0]) < 1 or
+                            not seg.is_contiguous()):
+        raise ValueError(f'{fn}: seg must be contiguous int64 [F + 1]')
+    _per_point(fn, weight, torch.float32, N, what + 'weight')
+    return points, N
+
+
 _HIP = None
 
 
@@ -532,7 +562,8 @@ class Context:
             raise ValueError('cell_refine: power must be float32 [F, S, C]')
         cap = int(c_frame.shape[0]) if n is None else int(n)
         rows = max(cap, 1)
-        pts = self._buf(out, 'points', (rows, 8), torch.float32) if want_points else (out or {}).get('points')
+        shape = (rows, len(POINT_COLUMNS))
+        pts = self._buf(out, 'points', shape, torch.float32) if want_points else (out or {}).get('points')
         az = self._buf(out, 'az', (rows,), torch.float64) if want_az else (out or {}).get('az')
         a4 = (c_double * 4)(*[float(x) for x in axes])
         self._bind()
@@ -554,29 +585,15 @@ class Context:
         out: optional dict of preallocated rows f64 [F, 8] / omega f64 [F, 3].  Returns (rows, omega or None):
         rows = {theta, t_x, t_y, W, rms, S_best / sum S, updates, flag}, omega[f - 1] = {0, 0, theta_f / dt}."""
         torch = self.torch
+        points, N = check_cloud('scan_register', points, seg, n, weight, self.empty)
         F = int(seg.shape[0]) - 1
-        if points.dim() != 2 or int(points.shape[1]) != 8 or points.dtype != torch.float32 or not points.is_contiguous():
-            raise ValueError('scan_register: points must be contiguous float32 [N, 8]')
-        N = int(points.shape[0]) if n is None else min(int(n), int(points.shape[0]))
-        if int(points.shape[0]) == 0:  # an empty tensor has no address; the function wants one
-            points = self.empty((1, 8), torch.float32)
-
-        def per_point(t, dtype, rows, what):
-            if t is not None and (t.dtype != dtype or t.dim() != 1 or int(t.shape[0]) < rows):
-                raise ValueError(f'scan_register: {what} must be {dtype} with one entry per point')
-        per_point(weight, torch.float32, N, 'weight')
-        per_point(rc, torch.int32, N, 'rc')
+        _per_point('scan_register', rc, torch.int32, N, 'rc')
         pv = dict(prev) if prev else {}
         pp = pv.get('points')
         M = 0
-        if pp is not None:
-            if pp.dim() != 2 or int(pp.shape[1]) != 8 or pp.dtype != torch.float32 or not pp.is_contiguous():
-                raise ValueError('scan_register: prev points must be contiguous float32 [M, 8]')
-            M = int(pp.shape[0]) if pv.get('n') is None else min(int(pv['n']), int(pp.shape[0]))
-            if int(pp.shape[0]) == 0:  # an empty reference is still a reference (flag 1, not 2)
-                pp = self.empty((1, 8), torch.float32)
-            per_point(pv.get('weight'), torch.float32, M, 'prev weight')
-            per_point(pv.get('rc'), torch.int32, M, 'prev rc')
+        if pp is not None:  # an empty reference is still a reference (flag 1, not 2)
+            pp, M = check_cloud('scan_register', pp, None, pv.get('n'), pv.get('weight'), self.empty, 'prev ')
+            _per_point('scan_register', pv.get('rc'), torch.int32, M, 'prev rc')
         if init is not None and (init.dtype != torch.float64 or tuple(init.shape) != (F, 3) or
                                  not init.is_contiguous()):
             raise ValueError(f'scan_register: init must be contiguous float64 [{F}, 3]')
@@ -602,19 +619,11 @@ class Context:
         out: optional dict of a preallocated stats i32 [F, 4].  Returns stats = {accepted points, hit cells, free
         cells, flag (1: pose not finite or too far from the map)} per frame, or None."""
         torch = self.torch
+        points, N = check_cloud('map_update', points, seg, n, weight, self.empty)
         F = int(seg.shape[0]) - 1
-        if points.dim() != 2 or int(points.shape[1]) != 8 or points.dtype != torch.float32 or not points.is_contiguous():
-            raise ValueError('map_update: points must be contiguous float32 [N, 8]')
-        N = int(points.shape[0]) if n is None else min(int(n), int(points.shape[0]))
-        if int(points.shape[0]) == 0:  # an empty tensor has no address; the function wants one
-            points = self.empty((1, 8), torch.float32)
-        if seg.dtype != torch.int64 or seg.dim() != 1 or not seg.is_contiguous():
-            raise ValueError('map_update: seg must be contiguous int64 [F + 1]')
         if poses.dtype != torch.float64 or poses.dim() != 2 or int(poses.shape[0]) < F or int(poses.shape[1]) != 7 or \
                 not poses.is_contiguous():
             raise ValueError(f'map_update: poses must be contiguous float64 [{F}, 7]')
-        if weight is not None and (weight.dtype != torch.float32 or weight.dim() != 1 or int(weight.shape[0]) < N):
-            raise ValueError('map_update: weight must be float32 with one entry per point')
         for name, t in (('hits', hits), ('free', free)):
             if t is not None and (t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous()
                                   or t.shape != hits.shape):

@@ -15,6 +15,7 @@ value of every other one at least once).
   determinism           two launches give the same bits
   omega                 row f - 1 = {0, 0, theta_f / dt}, row F - 1 = 0
 """
+import functools
 import itertools
 
 import numpy as np
@@ -43,10 +44,10 @@ def host_args(c, prev, weight):
                 prev=c['prev'] if prev else None, init=c['init'])
 
 
-@pytest.fixture(scope='module')
-def refs():
-    """The reference of every distinct (prev, weight, K, iters) in fp64 and long double, with its traces: computed once,
-    shared and left unchanged."""
+@functools.lru_cache(maxsize=None)
+def reference_rows():
+    """The reference of every distinct (prev, weight, K, iters) in fp64 and long double, with its traces: computed once
+    per session (tests/test_gpu_cloud.py takes its tolerances from the same rows), shared and left unchanged."""
     c = R.gpu_case()
     out = {}
     for _, prev, weight, K, iters in VARIANTS:
@@ -59,6 +60,11 @@ def refs():
         wide, _ = R.register(**a, K=K, iters=iters, dtype=R.WIDE)
         out[key] = dict(rows=r64, omega=o64, wide=wide, traces=tr)
     return out
+
+
+@pytest.fixture(scope='module')
+def refs():
+    return reference_rows()
 
 
 @pytest.fixture(scope='module')
@@ -188,6 +194,8 @@ def test_argument_errors(ctx, dev):
         ctx.scan_register(dev['points'], dev['seg'], prev=dev['prev'])
     with pytest.raises(ValueError):
         ctx.scan_register(dev['points'][:, :7].contiguous(), dev['seg'])
+    with pytest.raises(ValueError):  # the kernel would read an int32 seg as int64, past its end
+        ctx.scan_register(dev['points'], dev['seg'].to(ctx.torch.int32))
     with pytest.raises(ValueError):
         ctx.scan_register(dev['points'], dev['seg'], init=dev['init'][:2].contiguous())
     from rsl import _lib
