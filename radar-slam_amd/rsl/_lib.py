@@ -42,7 +42,7 @@ _P = c_void_p
 # the handle and the problem the three velocity solvers share: az, gidx, az_table, G, y, amask, seg, n, F, k, ridge,
 # bounds4
 _VEL = [_P, _P, _P, _P, c_int, _P, _P, _P, c_longlong, c_int, c_double, c_double, POINTER(c_double)]
-# name -> (restype, argtypes); must mirror include/rsl.h (tests/test_abi.py checks both directions)
+# name -> (restype, argtypes); must mirror include/rsl.h (tests/test_abi_host.py checks every type, both directions)
 SIGNATURES = {
     'rsl_version': (c_int, []),
     'rsl_create': (c_int, [POINTER(c_void_p), c_int]),
@@ -120,6 +120,55 @@ SIGNATURES = {
     'rsl_pose_rte': (c_int, [_P, _P, _P, c_longlong, _P, c_int, _P, _P, _P, _P]),
     'rsl_bvls': (c_int, [_P, _P, _P, c_longlong, _P, c_double, c_int, c_double, _P, _P, _P]),
 }
+
+
+def _pointer(a):
+    """A c_void_p slot: None stays None, a tensor (anything with data_ptr()) gives its address, an int or a c_void_p
+    passes."""
+    if a is None:
+        return None
+    addr = getattr(a, 'data_ptr', None)
+    return a if addr is None else c_void_p(addr())
+
+
+def _host_array(ctype):
+    """A POINTER(ctype) slot: None and what ctypes already takes (an array, a pointer, byref) pass; a Python sequence
+    or a numpy array becomes a ctype array of its length."""
+    scalar = float if ctype in (c_double, c_float) else int
+
+    def conv(a):
+        if a is None or isinstance(a, ctypes.Array) or not hasattr(a, '__len__'):
+            return a
+        return (ctype * len(a))(*[scalar(x) for x in a])
+    return conv
+
+
+def _converter(ctype):
+    if ctype is c_void_p:
+        return _pointer
+    if ctype in (c_int, c_longlong, c_ulonglong):
+        return int
+    if ctype is c_double:
+        return float
+    return _host_array(ctype._type_)
+
+
+# name -> one converter per argument after the handle, for every entry point that takes the handle first and returns
+# the c_int status: the calls Context.call makes
+CONVERTERS = {name: tuple(_converter(t) for t in args[1:]) for name, (res, args) in SIGNATURES.items()
+              if res is c_int and args and args[0] is c_void_p}
+# name -> the positions (after the handle) of its c_void_p slots: the device pointers
+POINTER_SLOTS = {name: tuple(i for i, t in enumerate(SIGNATURES[name][1][1:]) if t is c_void_p) for name in CONVERTERS}
+
+
+def marshal(name, args):
+    """The arguments of entry point `name` after the handle, converted as its SIGNATURES row says (a pure function: no
+    library, no device).  TypeError when the count differs."""
+    conv = CONVERTERS[name]
+    if len(args) != len(conv):
+        raise TypeError(f'{name}: {len(conv)} arguments after the handle expected, {len(args)} given')
+    return [f(a) for f, a in zip(conv, args)]
+
 
 _lib = None
 

@@ -9,7 +9,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .runtime import Context, _ptr, get_context
+from .runtime import Context, get_context
 
 
 def _poses(ctx, x):
@@ -41,10 +41,8 @@ class PoseAlignment:
         self.aligned = e((n, 7), torch.float64)
         self.ape_err = e((3, n), torch.float64)
         self.ape_stats = e((3, 5), torch.float64)
-        ctx._bind()
-        ctx.check(ctx.lib.rsl_pose_align(ctx.h, _ptr(self.est), _ptr(self.gt), n, _ptr(self.scratch),
-                                         _ptr(self.align), _ptr(self.aligned), _ptr(self.ape_err),
-                                         _ptr(self.ape_stats)), 'rsl_pose_align')
+        ctx.call('rsl_pose_align', self.est, self.gt, n, self.scratch, self.align, self.aligned, self.ape_err,
+                 self.ape_stats)
 
     def _scratch_for(self, nlen):
         import torch
@@ -65,9 +63,7 @@ class PoseAlignment:
         err = ctx.empty((nlen, self.n), torch.float64)
         cnt = ctx.empty((nlen,), torch.int64)
         st = ctx.empty((nlen, 5), torch.float64)
-        ctx._bind()
-        ctx.check(ctx.lib.rsl_pose_rte(ctx.h, _ptr(self.aligned), _ptr(self.gt), self.n, _ptr(dl), nlen,
-                                       _ptr(self.scratch), _ptr(err), _ptr(cnt), _ptr(st)), 'rsl_pose_rte')
+        ctx.call('rsl_pose_rte', self.aligned, self.gt, self.n, dl, nlen, self.scratch, err, cnt, st)
         return err, cnt.cpu().numpy(), st.cpu().numpy()
 
 

@@ -14,7 +14,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, tables
-from .runtime import POINT_COLUMNS, Context, _ptr, emit_compact_supported, get_context, unpack_coord
+from .runtime import POINT_COLUMNS, Context, emit_compact_supported, get_context, unpack_coord
 
 
 def _ctx(ctx: Optional[Context]) -> Context:
@@ -61,9 +61,7 @@ def preprocess_rows(rows, table: np.ndarray, dc: bool, ctx: Optional[Context] = 
     d_in = as_dev_c64(c, a.reshape(-1, S))
     d_tab = c.to_dev(np.asarray(table, dtype=np.complex128).astype(np.complex64))
     out = c.empty(d_in.shape, c.torch.complex64)
-    c._bind()
-    c.check(c.lib.rsl_preprocess_rows(c.h, _ptr(d_in), d_in.shape[0], S, _ptr(d_tab), int(dc), _ptr(out)),
-            'rsl_preprocess_rows')
+    c.call('rsl_preprocess_rows', d_in, d_in.shape[0], S, d_tab, dc, out)
     return to_host(out, np.complex128).reshape(shape)
 
 
@@ -377,9 +375,7 @@ def subspace_music(sigs, steer_c128: np.ndarray, num_sources: int, ctx: Optional
     G = st.shape[0]
     ds, dst = c.to_dev(s.view(np.float64)), c.to_dev(st.view(np.float64))
     out = c.empty((n, G), c.torch.float64)
-    c._bind()
-    c.check(c.lib.rsl_music_subspace(c.h, _ptr(ds), n, M, int(num_sources), _ptr(dst), G, _ptr(out)),
-            'rsl_music_subspace')
+    c.call('rsl_music_subspace', ds, n, M, num_sources, dst, G, out)
     return to_host(out)
 
 
@@ -390,9 +386,7 @@ def subspace_esprit(sigs, num_sources: int, esprit_scale: float, ctx: Optional[C
     n, M = s.shape
     ds = c.to_dev(s.view(np.float64))
     out = c.empty((n,), c.torch.float64)
-    c._bind()
-    c.check(c.lib.rsl_esprit_subspace(c.h, _ptr(ds), n, M, int(num_sources), float(esprit_scale), _ptr(out)),
-            'rsl_esprit_subspace')
+    c.call('rsl_esprit_subspace', ds, n, M, num_sources, esprit_scale, out)
     return to_host(out)
 
 
@@ -550,9 +544,7 @@ def phase_model(pos, ang, x6, k, y=None, wrap=False, ridge=0.0, ctx: Optional[Co
     pred = c.empty((max(n, 1),), torch.float64)
     resid = c.empty((max(n, 1),), torch.float64) if dy is not None else None
     cost = c.empty((1,), torch.float64) if dy is not None else None
-    c._bind()
-    c.check(c.lib.rsl_phase_model(c.h, _ptr(dp), _ptr(da), n, _ptr(dx), float(k), _ptr(dy), int(wrap), float(ridge),
-                                  _ptr(pred), _ptr(resid), _ptr(cost)), 'rsl_phase_model')
+    c.call('rsl_phase_model', dp, da, n, dx, k, dy, wrap, ridge, pred, resid, cost)
     out = dict(pred=to_host(pred[:n]))
     if dy is not None:
         out['resid'] = to_host(resid[:n])
@@ -569,21 +561,14 @@ def bvls(pos, ang, y, k, lo, hi, ridge=0.0, ctx: Optional[Context] = None):
     dy = c.to_dev(np.asarray(y, np.float64))
     dlo, dhi = c.to_dev(np.asarray(lo, np.float64)), c.to_dev(np.asarray(hi, np.float64))
     out = c.empty((nv + 1,), torch.float64)
-    c._bind()
-    c.check(c.lib.rsl_bvls(c.h, _ptr(dp), _ptr(da), n, _ptr(dy), float(k), nv, float(ridge), _ptr(dlo), _ptr(dhi),
-                           _ptr(out)), 'rsl_bvls')
+    c.call('rsl_bvls', dp, da, n, dy, k, nv, ridge, dlo, dhi, out)
     o = to_host(out)
     return o[:nv], float(o[nv])
 
 
-def solve_velocity_robust(az, y, *, k, loss='tukey', c=None, scale=None, iters=30, tol=1e-9, ridge=0.0,
-                          bounds=(-50.0, 50.0, -50.0, 50.0), amask=None, ctx: Optional[Context] = None):
-    """Huber / Tukey IRLS solve of one host segment (rsl_velocity_robust, one frame): az radians [N], y observed phase
-    [N], amask optional antenna masks (multiplicity = popcount).  scale=None estimates sigma from the residuals'
-    median (dependable only below roughly 30 % coherent outliers); give the sensor's phase-noise sigma where it is
-    known.  Returns the out row by name (velocity [2], cost, rmse_w, num_inliers, num_targets, scale, iterations,
-    converged) plus weights and residuals [N]."""
-    cx = _ctx(ctx)
+def _vel_segment(cx: Context, az, y, amask):
+    """One host segment on the device for the velocity solvers: (az f64 [n], y f64 [n], amask as i32 bits or None,
+    seg = [0, n], n)."""
     az = np.ascontiguousarray(np.asarray(az, np.float64).reshape(-1))
     yy = np.ascontiguousarray(np.asarray(y, np.float64).reshape(-1))
     if az.shape != yy.shape:
@@ -597,7 +582,18 @@ def solve_velocity_robust(az, y, *, k, loss='tukey', c=None, scale=None, iters=3
         if am.shape[0] != n:
             raise ValueError('amask must have the length of y')
         d_m = cx.to_dev(pad((am & 0xffffffff).astype(np.uint32).view(np.int32)))
-    seg = cx.to_dev(np.array([0, n], np.int64))
+    return d_az, d_y, d_m, cx.to_dev(np.array([0, n], np.int64)), n
+
+
+def solve_velocity_robust(az, y, *, k, loss='tukey', c=None, scale=None, iters=30, tol=1e-9, ridge=0.0,
+                          bounds=(-50.0, 50.0, -50.0, 50.0), amask=None, ctx: Optional[Context] = None):
+    """Huber / Tukey IRLS solve of one host segment (rsl_velocity_robust, one frame): az radians [N], y observed phase
+    [N], amask optional antenna masks (multiplicity = popcount).  scale=None estimates sigma from the residuals'
+    median (dependable only below roughly 30 % coherent outliers); give the sensor's phase-noise sigma where it is
+    known.  Returns the out row by name (velocity [2], cost, rmse_w, num_inliers, num_targets, scale, iterations,
+    converged) plus weights and residuals [N]."""
+    cx = _ctx(ctx)
+    d_az, d_y, d_m, seg, n = _vel_segment(cx, az, y, amask)
     out, w, r = cx.velocity_robust(d_az, d_y, seg, k=k, loss=loss, c=c, scale=scale, iters=iters, tol=tol, ridge=ridge,
                                    bounds=bounds, amask=d_m, n=n, want_weight=True, want_resid=True)
     o = to_host(out)[0]
@@ -614,20 +610,7 @@ def solve_velocity_consensus(az, y, *, k, scale, c=None, hyps=256, min_det=0.1, 
     a minority of the cells.  Returns the out row by name (velocity [2], cost, rmse_in, num_inliers, num_targets,
     best_hypothesis, num_valid) plus weights (the inlier mask) and residuals [N]."""
     cx = _ctx(ctx)
-    az = np.ascontiguousarray(np.asarray(az, np.float64).reshape(-1))
-    yy = np.ascontiguousarray(np.asarray(y, np.float64).reshape(-1))
-    if az.shape != yy.shape:
-        raise ValueError(f'az and y must have the same length, not {az.shape[0]} and {yy.shape[0]}')
-    n = yy.shape[0]
-    pad = lambda a: a if n else np.zeros(1, a.dtype)  # an empty segment still needs a valid pointer
-    d_az, d_y = cx.to_dev(pad(az)), cx.to_dev(pad(yy))
-    d_m = None
-    if amask is not None:
-        am = np.asarray(amask).astype(np.int64).reshape(-1)
-        if am.shape[0] != n:
-            raise ValueError('amask must have the length of y')
-        d_m = cx.to_dev(pad((am & 0xffffffff).astype(np.uint32).view(np.int32)))
-    seg = cx.to_dev(np.array([0, n], np.int64))
+    d_az, d_y, d_m, seg, n = _vel_segment(cx, az, y, amask)
     out, w, r = cx.velocity_consensus(d_az, d_y, seg, k=k, scale=scale, c=c, hyps=hyps, min_det=min_det, refine=refine,
                                       seed=seed, ridge=ridge, bounds=bounds, amask=d_m, n=n, want_weight=True,
                                       want_resid=True)
@@ -653,9 +636,7 @@ def associate(cur_xy, prev_xy, thr: float, ctx: Optional[Context] = None):
     scratch = c.empty((max((npv + 31) // 32, 1),), torch.int32)
     match = c.empty((nc,), torch.int32)
     dist = c.empty((nc,), torch.float64)
-    c._bind()
-    c.check(c.lib.rsl_associate(c.h, _ptr(dc), nc, _ptr(dp), npv, float(thr), _ptr(scratch), _ptr(match), _ptr(dist)),
-            'rsl_associate')
+    c.call('rsl_associate', dc, nc, dp, npv, thr, scratch, match, dist)
     return to_host(match).astype(np.int64), to_host(dist)
 
 
@@ -675,10 +656,8 @@ def _wrapped_call(c: Context, name, pos, ang, y, k, mode, w, vmax, wmax, prev, l
     dprev = c.to_dev(np.asarray(prev, np.float64).reshape(6)) if prev is not None else None
     dex = c.to_dev(ex.reshape(-1)) if nextra else None
     out = c.empty((8,), torch.float64)
-    c._bind()
-    c.check(getattr(c.lib, name)(c.h, _ptr(dp), _ptr(da), n, _ptr(dy), float(k), int(mode), float(w), float(vmax),
-                                 float(wmax), _ptr(dprev), lo6, hi6, int(nv), *own, _ptr(dex), nextra, int(iters),
-                                 _ptr(scratch), nbytes, _ptr(out)), name)
+    c.call(name, dp, da, n, dy, k, mode, w, vmax, wmax, dprev, lo6, hi6, nv, *own, dex, nextra, iters, scratch, nbytes,
+           out)
     o = to_host(out)
     return o[:6].copy(), float(o[6])
 
@@ -689,7 +668,7 @@ def wrapped_solve(pos, ang, y, k, *, mode: int, lo, hi, nv: int = 6, w: float = 
     """Global minimisation of the wrapped-phase cost (rsl_wrapped_solve): mode 0 = Improved regularisation,
     mode 1 = Advanced penalties.  Returns (x6, cost)."""
     c = _ctx(ctx)
-    return _wrapped_call(c, 'rsl_wrapped_solve', pos, ang, y, k, mode, w, vmax, wmax, prev, lo, hi, nv, (int(grid_n),),
+    return _wrapped_call(c, 'rsl_wrapped_solve', pos, ang, y, k, mode, w, vmax, wmax, prev, lo, hi, nv, (grid_n,),
                          extra, iters, lambda n, lo6, hi6, nextra: c.lib.rsl_wrapped_scratch_bytes(n, grid_n, nextra))
 
 
@@ -707,7 +686,6 @@ def wrapped_search(pos, ang, y, k, *, mode: int, lo, hi, nv: int = 6, w: float =
         p = np.asarray(prev, np.float64).reshape(6)
         base[2] = p[2] * 0.1 / 10.1
         base[3:] = p[3:] if nv == 6 else 0.0
-    b6 = (c_double * 6)(*[float(v) for v in base])
     # at least 64 points per axis (a smooth landscape when k is small, e.g. the pipeline's lambda = fc / c); the width
     # of a collapsed axis (adaptive bounds with lo == hi) does not count: that axis gets one point (search_grid), and
     # the other keeps its own spacing instead of a 32768-point line of starts
@@ -722,6 +700,6 @@ def wrapped_search(pos, ang, y, k, *, mode: int, lo, hi, nv: int = 6, w: float =
         return nbytes
 
     return _wrapped_call(c, 'rsl_wrapped_search', pos, ang, y, k, mode, w, vmax, wmax, prev, lo, hi, nv,
-                         (b6, spacing, int(nbest)), extra, iters, scratch_bytes)
+                         (base, spacing, nbest), extra, iters, scratch_bytes)
 
 

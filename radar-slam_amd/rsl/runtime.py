@@ -141,10 +141,23 @@ class Context:
     def empty(self, shape, dtype):
         return self.torch.empty(shape, dtype=dtype, device=self.device)
 
-    def _buf(self, bufs, name, shape, dtype):
-        """The caller's preallocated buffer ``bufs[name]`` where there is one, else a new tensor."""
+    def call(self, name: str, *args):
+        """Entry point `name` of librsl on torch's current stream: the arguments after the handle as its
+        _lib.SIGNATURES row takes them (tensors or None for device pointers, numbers, sequences for the small host
+        arrays).  A status other than RSL_OK raises as check does; a tensor that is not on this context's device raises
+        ValueError before the library is entered."""
+        conv = _lib.marshal(name, args)
+        for i in _lib.POINTER_SLOTS[name]:
+            if hasattr(args[i], 'data_ptr') and args[i].device != self.device:
+                raise ValueError(f'{name}: argument {i + 1} is a tensor on {args[i].device}, not on {self.device}')
+        self._bind()
+        self.check(getattr(self.lib, name)(self.h, *conv), name)  # args stay referenced until the call has returned
+
+    def _buf(self, bufs, name, shape, dtype, want=True):
+        """The caller's preallocated buffer ``bufs[name]`` where there is one (it is filled whether wanted or not),
+        else a new tensor, or None when it is not wanted."""
         t = bufs.get(name) if bufs else None
-        return t if t is not None else self.empty(shape, dtype)
+        return t if t is not None or not want else self.empty(shape, dtype)
 
     def empty_contiguous(self, shape, dtype):
         """A device tensor in its own physically contiguous allocation (hipExtMallocWithFlags with
@@ -172,8 +185,7 @@ class Context:
         return t.to(self.device, non_blocking=False)
 
     def sync(self):
-        self._bind()
-        self.check(self.lib.rsl_sync(self.h), 'rsl_sync')
+        self.call('rsl_sync')
 
     # -- timing ---------------------------------------------------------------------------------
     def timing(self, on: bool = True):
@@ -215,9 +227,7 @@ class Context:
             out = self.empty((F, A, S, C), torch.complex64)
         if work is None:
             work = self.empty((F, A, C, S), torch.complex64)
-        self._bind()
-        self.check(self.lib.rsl_rds(self.h, _ptr(cube), F, A, Ct, chirp0, C, S, _ptr(table), int(dc_removal),
-                                    _ptr(work), _ptr(out)), 'rsl_rds')
+        self.call('rsl_rds', cube, F, A, Ct, chirp0, C, S, table, dc_removal, work, out)
         return out
 
     # -- a7 + a8 fused -----------------------------------------------------------------------------
@@ -228,13 +238,9 @@ class Context:
         Returns the row grouping of ``peak_pow`` (pass it to ``emit``)."""
         F, A, Ct, S = cube.shape
         C = Ct - chirp0 if num_chirps is None else num_chirps
-        group = ctypes.c_int(1)
-        self._bind()
-        self.check(self.lib.rsl_rds_detect(self.h, _ptr(cube), F, A, Ct, chirp0, C, S, _ptr(table),
-                                           int(dc_removal), _ptr(work), _ptr(rds), float(thr_power), int(i_lo),
-                                           int(i_hi), _ptr(mask), _ptr(row_count), _ptr(db_map), _ptr(peak_pow),
-                                           ctypes.byref(group)),
-                   'rsl_rds_detect')
+        group = c_int(1)
+        self.call('rsl_rds_detect', cube, F, A, Ct, chirp0, C, S, table, dc_removal, work, rds, thr_power, i_lo, i_hi,
+                  mask, row_count, db_map, peak_pow, byref(group))
         return int(group.value)
 
     # -- a8 -------------------------------------------------------------------------------------
@@ -251,9 +257,7 @@ class Context:
     def detect(self, rds, thr_power: float, i_lo: int, i_hi: int, want_db: bool = False, out=None):
         F, A, S, C = rds.shape
         mask, rc, db, pk = self._detect_out(rds, want_db, out)
-        self._bind()
-        self.check(self.lib.rsl_detect(self.h, _ptr(rds), F, A, S, C, float(thr_power), int(i_lo), int(i_hi),
-                                       _ptr(mask), _ptr(rc), _ptr(db), _ptr(pk)), 'rsl_detect')
+        self.call('rsl_detect', rds, F, A, S, C, thr_power, i_lo, i_hi, mask, rc, db, pk)
         return mask, rc, db
 
     def detect_cfar(self, rds, guard, train, alpha: float, thr_power: float, i_lo: int, i_hi: int,
@@ -264,13 +268,12 @@ class Context:
         row-compact, group 1)."""
         F, A, S, C = rds.shape
         mask, rc, db, pk = self._detect_out(rds, want_db, out)
-        self._bind()
-        head = (self.h, _ptr(rds), F, A, S, C, int(guard[0]), int(guard[1]), int(train[0]), int(train[1]))
-        tail = (float(alpha), float(thr_power), int(i_lo), int(i_hi), _ptr(mask), _ptr(rc), _ptr(db), _ptr(pk))
+        head = (rds, F, A, S, C, guard[0], guard[1], train[0], train[1])
+        tail = (alpha, thr_power, i_lo, i_hi, mask, rc, db, pk)
         if method == 'os':
-            self.check(self.lib.rsl_detect_oscfar(*head, float(rank), *tail), 'rsl_detect_oscfar')
+            self.call('rsl_detect_oscfar', *head, rank, *tail)
         else:
-            self.check(self.lib.rsl_detect_cfar(*head, *tail), 'rsl_detect_cfar')
+            self.call('rsl_detect_cfar', *head, *tail)
         return mask, rc, db
 
     def detect_oscfar(self, rds, guard, train, rank: float, alpha: float, thr_power: float, i_lo: int, i_hi: int,
@@ -288,8 +291,7 @@ class Context:
         F, A, S, C = rds.shape
         if out is None:
             out = self.empty((F, S, C), torch.float32)
-        self._bind()
-        self.check(self.lib.rsl_power_integrate(self.h, _ptr(rds), F, A, S, C, _ptr(out)), 'rsl_power_integrate')
+        self.call('rsl_power_integrate', rds, F, A, S, C, out)
         return out
 
     def detect_power(self, power, rule, guard, train, rank: float, alpha: float, thr_power: float, i_lo: int,
@@ -307,11 +309,8 @@ class Context:
             rule = _lib.RULE_IDS[rule]
         F, S, C = power.shape
         mask, rc, db, pk = self._detect_out(power.unsqueeze(1), want_db, out)
-        self._bind()
-        self.check(self.lib.rsl_detect_power(self.h, _ptr(power), F, S, C, int(rule), int(guard[0]), int(guard[1]),
-                                             int(train[0]), int(train[1]), float(rank), float(alpha),
-                                             float(thr_power), int(i_lo), int(i_hi), _ptr(mask), _ptr(rc), _ptr(db),
-                                             _ptr(pk)), 'rsl_detect_power')
+        self.call('rsl_detect_power', power, F, S, C, rule, guard[0], guard[1], train[0], train[1], rank, alpha,
+                  thr_power, i_lo, i_hi, mask, rc, db, pk)
         return mask, rc, db
 
     def offsets(self, mask, row_count, C: int, bufs=None):
@@ -324,9 +323,7 @@ class Context:
         cb = self._buf(bufs, 'cell_base', (F + 1,), torch.int64)
         fc = self._buf(bufs, 'frame_counts', (2 * F,), torch.int64)
         um = self._buf(bufs, 'union_mask', (F, S, W), torch.int64)
-        self._bind()
-        self.check(self.lib.rsl_peak_offsets(self.h, _ptr(mask), _ptr(row_count), F, A, S, C, _ptr(eo), _ptr(co),
-                                             _ptr(sc), _ptr(eb), _ptr(cb), _ptr(fc), _ptr(um)), 'rsl_peak_offsets')
+        self.call('rsl_peak_offsets', mask, row_count, F, A, S, C, eo, co, sc, eb, cb, fc, um)
         return dict(entry_row_off=eo, cell_row_off=co, scratch=sc, entry_base=eb, cell_base=cb, frame_counts=fc,
                     union_mask=um)
 
@@ -351,14 +348,9 @@ class Context:
         e_pdb = get('e_pdb', entry_cap, torch.float32) if want_pdb else None
         c_f, c_rc, c_am = (get('c_frame', cell_cap, torch.int32), get('c_rc', cell_cap, torch.int32),
                            get('c_amask', cell_cap, torch.int32))
-        self._bind()
-        self.check(self.lib.rsl_peak_emit(self.h, _ptr(rds), _ptr(mask), _ptr(offs.get('union_mask')),
-                                          _ptr(peak_pow), int(peak_pow_group), F, A, S, C,
-                                          _ptr(offs['entry_row_off']),
-                                          _ptr(offs['cell_row_off']), _ptr(offs['entry_base']),
-                                          _ptr(offs['cell_base']), int(entry_cap), int(cell_cap), _ptr(e_co),
-                                          _ptr(e_c), _ptr(e_pdb), _ptr(c_f), _ptr(c_rc), _ptr(c_am)),
-                   'rsl_peak_emit')
+        self.call('rsl_peak_emit', rds, mask, offs.get('union_mask'), peak_pow, peak_pow_group, F, A, S, C,
+                  offs['entry_row_off'], offs['cell_row_off'], offs['entry_base'], offs['cell_base'], entry_cap,
+                  cell_cap, e_co, e_c, e_pdb, c_f, c_rc, c_am)
         return dict(e_coord=e_co, e_cell=e_c, e_pdb=e_pdb, c_frame=c_f, c_rc=c_rc, c_amask=c_am)
 
     # -- steering tables -------------------------------------------------------------------------
@@ -403,7 +395,6 @@ class Context:
             shape = ((max(cap, 1) + 31) // 32, G, 32) if spec_blocked else (G, max(cap, 1)) if spec_gmajor else \
                 (max(cap, 1), G)
             spec = self.empty(shape, torch.float32)
-        self._bind()
         m = int(method)
         if want_spec and spec_blocked:
             m |= _lib.DOA_SPEC_BLOCKED
@@ -411,20 +402,16 @@ class Context:
             m |= _lib.DOA_SPEC_GMAJOR
         if fast and steer['toeplitz'] and (not want_spec or (spec_blocked and not want_gmax)):
             m |= _lib.DOA_TOEPLITZ  # the f16-MFMA Toeplitz scan (argmax, or with the cell-blocked spectrum)
-        self.check(self.lib.rsl_doa(self.h, _ptr(rds), A, S, C, _ptr(c_frame), _ptr(c_rc), _ptr(n_dev), cap,
-                                    _ptr(steer['tab']), _ptr(steer['c128']), steer['G'], m, _ptr(idx), _ptr(gmax),
-                                    _ptr(spec)), 'rsl_doa')
+        self.call('rsl_doa', rds, A, S, C, c_frame, c_rc, n_dev, cap, steer['tab'], steer['c128'], steer['G'], m, idx,
+                  gmax, spec)
         return idx, gmax, spec
 
     def doa_extras(self, rds, c_frame, c_rc, steer, method: int, *, n: int, n_dev=None, esprit_scale: float,
                    out_idx, esprit=None, phase=None, gmax=None):
         """Fused Toeplitz DoA argmax + ESPRIT + spatial phase from one signature load (rsl_doa_extras)."""
         _, A, S, C = rds.shape
-        self._bind()
-        self.check(self.lib.rsl_doa_extras(self.h, _ptr(rds), A, S, C, _ptr(c_frame), _ptr(c_rc), _ptr(n_dev), int(n),
-                                           _ptr(steer['tab']), _ptr(steer['c128']), steer['G'], int(method),
-                                           float(esprit_scale), _ptr(out_idx), _ptr(gmax), _ptr(esprit),
-                                           _ptr(phase)), 'rsl_doa_extras')
+        self.call('rsl_doa_extras', rds, A, S, C, c_frame, c_rc, n_dev, n, steer['tab'], steer['c128'], steer['G'],
+                  method, esprit_scale, out_idx, gmax, esprit, phase)
         return out_idx, esprit, phase
 
     def steering_sub(self, steer_c128: np.ndarray, L: int):
@@ -451,18 +438,13 @@ class Context:
         cap = int(c_frame.shape[0]) if n is None else int(n)
         rows = max(cap, 1)
         nmax = int(nmax)
-
-        def get(name, shape, dt, want=True):  # a buffer the caller gave is filled whether wanted or not
-            return self._buf(out, name, shape, dt) if want else (out or {}).get(name)
-        nsrc = get('nsrc', (rows,), torch.int32)
-        idx = get('idx', (rows, max(nmax, 1)), torch.int32)
-        den = get('den', (rows, max(nmax, 1)), torch.float32, want_den)
-        eig = get('eig', (rows, L), torch.float32, want_eig)
-        spec = get('spec', (rows, G), torch.float32, want_spec)
-        self._bind()
-        self.check(self.lib.rsl_doa_smoothed(self.h, _ptr(rds), A, S, C, _ptr(c_frame), _ptr(c_rc), _ptr(n_dev), cap,
-                                             _ptr(steer_sub), G, L, nmax, int(num_sources), float(rel), _ptr(nsrc),
-                                             _ptr(idx), _ptr(den), _ptr(eig), _ptr(spec)), 'rsl_doa_smoothed')
+        nsrc = self._buf(out, 'nsrc', (rows,), torch.int32)
+        idx = self._buf(out, 'idx', (rows, max(nmax, 1)), torch.int32)
+        den = self._buf(out, 'den', (rows, max(nmax, 1)), torch.float32, want_den)
+        eig = self._buf(out, 'eig', (rows, L), torch.float32, want_eig)
+        spec = self._buf(out, 'spec', (rows, G), torch.float32, want_spec)
+        self.call('rsl_doa_smoothed', rds, A, S, C, c_frame, c_rc, n_dev, cap, steer_sub, G, L, nmax, num_sources, rel,
+                  nsrc, idx, den, eig, spec)
         return nsrc, idx, den, eig, spec
 
     # -- range-azimuth maps -----------------------------------------------------------------------
@@ -476,8 +458,7 @@ class Context:
         c0, c1 = (0, C) if doppler is None else (int(doppler[0]), int(doppler[1]))
         if out is None:
             out = self.empty((F, S, A, A), torch.complex64)
-        self._bind()
-        self.check(self.lib.rsl_range_cov(self.h, _ptr(rds), F, A, S, C, c0, c1, _ptr(out)), 'rsl_range_cov')
+        self.call('rsl_range_cov', rds, F, A, S, C, c0, c1, out)
         return out
 
     def steering_c64(self, steer_c128: np.ndarray):
@@ -511,10 +492,8 @@ class Context:
         for d in lead:
             n *= int(d)
         m = self._buf(out, 'map', lead + (G,), torch.float32)
-        arg = self._buf(out, 'arg', lead, torch.int32) if want_arg else (out or {}).get('arg')
-        self._bind()
-        self.check(self.lib.rsl_range_azimuth(self.h, _ptr(cov), n, A, _ptr(steer_c64), G, int(method),
-                                              float(loading), _ptr(m), _ptr(arg)), 'rsl_range_azimuth')
+        arg = self._buf(out, 'arg', lead, torch.int32, want_arg)
+        self.call('rsl_range_azimuth', cov, n, A, steer_c64, G, method, loading, m, arg)
         return m, arg
 
     def cell_extras(self, rds, c_frame, c_rc, *, n: int, n_dev=None, esprit_scale: float = 1 / math.pi,
@@ -526,10 +505,8 @@ class Context:
         esp = self._buf(bufs, 'esprit', (cap,), torch.float64) if want_esprit else None
         ph = self._buf(bufs, 'phase', (cap,), torch.float64) if want_phase else None
         az = self._buf(bufs, 'az', (cap,), torch.float64) if az_table is not None else None
-        self._bind()
-        self.check(self.lib.rsl_cell_extras(self.h, _ptr(rds), A, S, C, _ptr(c_frame), _ptr(c_rc), _ptr(n_dev),
-                                            int(n), float(esprit_scale), _ptr(gidx), _ptr(az_table), _ptr(sig),
-                                            _ptr(esp), _ptr(ph), _ptr(az)), 'rsl_cell_extras')
+        self.call('rsl_cell_extras', rds, A, S, C, c_frame, c_rc, n_dev, n, esprit_scale, gidx, az_table, sig, esp, ph,
+                  az)
         return sig, esp, ph, az
 
     def cell_refine(self, rds, c_frame, c_rc, gidx, az_table, steer_c64, *, n: Optional[int] = None, n_dev=None,
@@ -563,13 +540,10 @@ class Context:
         cap = int(c_frame.shape[0]) if n is None else int(n)
         rows = max(cap, 1)
         shape = (rows, len(POINT_COLUMNS))
-        pts = self._buf(out, 'points', shape, torch.float32) if want_points else (out or {}).get('points')
-        az = self._buf(out, 'az', (rows,), torch.float64) if want_az else (out or {}).get('az')
-        a4 = (c_double * 4)(*[float(x) for x in axes])
-        self._bind()
-        self.check(self.lib.rsl_cell_refine(self.h, _ptr(rds), _ptr(power), A, S, C, _ptr(c_frame), _ptr(c_rc),
-                                            _ptr(n_dev), cap, _ptr(gidx), _ptr(az_table), _ptr(steer_c64), G, rm, dm,
-                                            a4, _ptr(pts), _ptr(az)), 'rsl_cell_refine')
+        pts = self._buf(out, 'points', shape, torch.float32, want_points)
+        az = self._buf(out, 'az', (rows,), torch.float64, want_az)
+        self.call('rsl_cell_refine', rds, power, A, S, C, c_frame, c_rc, n_dev, cap, gidx, az_table, steer_c64, G, rm,
+                  dm, axes, pts, az)
         return pts, az
 
     def scan_register(self, points, seg, *, weight=None, rc=None, C: int = 0, axes=None, prev=None, init=None,
@@ -599,13 +573,8 @@ class Context:
             raise ValueError(f'scan_register: init must be contiguous float64 [{F}, 3]')
         rows = self._buf(out, 'rows', (max(F, 1), 8), torch.float64)
         om = self._buf(out, 'omega', (max(F, 1), 3), torch.float64) if want_omega else None
-        a4 = (c_double * 4)(*[float(x) for x in axes]) if axes is not None else None
-        self._bind()
-        self.check(self.lib.rsl_scan_register(
-            self.h, _ptr(points), _ptr(seg), F, N, _ptr(weight), _ptr(rc), int(C), a4, _ptr(pp),
-            _ptr(pv.get('weight')), _ptr(pv.get('rc')), M, _ptr(pv.get('n_dev')), _ptr(init), float(h),
-            float(h_coarse), float(dtheta), int(k), int(iters), float(shrink), float(tol), float(w_min), float(dt),
-            _ptr(rows), _ptr(om)), 'rsl_scan_register')
+        self.call('rsl_scan_register', points, seg, F, N, weight, rc, C, axes, pp, pv.get('weight'), pv.get('rc'), M,
+                  pv.get('n_dev'), init, h, h_coarse, dtheta, k, iters, shrink, tol, w_min, dt, rows, om)
         return rows, om
 
     def map_update(self, points, seg, poses, hits, *, grid, free=None, weight=None, r_min: float = 0.5,
@@ -630,11 +599,8 @@ class Context:
                 raise ValueError(f'map_update: {name} must be a contiguous int32 [ny, nx] plane')
         ny, nx = int(hits.shape[0]), int(hits.shape[1])
         stats = self._buf(out, 'stats', (max(F, 1), 4), torch.int32) if want_stats else None
-        g4 = (c_double * 4)(float(grid[0]), float(grid[1]), float(grid[2]), 0.0)
-        self._bind()
-        self.check(self.lib.rsl_map_update(self.h, _ptr(points), _ptr(seg), F, N, _ptr(weight), _ptr(poses), g4, nx, ny,
-                                           float(r_min), float(r_max), float(min_db), _ptr(hits), _ptr(free),
-                                           _ptr(stats)), 'rsl_map_update')
+        self.call('rsl_map_update', points, seg, F, N, weight, poses, (grid[0], grid[1], grid[2], 0.0), nx, ny, r_min,
+                  r_max, min_db, hits, free, stats)
         return stats
 
     def map_logodds(self, hits, free=None, *, l_occ: float = 0.85, l_free: float = 0.4, l_min: float = -4.0,
@@ -647,18 +613,14 @@ class Context:
                                   or t.shape != hits.shape):
                 raise ValueError(f'map_logodds: {name} must be a contiguous int32 plane')
         lo = out if out is not None else self.empty(tuple(hits.shape), torch.float32)
-        self._bind()
-        self.check(self.lib.rsl_map_logodds(self.h, _ptr(hits), _ptr(free), hits.numel(), float(l_occ), float(l_free),
-                                            float(l_min), float(l_max), _ptr(lo)), 'rsl_map_logodds')
+        self.call('rsl_map_logodds', hits, free, hits.numel(), l_occ, l_free, l_min, l_max, lo)
         return lo
 
     def confidence(self, rds, c_frame, c_rc, gidx, steer, n: int):
         torch = self.torch
         _, A, S, C = rds.shape
         conf = self.empty((max(n, 1),), torch.float64)
-        self._bind()
-        self.check(self.lib.rsl_confidence(self.h, _ptr(rds), A, S, C, _ptr(c_frame), _ptr(c_rc), int(n), _ptr(gidx),
-                                           _ptr(steer['c128']), _ptr(steer['phase']), _ptr(conf)), 'rsl_confidence')
+        self.call('rsl_confidence', rds, A, S, C, c_frame, c_rc, n, gidx, steer['c128'], steer['phase'], conf)
         return conf
 
     # -- configs[3] per-frame pattern ------------------------------------------------------------
@@ -670,10 +632,7 @@ class Context:
         n = max(ncube * int(kmax), 1)
         se, sf, sr = (self.empty((n,), torch.int32) for _ in range(3))
         sn = self.empty((max(ncube, 1),), torch.int32)
-        self._bind()
-        self.check(self.lib.rsl_peak_topk(self.h, _ptr(entry_base), int(entry_cap), ncube, _ptr(e_coord), _ptr(e_pdb),
-                                          float(thr_db), int(kmax), int(C), _ptr(se), _ptr(sf), _ptr(sr), _ptr(sn)),
-                   'rsl_peak_topk')
+        self.call('rsl_peak_topk', entry_base, entry_cap, ncube, e_coord, e_pdb, thr_db, kmax, C, se, sf, sr, sn)
         return se, sf, sr, sn
 
     def associate_nearest(self, range_m, az_rad, s0, off, *, thr: float = 5.0):
@@ -686,17 +645,14 @@ class Context:
         match = self.empty((max(N, 1),), torch.int32)
         dist = self.empty((max(N, 1),), torch.float64)
         phase = self.empty((max(N, 1),), torch.float64)
-        self._bind()
-        self.check(self.lib.rsl_associate_nearest(self.h, _ptr(range_m), _ptr(az_rad), _ptr(s0), _ptr(off), nframes, N,
-                                                  float(thr), _ptr(match), _ptr(dist), _ptr(phase)),
-                   'rsl_associate_nearest')
+        self.call('rsl_associate_nearest', range_m, az_rad, s0, off, nframes, N, thr, match, dist, phase)
         return match, dist, phase
 
     # -- a25-a29 ---------------------------------------------------------------------------------
-    def _vel_problem(self, y, seg, n, az_table, bounds, out, want_weight, want_resid):
+    def _vel_problem(self, y, seg, n, az_table, out, want_weight, want_resid):
         """What the three velocity solvers derive from their shared inputs: F, N (n, default len(y), clamped to it), G,
-        the box as c_double[4], the row buffer, and the optional weight (want_weight: True, or a device f32 [N] buffer
-        to fill) and resid buffers."""
+        the row buffer, and the optional weight (want_weight: True, or a device f32 [N] buffer to fill) and resid
+        buffers."""
         torch = self.torch
         F = int(seg.shape[0]) - 1
         o = out if out is not None else self.empty((max(F, 1), 8), torch.float64)
@@ -707,18 +663,14 @@ class Context:
         else:
             weight = None if want_weight is False or want_weight is None else want_weight
         resid = self.empty((max(N, 1),), torch.float64) if want_resid else None
-        b4 = (c_double * 4)(*[float(x) for x in bounds])
-        return F, N, G, b4, o, weight, resid
+        return F, N, G, o, weight, resid
 
     def velocity(self, az, y, seg, *, k: float, ridge: float = 0.0, bounds=(-50.0, 50.0, -50.0, 50.0),
                  amask=None, want_resid=False, out=None, gidx=None, az_table=None, n=None):
         """n: the per-target arrays' length (default len(y)); the segments in seg are clamped to it."""
-        F, N, G, b4, o, _, resid = self._vel_problem(y, seg, n, az_table, bounds, out, False, want_resid)
+        F, N, G, o, _, resid = self._vel_problem(y, seg, n, az_table, out, False, want_resid)
         pred = self.empty((max(N, 1),), self.torch.float64) if want_resid else None
-        self._bind()
-        self.check(self.lib.rsl_velocity(self.h, _ptr(az), _ptr(gidx), _ptr(az_table), G, _ptr(y), _ptr(amask),
-                                         _ptr(seg), N, F, float(k), float(ridge), b4, _ptr(o), _ptr(resid), _ptr(pred)),
-                   'rsl_velocity')
+        self.call('rsl_velocity', az, gidx, az_table, G, y, amask, seg, N, F, k, ridge, bounds, o, resid, pred)
         return o, resid, pred
 
     def velocity_robust(self, az, y, seg, *, k: float, loss, c: Optional[float] = None, scale: Optional[float] = None,
@@ -736,13 +688,9 @@ class Context:
         loss = int(loss)
         if c is None:
             c = _lib.LOSS_DEFAULT_C.get(loss, 1.0)  # an unknown id is rejected by the library
-        F, N, G, b4, o, weight, resid = self._vel_problem(y, seg, n, az_table, bounds, out, want_weight, want_resid)
-        self._bind()
-        self.check(self.lib.rsl_velocity_robust(self.h, _ptr(az), _ptr(gidx), _ptr(az_table), G, _ptr(y), _ptr(amask),
-                                                _ptr(seg), N, F, float(k), float(ridge), b4, loss, float(c),
-                                                0.0 if scale is None else float(scale), int(iters), float(tol),
-                                                _ptr(o), _ptr(weight), _ptr(resid)),
-                   'rsl_velocity_robust')
+        F, N, G, o, weight, resid = self._vel_problem(y, seg, n, az_table, out, want_weight, want_resid)
+        self.call('rsl_velocity_robust', az, gidx, az_table, G, y, amask, seg, N, F, k, ridge, bounds, loss, c,
+                  0.0 if scale is None else scale, iters, tol, o, weight, resid)
         return o, weight, resid
 
     def velocity_consensus(self, az, y, seg, *, k: float, scale: float, c: Optional[float] = None, hyps: int = 256,
@@ -765,13 +713,9 @@ class Context:
             raise ValueError(f'seed must lie in [0, 2^64), not {seed!r}')
         if not -2 ** 63 <= frame0 < 2 ** 63:
             raise ValueError(f'frame0 must fit 64 bits, not {frame0!r}')
-        F, N, G, b4, o, weight, resid = self._vel_problem(y, seg, n, az_table, bounds, out, want_weight, want_resid)
-        self._bind()
-        self.check(self.lib.rsl_velocity_consensus(self.h, _ptr(az), _ptr(gidx), _ptr(az_table), G, _ptr(y),
-                                                   _ptr(amask), _ptr(seg), N, F, float(k), float(ridge), b4, float(c),
-                                                   float(scale), int(hyps), float(min_det), int(refine), seed, frame0,
-                                                   _ptr(o), _ptr(weight), _ptr(resid)),
-                   'rsl_velocity_consensus')
+        F, N, G, o, weight, resid = self._vel_problem(y, seg, n, az_table, out, want_weight, want_resid)
+        self.call('rsl_velocity_consensus', az, gidx, az_table, G, y, amask, seg, N, F, k, ridge, bounds, c, scale,
+                  hyps, min_det, refine, seed, frame0, o, weight, resid)
         return o, weight, resid
 
 

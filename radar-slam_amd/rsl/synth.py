@@ -19,7 +19,6 @@ class SyntheticCubes:
                  chirp_duration: float = 40e-6, num_chirps: int = 64, num_antennas: int = 8,
                  antenna_spacing: Optional[float] = None, sampling_rate: float = 10e6, noise_power: float = 0.01):
         import torch
-        from .runtime import _ptr
         self.ctx = ctx
         self.A, self.C = int(num_antennas), int(num_chirps)
         self.S = int(chirp_duration * sampling_rate)  # simulate_raw.py:75
@@ -28,19 +27,15 @@ class SyntheticCubes:
                        for s in scatterers], dtype=np.float64).reshape(-1, 4)
         self.pattern = ctx.empty((self.A, self.S), torch.complex128)
         dsc = ctx.to_dev(sc) if len(sc) else None
-        ctx._bind()
-        ctx.check(ctx.lib.rsl_synth_pattern(ctx.h, _ptr(dsc), len(sc), self.A, self.S, float(fc), float(bandwidth),
-                                            float(chirp_duration), float(antenna_spacing or 0.0),
-                                            _ptr(self.pattern)), 'rsl_synth_pattern')
+        ctx.call('rsl_synth_pattern', dsc, len(sc), self.A, self.S, fc, bandwidth, chirp_duration,
+                 antenna_spacing or 0.0, self.pattern)
 
     def generate(self, frames: int, *, seed: int = 0, frame0: int = 0, out=None):
         """c64 [frames, A, C, S] on the device (asynchronous on the context's stream)."""
         import torch
-        from .runtime import _ptr
         c = self.ctx
         if out is None:
             out = c.empty((frames, self.A, self.C, self.S), torch.complex64)
-        c._bind()
-        c.check(c.lib.rsl_synth_cube(c.h, _ptr(self.pattern), int(frames), self.A, self.C, self.S, self.noise_power,
-                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(frame0), _ptr(out)), 'rsl_synth_cube')
+        c.call('rsl_synth_cube', self.pattern, frames, self.A, self.C, self.S, self.noise_power,
+               int(seed) & 0xFFFFFFFFFFFFFFFF, frame0, out)
         return out

@@ -158,13 +158,10 @@ class TrajectoryReducer:
     def step(self, vel, *, vstride: int, nv: int = 2, omega=None, ostride: int = 3):
         """vel: device f64 rows (v_x, v_y[, v_z], ...) of this rank's block.  Returns, on rank 0, all ranks' raw
         (unsmoothed) poses of this step [R*F, 7] = (x, y, z, qw, qx, qy, qz); None on the other ranks."""
-        from .runtime import _ptr
         import torch
         c = self.ctx
-        c._bind()
-        c.check(c.lib.rsl_traj_scan(c.h, _ptr(vel), int(vstride), int(nv), _ptr(omega), int(ostride), None,
-                                    self.dt, self.F, self.method, _ptr(self.pos), _ptr(self.quat),
-                                    _ptr(self.summary)), 'rsl_traj_scan')
+        c.call('rsl_traj_scan', vel, vstride, nv, omega, ostride, None, self.dt, self.F, self.method, self.pos,
+               self.quat, self.summary)
         if self.on:
             if self.gloo:
                 hs = torch.empty((self.world, SUMMARY), dtype=torch.float64)
@@ -174,10 +171,8 @@ class TrajectoryReducer:
                 self.dist.all_gather_into_tensor(self.summaries.view(-1), self.summary, group=self.group)
         else:
             self.summaries[0].copy_(self.summary)
-        c._bind()
-        c.check(c.lib.rsl_traj_stitch(c.h, _ptr(self.summaries), self.world, self.rank, self.dt, self.method,
-                                      _ptr(self.state), _ptr(self.base)), 'rsl_traj_stitch')
-        c.check(c.lib.rsl_traj_apply(c.h, _ptr(self.pos), _ptr(self.quat), self.F, _ptr(self.base)), 'rsl_traj_apply')
+        c.call('rsl_traj_stitch', self.summaries, self.world, self.rank, self.dt, self.method, self.state, self.base)
+        c.call('rsl_traj_apply', self.pos, self.quat, self.F, self.base)
         self.poses[:, 0:3].copy_(self.pos)
         self.poses[:, 3:7].copy_(self.quat)
         if self.on:
@@ -220,9 +215,7 @@ class TrajectoryReducer:
 
 def smooth(ctx, x, size: int = 5):
     """uniform_filter1d(x[:, c], size, mode='nearest') per column on the device (pose_integration.py:105-109)."""
-    from .runtime import _ptr
     F, ncol = x.shape
     out = ctx.empty((F, ncol), x.dtype)
-    ctx._bind()
-    ctx.check(ctx.lib.rsl_traj_smooth(ctx.h, _ptr(x), F, ncol, int(size), _ptr(out)), 'rsl_traj_smooth')
+    ctx.call('rsl_traj_smooth', x, F, ncol, size, out)
     return out

@@ -27,16 +27,13 @@ def _scan(vel, nv, omega, timestamps, method):
     """Device scan of one frame sequence -> (ctx, pos [N, 3], quat [N, 4]) device tensors, pose 0 = origin / identity."""
     import torch
     import rsl
-    from rsl.runtime import _ptr
     ctx = rsl.get_context()
     ts = np.ascontiguousarray(timestamps, dtype=np.float64)
     N = len(ts)
     dv = ctx.to_dev(np.ascontiguousarray(vel, dtype=np.float64).reshape(N, -1))
     dw = ctx.to_dev(np.ascontiguousarray(omega, dtype=np.float64).reshape(N, 3)) if omega is not None else None
     pos, quat = ctx.empty((N, 3), torch.float64), ctx.empty((N, 4), torch.float64)
-    ctx._bind()
-    ctx.check(ctx.lib.rsl_traj_scan(ctx.h, _ptr(dv), int(dv.shape[1]), int(nv), _ptr(dw), 3, _ptr(ctx.to_dev(ts)),
-                                    0.0, N, method, _ptr(pos), _ptr(quat), None), 'rsl_traj_scan')
+    ctx.call('rsl_traj_scan', dv, dv.shape[1], nv, dw, 3, ctx.to_dev(ts), 0.0, N, method, pos, quat, None)
     return ctx, pos, quat
 
 

@@ -34,6 +34,90 @@ def test_library_exports_header():
     assert lib.rsl_version() == 2
 
 
+def header_code():
+    """include/rsl.h without comments and preprocessor lines."""
+    src = open(os.path.join(ROOT, 'include', 'rsl.h')).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    src = re.sub(r'//[^\n]*', '', src)
+    return '\n'.join(ln for ln in src.splitlines() if not ln.lstrip().startswith('#'))
+
+
+_C_SCALARS = {'int': ctypes.c_int, 'long long': ctypes.c_longlong, 'unsigned long long': ctypes.c_ulonglong,
+              'double': ctypes.c_double, 'float': ctypes.c_float}
+
+
+def c_type(text):
+    """The ctypes type of a C type as include/rsl.h writes it."""
+    words = text.replace('*', ' * ').split()
+    const = words[0] == 'const'
+    words = words[1:] if const else words
+    stars = words.count('*')
+    base = ' '.join(w for w in words if w != '*')
+    assert stars <= 1, text
+    if not stars:
+        return ctypes.c_void_p if base == 'rsl_handle' else _C_SCALARS[base]
+    if base == 'void':
+        return ctypes.c_void_p
+    if base == 'char':
+        assert const, text
+        return ctypes.c_char_p
+    return ctypes.POINTER(ctypes.c_void_p if base == 'rsl_handle' else _C_SCALARS[base])
+
+
+def param_type(decl):
+    """c_type of a parameter declaration `<type> <name>`."""
+    return c_type(re.fullmatch(r'(.*?)\b[A-Za-z_]\w*\s*', decl, flags=re.S).group(1))
+
+
+def test_signature_table_matches_header_types():
+    """Every prototype of include/rsl.h against rsl._lib.SIGNATURES: the restype and every argument type, by identity,
+    and no table entry without a prototype.  Context.call converts its arguments by this table."""
+    from rsl import _lib
+    protos = re.findall(r'([A-Za-z_][\w\s\*]*?)\b(rsl_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', header_code())
+    assert len(protos) >= 57 and len({p[1] for p in protos}) == len(protos)
+    seen = set()
+    for ret, name, params in protos:
+        assert name in _lib.SIGNATURES, f'{name} declared in rsl.h but not in SIGNATURES'
+        res, args = _lib.SIGNATURES[name]
+        assert c_type(ret) is res, (name, ret, res)
+        want = [] if params.strip() == 'void' else [param_type(p) for p in params.split(',')]
+        assert len(want) == len(args), (name, len(want), len(args))
+        for i, (w, a, p) in enumerate(zip(want, args, params.split(','))):
+            assert w is a, f'{name}: argument {i} is `{p.strip()}` in rsl.h, {a.__name__} in SIGNATURES'
+        seen.add(name)
+    assert seen == set(_lib.SIGNATURES), sorted(set(_lib.SIGNATURES) - seen)
+
+
+# constants of include/rsl.h that the Python side does not mirror (a new constant goes here or into rsl/_lib.py)
+HEADER_ONLY = ('RSL_VERSION', r'RSL_K_\w+', r'RSL_CFAR_MAX_\w+', 'RSL_SS_MAX_SWEEPS', 'RSL_SS_OFF_TOL',
+               r'RSL_POINT_\w+')
+
+
+def test_constants_match_header():
+    """Every `#define RSL_<NAME> <number>` of include/rsl.h equals its mirror in rsl/_lib.py (<NAME> or RSL_<NAME>) or
+    is on HEADER_ONLY; K_NAMES are the RSL_K_* ids in order."""
+    from rsl import _lib
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'rsl.h')).read(), flags=re.S)
+    defs = dict(re.findall(r'^\s*#\s*define\s+(RSL_\w+)[ \t]+([-+]?(?:0x[0-9a-fA-F]+|[0-9.]+(?:e[-+]?\d+)?))f?[ \t]*$',
+                           src, flags=re.M))
+    assert len(defs) >= 53, sorted(defs)
+    mirrored = 0
+    for name, text in defs.items():
+        if any(re.fullmatch(pat, name) for pat in HEADER_ONLY):
+            continue
+        value = int(text, 0) if re.fullmatch(r'[-+]?(0x[0-9a-fA-F]+|\d+)', text) else float(text)
+        short = name[len('RSL_'):]
+        assert hasattr(_lib, short) or hasattr(_lib, name), f'{name} is neither mirrored in rsl/_lib.py nor HEADER_ONLY'
+        got = getattr(_lib, short) if hasattr(_lib, short) else getattr(_lib, name)
+        assert got == value and type(got) is type(value), (name, got, value)
+        mirrored += 1
+    assert mirrored >= 27
+    ids = {int(v, 0): k for k, v in defs.items() if k.startswith('RSL_K_') and k != 'RSL_K_COUNT'}
+    assert len(_lib.K_NAMES) == int(defs['RSL_K_COUNT']) == len(ids)
+    for i, n in enumerate(_lib.K_NAMES):
+        assert ids[i] == 'RSL_K_' + n.upper(), (i, n, ids[i])
+
+
 def test_library_reads_no_environment():
     """The product librsl.so selects no kernel variant from its caller's environment: it does not
     import getenv / secure_getenv at all.  The ablation switches exist only in the development build
