@@ -1,5 +1,10 @@
-// rsl_api.hip — C-ABI layer of librsl.so (see include/rsl.h).  No kernels here: argument checks,
-// per-size twiddle tables, launch + optional hipEvent timing on the handle's stream.
+// rsl_api.hip — C-ABI layer of librsl.so (see include/rsl.h).  No kernels here.  Every launching entry point is three
+// steps in one order: its argument checks on one `Check` (first refusal kept, the entry point's name put in front of the
+// text, a null handle the first refusal of all), with its empty-batch return where the header puts it among them; the
+// typed view of its untyped arguments (cell_list, cloud_view, detect_args, peak_offsets, peak_lists, steer_view); and
+// `enter`, the one frame a launch runs in: the handle's device made current and checked, the optional hipEvent timing
+// scope on the handle's stream, the launcher, its hipError_t mapped to the status.  Also here: the handle, the per-size
+// twiddle tables, and the host-side steering table.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -46,32 +51,62 @@ int hip_check(rsl_context* h, hipError_t e, const char* what) {
   return fail(h, RSL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-struct Scope {
+// The argument check of one entry point, built from (h, "rsl_x").  It keeps the first refusal, puts the entry point's
+// name in front of its text and holds the status; a null handle is refused before anything else (RSL_ERR_INVALID,
+// nothing stored).  Every test returns whether the call now stands refused, so the checks of an entry point chain with
+// || in the order in which they are to win, and none is evaluated after the first that fails:
+//   if (chk.invalid(F < 0, "bad shape") || chk.unsupported(C > 4096, "C too large")) return chk.status;
+struct Check {
   rsl_context* h;
-  int kid;
-  hipEvent_t a = nullptr, b = nullptr;
-  Scope(rsl_context* h_, int kid_) : h(h_), kid(kid_) {
-    hipSetDevice(h->device);
-    if (h->timing) {
-      if (!h->ev_pool.empty()) {
-        a = h->ev_pool.back().first;
-        b = h->ev_pool.back().second;
-        h->ev_pool.pop_back();
-      } else {
-        hipEventCreate(&a);
-        hipEventCreate(&b);
-      }
-      hipEventRecord(a, h->stream);
-    }
+  const char* fn;
+  int status;
+  Check(rsl_context* h_, const char* fn_) : h(h_), fn(fn_), status(h_ ? RSL_OK : RSL_ERR_INVALID) {}
+  bool refuse(int code, bool cond, const char* what) {
+    if (!status && cond) status = fail(h, code, std::string(fn) + ": " + what);
+    return status != RSL_OK;
   }
-  ~Scope() {
-    if (a) {
-      hipEventRecord(b, h->stream);
-      h->ev[kid].push_back({a, b});
-    }
-  }
+  bool invalid(bool cond, const char* what) { return refuse(RSL_ERR_INVALID, cond, what); }
+  bool unsupported(bool cond, const char* what) { return refuse(RSL_ERR_UNSUPPORTED, cond, what); }
 };
 
+int set_device(rsl_context* h) { return hip_check(h, hipSetDevice(h->device), "hipSetDevice"); }
+
+// The frame of a launch, after the checks and the empty-batch return of its entry point (so a refused or empty call
+// records no event), in this order: the handle's device is made current, and where that fails the call is RSL_ERR_HIP
+// and nothing launches; with timing on, an event pair opens on the handle's stream (one that cannot be created or
+// recorded is given up: the launch then runs untimed); steps() launches and returns the status; the pair closes and
+// goes to collect() under the kernel id.  The caller's current device is not put back.
+template <class Steps>
+int scoped(rsl_context* h, int kid, Steps&& steps) {
+  if (int r = set_device(h)) return r;
+  std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+  bool timed = false;
+  if (h->timing) {
+    if (!h->ev_pool.empty()) {
+      ev = h->ev_pool.back();
+      h->ev_pool.pop_back();
+    } else if (hipEventCreate(&ev.first) != hipSuccess || hipEventCreate(&ev.second) != hipSuccess) {
+      if (ev.first) hipEventDestroy(ev.first);
+      ev.first = nullptr;
+    }
+    timed = ev.first && hipEventRecord(ev.first, h->stream) == hipSuccess;
+    if (ev.first && !timed) h->ev_pool.push_back(ev);
+  }
+  const int r = steps();
+  if (timed) {
+    hipEventRecord(ev.second, h->stream);  // where this fails, collect() drops the launch from totals and spans
+    h->ev[kid].push_back(ev);
+  }
+  return r;
+}
+
+// The frame around one launcher call: `what` names it in the text of an RSL_ERR_HIP.
+template <class Launch>
+int enter(rsl_context* h, int kid, const char* what, Launch&& launch) {
+  return scoped(h, kid, [&] { return hip_check(h, launch(), what); });
+}
+
+// The table of size n on the current device (the caller has made the handle's device current), built at first use.
 float2* twiddles(rsl_context* h, int n) {
   auto it = h->tw.find(n);
   if (it != h->tw.end()) return it->second;
@@ -126,6 +161,25 @@ rsl::CloudView cloud_view(const void* points, const void* seg, long long n, int 
   return {(const float*)points, (const long long*)seg, n, F, (const float*)weight};
 }
 
+// What a detector entry point hands its launcher, from the untyped arguments of the C ABI.
+rsl::DetectArgs detect_args(double thr_power, int i_lo, int i_hi, void* mask, void* row_count, void* db_map,
+                            void* peak_pow) {
+  return {thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map, (float*)peak_pow};
+}
+
+// What rsl_peak_emit reads of rsl_peak_offsets' results, and the lists it writes, from its untyped arguments.
+rsl::PeakOffsets peak_offsets(const void* entry_row_off, const void* cell_row_off, const void* entry_base,
+                              const void* cell_base) {
+  return {(const int*)entry_row_off, (const int*)cell_row_off, (const long long*)entry_base,
+          (const long long*)cell_base};
+}
+
+rsl::PeakLists peak_lists(long long entry_cap, long long cell_cap, void* e_coord, void* e_cell, void* e_pdb,
+                          void* c_frame, void* c_rc, void* c_amask) {
+  return {entry_cap, cell_cap, (unsigned*)e_coord, (int*)e_cell, (float*)e_pdb, (int*)c_frame, (int*)c_rc,
+          (unsigned*)c_amask};
+}
+
 // The sections of a steering table that rsl_steer_table_build(G, M) wrote (rsl_doa_common.h SteerLayout).
 struct SteerView {
   rsl::SteerLayout lay;
@@ -138,6 +192,117 @@ SteerView steer_view(const void* tab, int G, int M) {
   const rsl::SteerLayout lay = rsl::steer_layout(G, M);
   const float* t = (const float*)tab;
   return {lay, t, t + lay.f32_floats, reinterpret_cast<const double*>(t + lay.t64_offset)};
+}
+
+// What rsl_rds and rsl_rds_detect share: the cube, its shape rule, and K1.
+struct RangeStage {
+  const void* cube;
+  int F, A, C_total, chirp0, C, S;
+  const void* table;
+  int dc_removal;
+  void* work;
+  bool bad_shape() const { return F < 0 || A <= 0 || S <= 0 || C <= 0 || chirp0 < 0 || chirp0 + C > C_total; }
+  // The twiddle tables of both stages on the handle's device (*tC: the one K2 takes), then K1 in its frame.  packed:
+  // range spectra of 6 B per value between K1 and K2 (each bin's exponent inside its 48-B unit; the tiles fill the
+  // first 3/4 of the c64-sized work buffer the caller provides).
+  int launch(rsl_context* h, bool packed, float2** tC) const {
+    if (int r = set_device(h)) return r;
+    float2* tS = twiddles(h, S);
+    *tC = twiddles(h, C);
+    if (!tS || !*tC) return fail(h, RSL_ERR_HIP, "twiddle table allocation failed");
+    return enter(h, RSL_K_RANGE_FFT, "range_fft", [&] {
+      return rsl::launch_range_fft(h->stream, (const float2*)cube, F, A, C_total, chirp0, C, S, (const float2*)table,
+                                   tS, dc_removal, (float2*)work, h->rfq, packed);
+    });
+  }
+};
+
+// rsl_detect_cfar (rank null) and rsl_detect_oscfar (its rank), and rsl_detect_power's two CFAR rules (power: `maps`
+// holds F fp32 power maps and A is 1): the checks in the order the header lists them, on the entry point's `chk`, then
+// the launch.  No LDS check: every window within the limits fits at every C <= RSL_CFAR_MAX_C, which rsl_cfar.hip and
+// rsl_oscfar.hip assert at compile time.
+int detect_cfar_family(Check& chk, const void* maps, bool power, int F, int A, int S, int C, rsl::CfarWindow win,
+                       const double* rank, double alpha, const rsl::DetectArgs& det) {
+  if (chk.invalid(F < 0 || A <= 0 || S <= 0 || C <= 0 || S > 8192, "bad shape") ||
+      chk.invalid(win.gr < 0 || win.gd < 0 || win.tr < 0 || win.td < 0 || win.tr + win.td < 1,
+                  "bad window (half-sizes >= 0, at least one training cell)") ||
+      chk.invalid(win.hr() > RSL_CFAR_MAX_HALF || win.hd() > RSL_CFAR_MAX_HALF,
+                  "window half-size above RSL_CFAR_MAX_HALF") ||
+      chk.invalid(win.nfull() > C || 2 * win.hr() + 1 > S, "window larger than the map") ||
+      chk.invalid(!(alpha > 0) || !std::isfinite(alpha), "alpha must be finite, > 0") ||
+      chk.unsupported(C > RSL_CFAR_MAX_C, "C above RSL_CFAR_MAX_C") ||
+      chk.invalid(rank && !(*rank > 0 && *rank <= 1), "rank must lie in (0, 1]"))
+    return chk.status;
+  if (F == 0) return RSL_OK;
+  if (chk.invalid(!maps || !det.mask || !det.row_count, "null pointer")) return chk.status;
+  rsl_context* h = chk.h;
+  const float2* z = (const float2*)maps;
+  const float* p = (const float*)maps;
+  const float af = (float)alpha;
+  if (rank)
+    return enter(h, RSL_K_DETECT, "detect_oscfar", [&] {
+      return power ? rsl::launch_detect_oscfar(h->stream, p, F, S, C, win, *rank, af, det)
+                   : rsl::launch_detect_oscfar(h->stream, z, F, A, S, C, win, *rank, af, det);
+    });
+  return enter(h, RSL_K_DETECT, "detect_cfar", [&] {
+    return power ? rsl::launch_detect_cfar(h->stream, p, F, S, C, win, af, det)
+                 : rsl::launch_detect_cfar(h->stream, z, F, A, S, C, win, af, det);
+  });
+}
+
+// The checks rsl_velocity, rsl_velocity_robust and rsl_velocity_consensus share, on the entry point's `chk`, in one
+// order: the counts; the entry point's own scalars (own(): its checks on chk, whether one refused); the ridge; an empty
+// batch (RSL_OK with p->F = 0: nothing to launch); the pointers; the grid table; the box.  Fills *p with the typed
+// problem.
+template <class Own>
+int velocity_problem(Check& chk, Own&& own, const void* az, const void* gidx, const void* az_table, int G,
+                     const void* y, const void* amask, const void* seg, long long n, int F, double k, double ridge,
+                     const double* bounds4, const void* out, rsl::VelProblem* p) {
+  *p = {};
+  if (chk.invalid(F < 0 || n < 0, "bad argument") || own() || chk.invalid(!(ridge >= 0), "ridge must be >= 0"))
+    return chk.status;
+  if (F == 0) return RSL_OK;
+  if (chk.invalid((!az && !gidx) || !y || !seg || !bounds4 || !out, "null pointer") ||
+      chk.invalid(gidx && (!az_table || G <= 0 || G > 2048), "bad grid table") ||
+      chk.invalid(!(bounds4[0] <= bounds4[1]) || !(bounds4[2] <= bounds4[3]), "bad bounds"))
+    return chk.status;
+  *p = {(const double*)az, (const int*)gidx, (const double*)az_table, G, (const double*)y, (const unsigned*)amask,
+        (const long long*)seg, n, F, k, ridge, bounds4[0], bounds4[1], bounds4[2], bounds4[3]};
+  return RSL_OK;
+}
+
+// The checks rsl_wrapped_solve and rsl_wrapped_search share, on the entry point's `chk`, in their order: the arguments
+// (own_bad: the entry point's own conditions), the pointers (own_null: one of the entry point's own is null), the box,
+// then the scratch size (need: the entry point's *_scratch_bytes).
+int wrapped_check(Check& chk, const rsl::WrapArgs& a, bool own_bad, bool own_null, const void* scratch,
+                  long long scratch_bytes, long long need, const void* out) {
+  auto bad_box = [&] {
+    for (int c = 0; c < 6; ++c)
+      if (!(a.lo[c] <= a.hi[c])) return true;
+    return false;
+  };
+  if (chk.invalid(a.n < 1 || (a.nv != 3 && a.nv != 6) || (a.mode != 0 && a.mode != 1) || own_bad || a.nextra < 0 ||
+                      a.iters < 0,
+                  "bad argument") ||
+      chk.invalid(!a.pos || !a.ang || !a.y || !a.lo || !a.hi || own_null || !scratch || !out ||
+                      (a.nextra > 0 && !a.extra),
+                  "null pointer") ||
+      chk.invalid(bad_box(), "bad bounds") || chk.invalid(scratch_bytes < need, "scratch too small"))
+    return chk.status;
+  return RSL_OK;
+}
+
+// stage-1 grid of rsl_wrapped_search: ceil(width / spacing) points per axis, at least 1, at most 2^15 (so the grid
+// has < 2^30 starts)
+void search_grid(const double* lo6, const double* hi6, double spacing, long long* gx, long long* gy) {
+  auto pts = [&](double w) {
+    double g = spacing > 0 ? ceil(w / spacing) : 1.0;
+    if (!(g >= 1.0)) g = 1.0;
+    if (g > 32768.0) g = 32768.0;
+    return (long long)g;
+  };
+  *gx = pts(hi6[0] - lo6[0]);
+  *gy = pts(hi6[1] - lo6[1]);
 }
 
 }  // namespace
@@ -198,7 +363,7 @@ int rsl_set_stream(rsl_handle h, void* s) {
 
 int rsl_sync(rsl_handle h) {
   if (!h) return RSL_ERR_INVALID;
-  hipSetDevice(h->device);
+  if (int r = set_device(h)) return r;
   return hip_check(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize");
 }
 
@@ -243,234 +408,170 @@ int rsl_timing_read(rsl_handle h, int kid, double* total_ms, long long* launches
 
 int rsl_rds(rsl_handle h, const void* cube, int F, int A, int C_total, int chirp0, int C, int S, const void* table,
             int dc_removal, void* work, void* rds) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || A <= 0 || S <= 0 || C <= 0 || chirp0 < 0 || chirp0 + C > C_total)
-    return fail(h, RSL_ERR_INVALID, "rsl_rds: bad shape");
+  Check chk(h, "rsl_rds");
+  const RangeStage k1{cube, F, A, C_total, chirp0, C, S, table, dc_removal, work};
+  if (chk.invalid(k1.bad_shape(), "bad shape")) return chk.status;
   if (F == 0) return RSL_OK;  // empty batch: the (zero-size) buffers may be null
-  if (!cube || !table || !work || !rds) return fail(h, RSL_ERR_INVALID, "rsl_rds: null pointer");
-  if (!rsl_fft_supported(S) || !rsl_fft_supported(C))
-    return fail(h, RSL_ERR_UNSUPPORTED, "rsl_rds: FFT size not supported (S=" + std::to_string(S) +
-                                            ", C=" + std::to_string(C) + ")");
-  hipSetDevice(h->device);
-  float2* tS = twiddles(h, S);
-  float2* tC = twiddles(h, C);
-  if (!tS || !tC) return fail(h, RSL_ERR_HIP, "twiddle table allocation failed");
-  bool sup = true;
-  hipError_t e;
-  {
-    Scope sc(h, RSL_K_RANGE_FFT);
-    e = rsl::launch_range_fft(h->stream, (const float2*)cube, F, A, C_total, chirp0, C, S, (const float2*)table, tS,
-                              dc_removal, (float2*)work, &sup, h->rfq);
+  if (chk.invalid(!cube || !table || !work || !rds, "null pointer")) return chk.status;
+  if (!rsl_fft_supported(S) || !rsl_fft_supported(C)) {  // the one text that carries values
+    const std::string sizes = "FFT size not supported (S=" + std::to_string(S) + ", C=" + std::to_string(C) + ")";
+    chk.unsupported(true, sizes.c_str());
+    return chk.status;
   }
-  if (int r = hip_check(h, e, "range_fft")) return r;
-  {
-    Scope sc(h, RSL_K_DOPPLER_FFT);
-    e = rsl::launch_doppler_fft(h->stream, (const float2*)work, F, A, C, S, tC, (float2*)rds, &sup);
-  }
-  return hip_check(h, e, "doppler_fft");
-}
-
-// What a detector entry point hands its launcher, from the untyped arguments of the C ABI.
-static rsl::DetectArgs detect_args(double thr_power, int i_lo, int i_hi, void* mask, void* row_count, void* db_map,
-                                   void* peak_pow) {
-  return {thr_power, i_lo, i_hi, (unsigned long long*)mask, (int*)row_count, (float*)db_map, (float*)peak_pow};
+  float2* tC;
+  if (int r = k1.launch(h, false, &tC)) return r;
+  return enter(h, RSL_K_DOPPLER_FFT, "doppler_fft", [&] {
+    return rsl::launch_doppler_fft(h->stream, (const float2*)work, F, A, C, S, tC, (float2*)rds);
+  });
 }
 
 int rsl_rds_detect(rsl_handle h, const void* cube, int F, int A, int C_total, int chirp0, int C, int S,
                    const void* table, int dc_removal, void* work, void* rds, double thr_power, int i_lo, int i_hi,
                    void* mask, void* row_count, void* db_map, void* peak_pow, int* peak_pow_group) {
-  if (!h) return RSL_ERR_INVALID;
+  Check chk(h, "rsl_rds_detect");
+  if (chk.status) return chk.status;  // a null handle: nothing is written
   if (peak_pow_group) *peak_pow_group = 1;
-  if (F < 0 || A <= 0 || S <= 0 || C <= 0 || chirp0 < 0 || chirp0 + C > C_total)
-    return fail(h, RSL_ERR_INVALID, "rsl_rds_detect: bad shape");
+  const RangeStage k1{cube, F, A, C_total, chirp0, C, S, table, dc_removal, work};
+  if (chk.invalid(k1.bad_shape(), "bad shape")) return chk.status;
   if (F == 0) return RSL_OK;  // empty batch: the (zero-size) buffers may be null
-  if (!mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_rds_detect: null pointer");
-  if (!rsl::doppler_detect_supported(C, S)) {  // unfused: a7 then a8
+  if (chk.invalid(!mask || !row_count, "null pointer")) return chk.status;
+  if (!rsl::doppler_detect_supported(C, S)) {  // unfused: a7 then a8, each under its own name
     if (int r = rsl_rds(h, cube, F, A, C_total, chirp0, C, S, table, dc_removal, work, rds)) return r;
     return rsl_detect(h, rds, F, A, S, C, thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow);
   }
-  if (!cube || !table || !work || !rds) return fail(h, RSL_ERR_INVALID, "rsl_rds_detect: null pointer");
-  if (!rsl_fft_supported(S)) return fail(h, RSL_ERR_UNSUPPORTED, "rsl_rds_detect: FFT size not supported");
-  hipSetDevice(h->device);
-  float2* tS = twiddles(h, S);
-  float2* tC = twiddles(h, C);
-  if (!tS || !tC) return fail(h, RSL_ERR_HIP, "twiddle table allocation failed");
-  bool sup = true;
-  int group = 1;
-  hipError_t e;
-  // packed range spectra between K1 and K2 (6 B per value, each bin's exponent inside its 48-B unit; the tiles fill
-  // the first 3/4 of the c64-sized work buffer the caller provides)
+  if (chk.invalid(!cube || !table || !work || !rds, "null pointer") ||
+      chk.unsupported(!rsl_fft_supported(S), "FFT size not supported"))
+    return chk.status;
   const bool packed = rsl::work_packed_supported(C, S);
-  {
-    Scope sc(h, RSL_K_RANGE_FFT);
-    e = rsl::launch_range_fft(h->stream, (const float2*)cube, F, A, C_total, chirp0, C, S, (const float2*)table, tS,
-                              dc_removal, (float2*)work, &sup, h->rfq, packed);
-  }
-  if (int r = hip_check(h, e, "range_fft")) return r;
-  {
-    Scope sc(h, RSL_K_DOPPLER_FFT);
-    const rsl::DetectArgs det = detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow);
-    e = rsl::launch_doppler_detect(h->stream, (const float2*)work, F, A, C, S, tC, (float2*)rds, det, &sup, &group,
-                                   packed);
-  }
+  float2* tC;
+  if (int r = k1.launch(h, packed, &tC)) return r;
+  int group = 1;
+  const int r = enter(h, RSL_K_DOPPLER_FFT, "doppler_detect", [&] {
+    return rsl::launch_doppler_detect(h->stream, (const float2*)work, F, A, C, S, tC, (float2*)rds,
+                                      detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow), &group,
+                                      packed);
+  });
   if (peak_pow_group) *peak_pow_group = group;
-  return hip_check(h, e, "doppler_detect");
+  return r;
 }
 
 int rsl_detect(rsl_handle h, const void* rds, int F, int A, int S, int C, double thr_power, int i_lo, int i_hi,
                void* mask, void* row_count, void* db_map, void* peak_pow) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || A <= 0 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_detect: bad shape");
+  Check chk(h, "rsl_detect");
+  if (chk.invalid(F < 0 || A <= 0 || S <= 0 || C <= 0, "bad shape")) return chk.status;
   if (F == 0) return RSL_OK;
-  if (!rds || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect: null pointer");
-  if (!rsl::detect_rows(C)) return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect: C too large");
-  Scope sc(h, RSL_K_DETECT);
-  const rsl::DetectArgs det = detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow);
-  return hip_check(h, rsl::launch_detect(h->stream, (const float2*)rds, F, A, S, C, det), "detect");
-}
-
-// rsl_detect_cfar (rank null) and rsl_detect_oscfar (its rank), and rsl_detect_power's two CFAR rules (power: `maps`
-// holds F fp32 power maps and A is 1): the checks in the order the header lists them, `fn` naming the entry point in the
-// error text, then the launch.  No LDS check: every window within the limits fits at every C <= RSL_CFAR_MAX_C, which
-// rsl_cfar.hip and rsl_oscfar.hip assert at compile time.
-static int detect_cfar_family(rsl_handle h, const std::string& fn, const void* maps, bool power, int F, int A, int S,
-                              int C, rsl::CfarWindow win, const double* rank, double alpha,
-                              const rsl::DetectArgs& det) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || A <= 0 || S <= 0 || C <= 0 || S > 8192) return fail(h, RSL_ERR_INVALID, fn + ": bad shape");
-  if (win.gr < 0 || win.gd < 0 || win.tr < 0 || win.td < 0 || win.tr + win.td < 1)
-    return fail(h, RSL_ERR_INVALID, fn + ": bad window (half-sizes >= 0, at least one training cell)");
-  if (win.hr() > RSL_CFAR_MAX_HALF || win.hd() > RSL_CFAR_MAX_HALF)
-    return fail(h, RSL_ERR_INVALID, fn + ": window half-size above RSL_CFAR_MAX_HALF");
-  if (win.nfull() > C || 2 * win.hr() + 1 > S) return fail(h, RSL_ERR_INVALID, fn + ": window larger than the map");
-  if (!(alpha > 0) || !std::isfinite(alpha)) return fail(h, RSL_ERR_INVALID, fn + ": alpha must be finite, > 0");
-  if (C > RSL_CFAR_MAX_C) return fail(h, RSL_ERR_UNSUPPORTED, fn + ": C above RSL_CFAR_MAX_C");
-  if (rank && !(*rank > 0 && *rank <= 1)) return fail(h, RSL_ERR_INVALID, fn + ": rank must lie in (0, 1]");
-  if (F == 0) return RSL_OK;
-  if (!maps || !det.mask || !det.row_count) return fail(h, RSL_ERR_INVALID, fn + ": null pointer");
-  Scope sc(h, RSL_K_DETECT);
-  const float2* z = (const float2*)maps;
-  const float* p = (const float*)maps;
-  const float af = (float)alpha;
-  if (rank)
-    return hip_check(h,
-                     power ? rsl::launch_detect_oscfar(h->stream, p, F, S, C, win, *rank, af, det)
-                           : rsl::launch_detect_oscfar(h->stream, z, F, A, S, C, win, *rank, af, det),
-                     "detect_oscfar");
-  return hip_check(h,
-                   power ? rsl::launch_detect_cfar(h->stream, p, F, S, C, win, af, det)
-                         : rsl::launch_detect_cfar(h->stream, z, F, A, S, C, win, af, det),
-                   "detect_cfar");
+  if (chk.invalid(!rds || !mask || !row_count, "null pointer") ||
+      chk.unsupported(!rsl::detect_rows(C), "C too large"))
+    return chk.status;
+  return enter(h, RSL_K_DETECT, "detect", [&] {
+    return rsl::launch_detect(h->stream, (const float2*)rds, F, A, S, C,
+                              detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow));
+  });
 }
 
 int rsl_detect_cfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d, int train_r,
                     int train_d, double alpha, double thr_power, int i_lo, int i_hi, void* mask, void* row_count,
                     void* db_map, void* peak_pow) {
-  return detect_cfar_family(h, "rsl_detect_cfar", rds, false, F, A, S, C, {guard_r, guard_d, train_r, train_d},
-                            nullptr, alpha, detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow));
+  Check chk(h, "rsl_detect_cfar");
+  return detect_cfar_family(chk, rds, false, F, A, S, C, {guard_r, guard_d, train_r, train_d}, nullptr, alpha,
+                            detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow));
 }
 
 int rsl_detect_oscfar(rsl_handle h, const void* rds, int F, int A, int S, int C, int guard_r, int guard_d,
                       int train_r, int train_d, double rank, double alpha, double thr_power, int i_lo, int i_hi,
                       void* mask, void* row_count, void* db_map, void* peak_pow) {
+  Check chk(h, "rsl_detect_oscfar");
   // the factor is checked as the float the kernel multiplies by
-  return detect_cfar_family(h, "rsl_detect_oscfar", rds, false, F, A, S, C, {guard_r, guard_d, train_r, train_d},
-                            &rank, (float)alpha,
+  return detect_cfar_family(chk, rds, false, F, A, S, C, {guard_r, guard_d, train_r, train_d}, &rank, (float)alpha,
                             detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow));
 }
 
 int rsl_power_integrate(rsl_handle h, const void* rds, int F, int A, int S, int C, void* power) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || A <= 0 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_power_integrate: bad shape");
-  if (A > 32) return fail(h, RSL_ERR_INVALID, "rsl_power_integrate: more than 32 antennas");
+  Check chk(h, "rsl_power_integrate");
+  if (chk.invalid(F < 0 || A <= 0 || S <= 0 || C <= 0, "bad shape") ||
+      chk.invalid(A > 32, "more than 32 antennas"))
+    return chk.status;
   if (F == 0) return RSL_OK;
-  if (!rds || !power) return fail(h, RSL_ERR_INVALID, "rsl_power_integrate: null pointer");
-  Scope sc(h, RSL_K_DETECT);
-  return hip_check(h, rsl::launch_power_integrate(h->stream, (const float2*)rds, F, A, S, C, (float*)power),
-                   "power_integrate");
+  if (chk.invalid(!rds || !power, "null pointer")) return chk.status;
+  return enter(h, RSL_K_DETECT, "power_integrate", [&] {
+    return rsl::launch_power_integrate(h->stream, (const float2*)rds, F, A, S, C, (float*)power);
+  });
 }
 
 int rsl_detect_power(rsl_handle h, const void* power, int F, int S, int C, int rule, int guard_r, int guard_d,
                      int train_r, int train_d, double rank, double alpha, double thr_power, int i_lo, int i_hi,
                      void* mask, void* row_count, void* db_map, void* peak_pow) {
-  if (!h) return RSL_ERR_INVALID;
+  Check chk(h, "rsl_detect_power");
   const rsl::DetectArgs det = detect_args(thr_power, i_lo, i_hi, mask, row_count, db_map, peak_pow);
   const rsl::CfarWindow win = {guard_r, guard_d, train_r, train_d};
   switch (rule) {
-    case RSL_RULE_THRESHOLD: {  // rsl_detect's checks; window, rank and alpha are not looked at
-      if (F < 0 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_detect_power: bad shape");
+    case RSL_RULE_THRESHOLD:  // rsl_detect's checks; window, rank and alpha are not looked at
+      if (chk.invalid(F < 0 || S <= 0 || C <= 0, "bad shape")) return chk.status;
       if (F == 0) return RSL_OK;
-      if (!power || !mask || !row_count) return fail(h, RSL_ERR_INVALID, "rsl_detect_power: null pointer");
-      if (!rsl::detect_rows(C)) return fail(h, RSL_ERR_UNSUPPORTED, "rsl_detect_power: C too large");
-      Scope sc(h, RSL_K_DETECT);
-      return hip_check(h, rsl::launch_detect(h->stream, (const float*)power, F, S, C, det), "detect");
-    }
+      if (chk.invalid(!power || !mask || !row_count, "null pointer") ||
+          chk.unsupported(!rsl::detect_rows(C), "C too large"))
+        return chk.status;
+      return enter(h, RSL_K_DETECT, "detect",
+                   [&] { return rsl::launch_detect(h->stream, (const float*)power, F, S, C, det); });
     case RSL_RULE_CA:
-      return detect_cfar_family(h, "rsl_detect_power", power, true, F, 1, S, C, win, nullptr, alpha, det);
+      return detect_cfar_family(chk, power, true, F, 1, S, C, win, nullptr, alpha, det);
     case RSL_RULE_OS:
-      return detect_cfar_family(h, "rsl_detect_power", power, true, F, 1, S, C, win, &rank, (float)alpha, det);
+      return detect_cfar_family(chk, power, true, F, 1, S, C, win, &rank, (float)alpha, det);
     default:
-      return fail(h, RSL_ERR_INVALID, "rsl_detect_power: unknown rule");
+      chk.invalid(true, "unknown rule");
+      return chk.status;
   }
 }
 
 int rsl_peak_offsets(rsl_handle h, const void* mask, const void* row_count, int F, int A, int S, int C,
                      void* entry_row_off, void* cell_row_off, void* scratch, void* entry_base, void* cell_base,
                      void* frame_counts, void* union_mask) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || A <= 0 || S <= 0 || C <= 0 || A > 32) return fail(h, RSL_ERR_INVALID, "rsl_peak_offsets: bad shape");
-  if (!entry_base || !cell_base) return fail(h, RSL_ERR_INVALID, "rsl_peak_offsets: null pointer");
-  if (F > 0 && (!mask || !row_count || !entry_row_off || !cell_row_off || !scratch || !frame_counts))
-    return fail(h, RSL_ERR_INVALID, "rsl_peak_offsets: null pointer");
+  Check chk(h, "rsl_peak_offsets");
+  if (chk.invalid(F < 0 || A <= 0 || S <= 0 || C <= 0 || A > 32, "bad shape") ||
+      chk.invalid(!entry_base || !cell_base, "null pointer") ||
+      chk.invalid(F > 0 && (!mask || !row_count || !entry_row_off || !cell_row_off || !scratch || !frame_counts),
+                  "null pointer"))
+    return chk.status;
   if (F == 0) {
-    hipSetDevice(h->device);
+    if (int r = set_device(h)) return r;
     long long z = 0;
     hipMemcpyAsync(entry_base, &z, 8, hipMemcpyHostToDevice, h->stream);
     hipMemcpyAsync(cell_base, &z, 8, hipMemcpyHostToDevice, h->stream);
     return hip_check(h, hipStreamSynchronize(h->stream), "offsets(F=0)");
   }
-  Scope sc(h, RSL_K_OFFSETS);
-  return hip_check(h,
-                   rsl::launch_offsets(h->stream, (const unsigned long long*)mask, (const int*)row_count, F, A, S, C,
-                                       (int*)entry_row_off, (int*)cell_row_off, (int*)scratch,
-                                       (long long*)entry_base, (long long*)cell_base, (long long*)frame_counts,
-                                       (unsigned long long*)union_mask),
-                   "offsets");
+  return enter(h, RSL_K_OFFSETS, "offsets", [&] {
+    return rsl::launch_offsets(h->stream, (const unsigned long long*)mask, (const int*)row_count, F, A, S, C,
+                               (int*)entry_row_off, (int*)cell_row_off, (int*)scratch, (long long*)entry_base,
+                               (long long*)cell_base, (long long*)frame_counts, (unsigned long long*)union_mask);
+  });
 }
 
 int rsl_peak_emit(rsl_handle h, const void* rds, const void* mask, const void* union_mask, const void* peak_pow,
                   int peak_pow_group, int F, int A, int S, int C, const void* entry_row_off, const void* cell_row_off, const void* entry_base,
                   const void* cell_base, long long entry_cap, long long cell_cap, void* e_coord, void* e_cell,
                   void* e_pdb, void* c_frame, void* c_rc, void* c_amask) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || A <= 0 || A > 32 || S <= 0 || C <= 0 || S > 8192 || C > 8192)
-    return fail(h, RSL_ERR_INVALID, "rsl_peak_emit: bad shape");
+  Check chk(h, "rsl_peak_emit");
+  if (chk.invalid(F < 0 || A <= 0 || A > 32 || S <= 0 || C <= 0 || S > 8192 || C > 8192, "bad shape"))
+    return chk.status;
   if (F == 0) return RSL_OK;
-  if (!mask || !entry_row_off || !cell_row_off || !entry_base || !cell_base)
-    return fail(h, RSL_ERR_INVALID, "rsl_peak_emit: null pointer");
-  if ((entry_cap > 0 && (!e_coord || !e_cell)) || (cell_cap > 0 && (!c_frame || !c_rc || !c_amask)))
-    return fail(h, RSL_ERR_INVALID, "rsl_peak_emit: null output");
-  if (peak_pow && (peak_pow_group < 1 || S % peak_pow_group != 0))
-    return fail(h, RSL_ERR_INVALID, "rsl_peak_emit: peak_pow_group must divide S");
-  Scope sc(h, RSL_K_EMIT);
-  if (rsl::emit_compact_supported(C, union_mask, peak_pow, e_pdb))
-    return hip_check(h,
-                     rsl::launch_emit_compact(h->stream, (const unsigned long long*)mask,
-                                              (const unsigned long long*)union_mask, (const float*)peak_pow,
-                                              peak_pow_group, F, A, S, C, (const int*)entry_row_off,
-                                              (const int*)cell_row_off, (const long long*)entry_base,
-                                              (const long long*)cell_base, entry_cap, cell_cap, (unsigned*)e_coord,
-                                              (int*)e_cell, (float*)e_pdb, (int*)c_frame, (int*)c_rc,
-                                              (unsigned*)c_amask),
-                     "emit2");
-  if (!rds) return fail(h, RSL_ERR_INVALID, "rsl_peak_emit: rds needed without union_mask / peak_pow");
-  return hip_check(h,
-                   rsl::launch_emit_rows(h->stream, (const float2*)rds, (const unsigned long long*)mask, F, A, S, C,
-                                         (const int*)entry_row_off, (const int*)cell_row_off,
-                                         (const long long*)entry_base, (const long long*)cell_base, entry_cap,
-                                         cell_cap, (unsigned*)e_coord, (int*)e_cell, (float*)e_pdb, (int*)c_frame,
-                                         (int*)c_rc, (unsigned*)c_amask),
-                   "emit");
+  const bool compact = rsl::emit_compact_supported(C, union_mask, peak_pow, e_pdb);
+  if (chk.invalid(!mask || !entry_row_off || !cell_row_off || !entry_base || !cell_base, "null pointer") ||
+      chk.invalid((entry_cap > 0 && (!e_coord || !e_cell)) || (cell_cap > 0 && (!c_frame || !c_rc || !c_amask)),
+                  "null output") ||
+      chk.invalid(peak_pow && (peak_pow_group < 1 || S % peak_pow_group != 0), "peak_pow_group must divide S") ||
+      chk.invalid(!compact && !rds, "rds needed without union_mask / peak_pow"))
+    return chk.status;
+  const rsl::PeakOffsets off = peak_offsets(entry_row_off, cell_row_off, entry_base, cell_base);
+  const rsl::PeakLists out = peak_lists(entry_cap, cell_cap, e_coord, e_cell, e_pdb, c_frame, c_rc, c_amask);
+  if (compact)
+    return enter(h, RSL_K_EMIT, "emit2", [&] {
+      return rsl::launch_emit_compact(h->stream, (const unsigned long long*)mask,
+                                      (const unsigned long long*)union_mask, (const float*)peak_pow, peak_pow_group,
+                                      F, A, S, C, off, out);
+    });
+  return enter(h, RSL_K_EMIT, "emit", [&] {
+    return rsl::launch_emit_rows(h->stream, (const float2*)rds, (const unsigned long long*)mask, F, A, S, C, off, out);
+  });
 }
 
 long long rsl_steer_table_floats(int G, int M) {
@@ -514,249 +615,219 @@ int rsl_steer_table_build(const double* steer, int G, int M, float* out, int* nt
 int rsl_doa(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
             const void* ncell_dev, long long ncell, const void* steer_tab, const void* steer_c128, int G, int method,
             void* out_idx, void* out_gmax, void* out_spec) {
-  if (!h) return RSL_ERR_INVALID;
-  if (A <= 0 || A > 16 || S <= 0 || C <= 0 || G <= 0) return fail(h, RSL_ERR_INVALID, "rsl_doa: bad shape");
-  if (!rds || !c_frame || !c_rc || !steer_tab || !out_idx) return fail(h, RSL_ERR_INVALID, "rsl_doa: null pointer");
+  Check chk(h, "rsl_doa");
   const int base_method = method & 0xff;
+  if (chk.invalid(A <= 0 || A > 16 || S <= 0 || C <= 0 || G <= 0, "bad shape") ||
+      chk.invalid(!rds || !c_frame || !c_rc || !steer_tab || !out_idx, "null pointer") ||
+      chk.invalid(base_method != RSL_METHOD_MUSIC && base_method != RSL_METHOD_BEAMFORMING, "unknown method"))
+    return chk.status;
   const bool toep = (method & RSL_DOA_TOEPLITZ) != 0;
-  if (base_method != RSL_METHOD_MUSIC && base_method != RSL_METHOD_BEAMFORMING)
-    return fail(h, RSL_ERR_INVALID, "rsl_doa: unknown method");
   const bool music = base_method == RSL_METHOD_MUSIC;
   (void)steer_c128;  // the exact re-scan reads the fp64 copy inside steer_tab (rsl_steer_table_build)
   const SteerView tab = steer_view(steer_tab, G, A);
   const rsl::CellList cl = cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell);
   if (!ncell_dev && ncell <= 0) return RSL_OK;
-  Scope sc(h, RSL_K_DOA_SCAN);
-  // the Toeplitz f16-MFMA scan: argmax only, or with the whole spectrum in the cell-blocked layout (no gmax there)
-  const bool toep_spec = out_spec && (method & RSL_DOA_SPEC_BLOCKED) && !out_gmax;
-  if (toep && (!out_spec || toep_spec) && tab.lay.toep_fits)
-    return hip_check(h,
-                     rsl::launch_doa_toep(h->stream, cl, tab.toep, G, music, tab.t64, (int*)out_idx, (float*)out_gmax,
-                                          0.0, nullptr, nullptr, toep_spec ? (float*)out_spec : nullptr),
-                     "doa_toep");
-  const long long spec_ld = (method & RSL_DOA_SPEC_BLOCKED) ? -1 : (method & RSL_DOA_SPEC_GMAJOR) ? ncell : 0;
-  if (int r = hip_check(h,
-                        rsl::launch_doa_scan(h->stream, cl, tab.f32, G, music, (int*)out_idx, (float*)out_gmax,
-                                             (float*)out_spec, spec_ld),
-                        "doa_scan"))
-    return r;
-  // the cells the f32 scan marked ambiguous: exact fp64 argmax (rsl_doa_toep.hip k_doa_fixup)
-  return hip_check(h, rsl::launch_doa_fixup(h->stream, cl, G, music, tab.t64, (int*)out_idx, (float*)out_gmax),
-                   "doa_fixup");
+  // one scope for the scan and its fixup, ending at the first step that fails
+  return scoped(h, RSL_K_DOA_SCAN, [&] {
+    // the Toeplitz f16-MFMA scan: argmax only, or with the whole spectrum in the cell-blocked layout (no gmax there)
+    const bool toep_spec = out_spec && (method & RSL_DOA_SPEC_BLOCKED) && !out_gmax;
+    if (toep && (!out_spec || toep_spec) && tab.lay.toep_fits)
+      return hip_check(h,
+                       rsl::launch_doa_toep(h->stream, cl, tab.toep, G, music, tab.t64, (int*)out_idx,
+                                            (float*)out_gmax, 0.0, nullptr, nullptr,
+                                            toep_spec ? (float*)out_spec : nullptr),
+                       "doa_toep");
+    const long long spec_ld = (method & RSL_DOA_SPEC_BLOCKED) ? -1 : (method & RSL_DOA_SPEC_GMAJOR) ? ncell : 0;
+    if (int r = hip_check(h,
+                          rsl::launch_doa_scan(h->stream, cl, tab.f32, G, music, (int*)out_idx, (float*)out_gmax,
+                                               (float*)out_spec, spec_ld),
+                          "doa_scan"))
+      return r;
+    // the cells the f32 scan marked ambiguous: exact fp64 argmax (rsl_doa_toep.hip k_doa_fixup)
+    return hip_check(h, rsl::launch_doa_fixup(h->stream, cl, G, music, tab.t64, (int*)out_idx, (float*)out_gmax),
+                     "doa_fixup");
+  });
 }
 
 int rsl_doa_extras(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
                    const void* ncell_dev, long long ncell, const void* steer_tab, const void* steer_c128, int G,
                    int method, double esprit_scale, void* out_idx, void* out_gmax, void* esprit_deg, void* phase) {
-  if (!h) return RSL_ERR_INVALID;
-  if (A < 2 || A > 16 || S <= 0 || C <= 0 || G <= 0) return fail(h, RSL_ERR_INVALID, "rsl_doa_extras: bad shape");
-  if (!rds || !c_frame || !c_rc || !steer_tab || !out_idx)
-    return fail(h, RSL_ERR_INVALID, "rsl_doa_extras: null pointer");
-  if (method != RSL_METHOD_MUSIC && method != RSL_METHOD_BEAMFORMING)
-    return fail(h, RSL_ERR_INVALID, "rsl_doa_extras: unknown method");
+  Check chk(h, "rsl_doa_extras");
+  if (chk.invalid(A < 2 || A > 16 || S <= 0 || C <= 0 || G <= 0, "bad shape") ||
+      chk.invalid(!rds || !c_frame || !c_rc || !steer_tab || !out_idx, "null pointer") ||
+      chk.invalid(method != RSL_METHOD_MUSIC && method != RSL_METHOD_BEAMFORMING, "unknown method"))
+    return chk.status;
   const bool music = method == RSL_METHOD_MUSIC;
   (void)steer_c128;  // the exact re-scan reads the fp64 copy inside steer_tab (rsl_steer_table_build)
   const SteerView tab = steer_view(steer_tab, G, A);
-  if (!tab.lay.toep_fits)
-    return fail(h, RSL_ERR_UNSUPPORTED, "rsl_doa_extras: grid too large for the Toeplitz path (use rsl_doa)");
+  if (chk.unsupported(!tab.lay.toep_fits, "grid too large for the Toeplitz path (use rsl_doa)")) return chk.status;
   if (!ncell_dev && ncell <= 0) return RSL_OK;
-  Scope sc(h, RSL_K_DOA_SCAN);
-  return hip_check(h,
-                   rsl::launch_doa_toep(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell), tab.toep,
-                                        G, music, tab.t64, (int*)out_idx, (float*)out_gmax, esprit_scale,
-                                        (double*)esprit_deg, (double*)phase),
-                   "doa_extras");
+  return enter(h, RSL_K_DOA_SCAN, "doa_extras", [&] {
+    return rsl::launch_doa_toep(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell), tab.toep, G,
+                                music, tab.t64, (int*)out_idx, (float*)out_gmax, esprit_scale, (double*)esprit_deg,
+                                (double*)phase);
+  });
 }
 
 int rsl_doa_smoothed(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
                      const void* ncell_dev, long long ncell, const void* steer_sub_c64, int G, int L, int nmax,
                      int num_sources, double rel, void* out_nsrc, void* out_idx, void* out_den, void* out_eig,
                      void* out_spec) {
-  if (!h) return RSL_ERR_INVALID;
-  if (A < 3 || A > 16 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: bad shape (3 <= A <= 16)");
-  if (L < 2 || L > A || L > RSL_SS_MAX_L)
-    return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: sub-array length outside [2, min(A, RSL_SS_MAX_L)]");
-  if (nmax < 1 || nmax > L - 1) return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: nmax outside [1, L - 1]");
-  if (num_sources < 0 || num_sources > nmax)
-    return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: num_sources outside [0, nmax]");
-  if (!(rel > 0.0 && rel < 1.0)) return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: rel outside (0, 1)");
-  if (G < 3) return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: G < 3");
-  if (!rds || !c_frame || !c_rc || !steer_sub_c64 || !out_nsrc || !out_idx)
-    return fail(h, RSL_ERR_INVALID, "rsl_doa_smoothed: null pointer");
+  Check chk(h, "rsl_doa_smoothed");
+  if (chk.invalid(A < 3 || A > 16 || S <= 0 || C <= 0, "bad shape (3 <= A <= 16)") ||
+      chk.invalid(L < 2 || L > A || L > RSL_SS_MAX_L, "sub-array length outside [2, min(A, RSL_SS_MAX_L)]") ||
+      chk.invalid(nmax < 1 || nmax > L - 1, "nmax outside [1, L - 1]") ||
+      chk.invalid(num_sources < 0 || num_sources > nmax, "num_sources outside [0, nmax]") ||
+      chk.invalid(!(rel > 0.0 && rel < 1.0), "rel outside (0, 1)") || chk.invalid(G < 3, "G < 3") ||
+      chk.invalid(!rds || !c_frame || !c_rc || !steer_sub_c64 || !out_nsrc || !out_idx, "null pointer"))
+    return chk.status;
   if (ncell <= 0) return RSL_OK;  // ncell is the launch bound (capacity) when ncell_dev is given
-  Scope sc(h, RSL_K_DOA_SCAN);
-  return hip_check(h,
-                   rsl::launch_doa_smoothed(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell),
-                                            (const float2*)steer_sub_c64, G, L, nmax, num_sources, (float)rel,
-                                            (int*)out_nsrc, (int*)out_idx, (float*)out_den, (float*)out_eig,
-                                            (float*)out_spec),
-                   "doa_smoothed");
+  return enter(h, RSL_K_DOA_SCAN, "doa_smoothed", [&] {
+    return rsl::launch_doa_smoothed(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell),
+                                    (const float2*)steer_sub_c64, G, L, nmax, num_sources, (float)rel, (int*)out_nsrc,
+                                    (int*)out_idx, (float*)out_den, (float*)out_eig, (float*)out_spec);
+  });
 }
 
 int rsl_range_cov(rsl_handle h, const void* rds, int F, int A, int S, int C, int c0, int c1, void* cov) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_range_cov: bad shape");
-  if (A < 2 || A > RSL_RA_MAX_A) return fail(h, RSL_ERR_INVALID, "rsl_range_cov: antennas outside [2, RSL_RA_MAX_A]");
-  if (c0 < 0 || c0 >= c1 || c1 > C) return fail(h, RSL_ERR_INVALID, "rsl_range_cov: window needs 0 <= c0 < c1 <= C");
+  Check chk(h, "rsl_range_cov");
+  if (chk.invalid(F < 0 || S <= 0 || C <= 0, "bad shape") ||
+      chk.invalid(A < 2 || A > RSL_RA_MAX_A, "antennas outside [2, RSL_RA_MAX_A]") ||
+      chk.invalid(c0 < 0 || c0 >= c1 || c1 > C, "window needs 0 <= c0 < c1 <= C"))
+    return chk.status;
   if (F == 0) return RSL_OK;
-  if (!rds || !cov) return fail(h, RSL_ERR_INVALID, "rsl_range_cov: null pointer");
-  Scope sc(h, RSL_K_DOA_SCAN);
-  return hip_check(h, rsl::launch_range_cov(h->stream, (const float2*)rds, F, A, S, C, c0, c1, (float2*)cov),
-                   "range_cov");
+  if (chk.invalid(!rds || !cov, "null pointer")) return chk.status;
+  return enter(h, RSL_K_DOA_SCAN, "range_cov", [&] {
+    return rsl::launch_range_cov(h->stream, (const float2*)rds, F, A, S, C, c0, c1, (float2*)cov);
+  });
 }
 
 int rsl_range_azimuth(rsl_handle h, const void* cov, long long n, int A, const void* steer_c64, int G, int method,
                       double loading, void* map, void* arg) {
-  if (!h) return RSL_ERR_INVALID;
-  if (n < 0) return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: n < 0");
-  if (method != RSL_RA_BARTLETT && method != RSL_RA_CAPON)
-    return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: method must be RSL_RA_BARTLETT or RSL_RA_CAPON");
-  if (A < 2 || A > RSL_RA_MAX_A)
-    return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: antennas outside [2, RSL_RA_MAX_A]");
-  if (G < 1) return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: G < 1");
-  if (!(loading >= RSL_RA_MIN_LOADING && loading <= 1.0))
-    return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: loading outside [RSL_RA_MIN_LOADING, 1]");
+  Check chk(h, "rsl_range_azimuth");
+  if (chk.invalid(n < 0, "n < 0") ||
+      chk.invalid(method != RSL_RA_BARTLETT && method != RSL_RA_CAPON,
+                  "method must be RSL_RA_BARTLETT or RSL_RA_CAPON") ||
+      chk.invalid(A < 2 || A > RSL_RA_MAX_A, "antennas outside [2, RSL_RA_MAX_A]") || chk.invalid(G < 1, "G < 1") ||
+      chk.invalid(!(loading >= RSL_RA_MIN_LOADING && loading <= 1.0), "loading outside [RSL_RA_MIN_LOADING, 1]"))
+    return chk.status;
   if (n == 0) return RSL_OK;
-  if (!cov || !steer_c64 || !map) return fail(h, RSL_ERR_INVALID, "rsl_range_azimuth: null pointer");
-  Scope sc(h, RSL_K_DOA_SCAN);
-  return hip_check(h,
-                   rsl::launch_range_azimuth(h->stream, (const float2*)cov, n, A, (const float2*)steer_c64, G,
-                                             method == RSL_RA_CAPON, (float)loading, (float*)map, (int*)arg),
-                   "range_azimuth");
+  if (chk.invalid(!cov || !steer_c64 || !map, "null pointer")) return chk.status;
+  return enter(h, RSL_K_DOA_SCAN, "range_azimuth", [&] {
+    return rsl::launch_range_azimuth(h->stream, (const float2*)cov, n, A, (const float2*)steer_c64, G,
+                                     method == RSL_RA_CAPON, (float)loading, (float*)map, (int*)arg);
+  });
 }
 
 int rsl_cell_extras(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
                     const void* ncell_dev, long long ncell, double esprit_scale, const void* gidx,
                     const void* az_table, void* sig_out, void* esprit_deg, void* phase, void* az_out) {
-  if (!h) return RSL_ERR_INVALID;
-  if (A <= 0 || A > 32 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_cell_extras: bad shape");
-  if (A < 2) return fail(h, RSL_ERR_INVALID, "rsl_cell_extras: needs at least 2 antennas");  // phase reads s0 and s1
-  if (!rds || !c_frame || !c_rc) return fail(h, RSL_ERR_INVALID, "rsl_cell_extras: null pointer");
-  if (az_out && (!gidx || !az_table)) return fail(h, RSL_ERR_INVALID, "rsl_cell_extras: az_out needs gidx+table");
+  Check chk(h, "rsl_cell_extras");
+  if (chk.invalid(A <= 0 || A > 32 || S <= 0 || C <= 0, "bad shape") ||
+      chk.invalid(A < 2, "needs at least 2 antennas") ||  // phase reads s0 and s1
+      chk.invalid(!rds || !c_frame || !c_rc, "null pointer") ||
+      chk.invalid(az_out && (!gidx || !az_table), "az_out needs gidx+table"))
+    return chk.status;
   if (ncell <= 0) return RSL_OK;  // ncell is the launch bound (capacity) when ncell_dev is given
-  Scope sc(h, RSL_K_CELL_EXTRAS);
-  return hip_check(h,
-                   rsl::launch_cell_extras(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell),
-                                           esprit_scale, (const int*)gidx, (const double*)az_table, (float2*)sig_out,
-                                           (double*)esprit_deg, (double*)phase, (double*)az_out),
-                   "cell_extras");
+  return enter(h, RSL_K_CELL_EXTRAS, "cell_extras", [&] {
+    return rsl::launch_cell_extras(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell), esprit_scale,
+                                   (const int*)gidx, (const double*)az_table, (float2*)sig_out, (double*)esprit_deg,
+                                   (double*)phase, (double*)az_out);
+  });
 }
 
 int rsl_cell_refine(rsl_handle h, const void* rds, const void* power, int A, int S, int C, const void* c_frame,
                     const void* c_rc, const void* ncell_dev, long long ncell, const void* gidx, const void* az_table,
                     const void* steer_c64, int G, int range_mode, int doppler_mode, const double* axes4,
                     void* out_points, void* out_az) {
-  if (!h) return RSL_ERR_INVALID;
-  if (A < 2 || A > 32) return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: antennas outside [2, 32]");
-  if (S <= 0 || C <= 0 || G <= 0) return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: bad shape");
-  for (int mode : {range_mode, doppler_mode})
-    if (mode < RSL_REFINE_NONE || mode > RSL_REFINE_HANN)
-      return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: unknown RSL_REFINE_* mode");
-  if (axes4 && !(std::isfinite(axes4[1]) && std::isfinite(axes4[3])))
-    return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: an axis step is not finite");
-  if (!out_points && !out_az) return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: both outputs null");
-  if (reinterpret_cast<size_t>(out_points) & 15)
-    return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: out_points is not 16-byte aligned");
+  Check chk(h, "rsl_cell_refine");
+  auto unknown = [](int mode) { return mode < RSL_REFINE_NONE || mode > RSL_REFINE_HANN; };
+  if (chk.invalid(A < 2 || A > 32, "antennas outside [2, 32]") ||
+      chk.invalid(S <= 0 || C <= 0 || G <= 0, "bad shape") ||
+      chk.invalid(unknown(range_mode) || unknown(doppler_mode), "unknown RSL_REFINE_* mode") ||
+      chk.invalid(axes4 && !(std::isfinite(axes4[1]) && std::isfinite(axes4[3])), "an axis step is not finite") ||
+      chk.invalid(!out_points && !out_az, "both outputs null") ||
+      chk.invalid((reinterpret_cast<size_t>(out_points) & 15) != 0, "out_points is not 16-byte aligned"))
+    return chk.status;
   if (ncell <= 0) return RSL_OK;  // ncell is the launch bound (capacity) when ncell_dev is given
-  if (!rds || !c_frame || !c_rc || !gidx || !az_table || !steer_c64 || !axes4)
-    return fail(h, RSL_ERR_INVALID, "rsl_cell_refine: null pointer");
-  Scope sc(h, RSL_K_CELL_EXTRAS);
-  return hip_check(h,
-                   rsl::launch_cell_refine(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell),
-                                           (const float*)power, (const int*)gidx, (const double*)az_table,
-                                           (const float2*)steer_c64, G, range_mode, doppler_mode, axes4,
-                                           (float*)out_points, (double*)out_az),
-                   "cell_refine");
+  if (chk.invalid(!rds || !c_frame || !c_rc || !gidx || !az_table || !steer_c64 || !axes4, "null pointer"))
+    return chk.status;
+  return enter(h, RSL_K_CELL_EXTRAS, "cell_refine", [&] {
+    return rsl::launch_cell_refine(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, ncell_dev, ncell),
+                                   (const float*)power, (const int*)gidx, (const double*)az_table,
+                                   (const float2*)steer_c64, G, range_mode, doppler_mode, axes4, (float*)out_points,
+                                   (double*)out_az);
+  });
 }
 
 int rsl_confidence(rsl_handle h, const void* rds, int A, int S, int C, const void* c_frame, const void* c_rc,
                    long long n, const void* gidx, const void* steer_c128, const void* steer_phase, void* conf) {
-  if (!h) return RSL_ERR_INVALID;
-  if (A <= 0 || A > 32 || S <= 0 || C <= 0) return fail(h, RSL_ERR_INVALID, "rsl_confidence: bad shape");
-  if (!rds || !c_frame || !c_rc || !gidx || !steer_c128 || !steer_phase || !conf)
-    return fail(h, RSL_ERR_INVALID, "rsl_confidence: null pointer");
-  Scope sc(h, RSL_K_CONFIDENCE);
-  return hip_check(h,
-                   rsl::launch_confidence(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, nullptr, n),
-                                          (const int*)gidx, (const double*)steer_c128, (const double*)steer_phase,
-                                          (double*)conf),
-                   "confidence");
-}
-
-// The checks rsl_velocity, rsl_velocity_robust and rsl_velocity_consensus (fn) share, in one order: the counts; the
-// entry point's own scalars (own: the message of the first that fails, else null); the ridge; an empty batch (RSL_OK
-// with p->F = 0: nothing to launch); the pointers; the grid table; the box.  Fills *p with the typed problem.
-static int velocity_problem(rsl_handle h, const char* fn, const char* own, const void* az, const void* gidx,
-                            const void* az_table, int G, const void* y, const void* amask, const void* seg, long long n,
-                            int F, double k, double ridge, const double* bounds4, const void* out, rsl::VelProblem* p) {
-  *p = {};
-  if (!h) return RSL_ERR_INVALID;
-  auto bad = [&](const char* what) { return fail(h, RSL_ERR_INVALID, std::string(fn) + ": " + what); };
-  if (F < 0 || n < 0) return bad("bad argument");
-  if (own) return bad(own);
-  if (!(ridge >= 0)) return bad("ridge must be >= 0");
-  if (F == 0) return RSL_OK;
-  if ((!az && !gidx) || !y || !seg || !bounds4 || !out) return bad("null pointer");
-  if (gidx && (!az_table || G <= 0 || G > 2048)) return bad("bad grid table");
-  if (!(bounds4[0] <= bounds4[1]) || !(bounds4[2] <= bounds4[3])) return bad("bad bounds");
-  *p = {(const double*)az, (const int*)gidx, (const double*)az_table, G, (const double*)y, (const unsigned*)amask,
-        (const long long*)seg, n, F, k, ridge, bounds4[0], bounds4[1], bounds4[2], bounds4[3]};
-  return RSL_OK;
+  Check chk(h, "rsl_confidence");
+  if (chk.invalid(A <= 0 || A > 32 || S <= 0 || C <= 0, "bad shape") ||
+      chk.invalid(!rds || !c_frame || !c_rc || !gidx || !steer_c128 || !steer_phase || !conf, "null pointer"))
+    return chk.status;
+  return enter(h, RSL_K_CONFIDENCE, "confidence", [&] {
+    return rsl::launch_confidence(h->stream, cell_list(rds, A, S, C, c_frame, c_rc, nullptr, n), (const int*)gidx,
+                                  (const double*)steer_c128, (const double*)steer_phase, (double*)conf);
+  });
 }
 
 int rsl_velocity(rsl_handle h, const void* az, const void* gidx, const void* az_table, int G, const void* y,
                  const void* amask, const void* seg, long long n, int F, double k, double ridge, const double* bounds4,
                  void* out, void* resid, void* pred) {
+  Check chk(h, "rsl_velocity");
   rsl::VelProblem p;
-  const int rc = velocity_problem(h, "rsl_velocity", nullptr, az, gidx, az_table, G, y, amask, seg, n, F, k, ridge,
+  const int rc = velocity_problem(chk, [] { return false; }, az, gidx, az_table, G, y, amask, seg, n, F, k, ridge,
                                   bounds4, out, &p);
   if (rc || p.F == 0) return rc;
-  Scope sc(h, RSL_K_VELOCITY);
-  return hip_check(h, rsl::launch_velocity(h->stream, p, (double*)out, (double*)resid, (double*)pred), "velocity");
+  return enter(h, RSL_K_VELOCITY, "velocity", [&] {
+    return rsl::launch_velocity(h->stream, p, (double*)out, (double*)resid, (double*)pred);
+  });
 }
 
 int rsl_velocity_robust(rsl_handle h, const void* az, const void* gidx, const void* az_table, int G, const void* y,
                         const void* amask, const void* seg, long long n, int F, double k, double ridge,
                         const double* bounds4, int loss, double c, double scale, int iters, double tol, void* out,
                         void* weight, void* resid) {
-  const char* own = (loss != RSL_LOSS_HUBER && loss != RSL_LOSS_TUKEY) ? "loss must be RSL_LOSS_HUBER or RSL_LOSS_TUKEY"
-                    : (!(c > 0) || !std::isfinite(c))                  ? "c must be finite, > 0"
-                    : (std::isnan(scale) || (std::isinf(scale) && scale > 0))
-                        ? "scale must be finite (<= 0: estimated)"
-                    : (iters < 1 || iters > 1000) ? "iters outside 1..1000"
-                    : !(tol >= 0)                 ? "tol must be >= 0"
-                                                  : nullptr;
+  Check chk(h, "rsl_velocity_robust");
+  auto own = [&] {
+    return chk.invalid(loss != RSL_LOSS_HUBER && loss != RSL_LOSS_TUKEY,
+                       "loss must be RSL_LOSS_HUBER or RSL_LOSS_TUKEY") ||
+           chk.invalid(!(c > 0) || !std::isfinite(c), "c must be finite, > 0") ||
+           chk.invalid(std::isnan(scale) || (std::isinf(scale) && scale > 0),
+                       "scale must be finite (<= 0: estimated)") ||
+           chk.invalid(iters < 1 || iters > 1000, "iters outside 1..1000") ||
+           chk.invalid(!(tol >= 0), "tol must be >= 0");
+  };
   rsl::VelProblem p;
-  const int rc = velocity_problem(h, "rsl_velocity_robust", own, az, gidx, az_table, G, y, amask, seg, n, F, k, ridge,
-                                  bounds4, out, &p);
+  const int rc = velocity_problem(chk, own, az, gidx, az_table, G, y, amask, seg, n, F, k, ridge, bounds4, out, &p);
   if (rc || p.F == 0) return rc;
-  Scope sc(h, RSL_K_VELOCITY);
-  return hip_check(h,
-                   rsl::launch_velocity_robust(h->stream, p, loss, c, scale, iters, tol, (double*)out, (float*)weight,
-                                               (double*)resid),
-                   "velocity_robust");
+  return enter(h, RSL_K_VELOCITY, "velocity_robust", [&] {
+    return rsl::launch_velocity_robust(h->stream, p, loss, c, scale, iters, tol, (double*)out, (float*)weight,
+                                       (double*)resid);
+  });
 }
 
 int rsl_velocity_consensus(rsl_handle h, const void* az, const void* gidx, const void* az_table, int G, const void* y,
                            const void* amask, const void* seg, long long n, int F, double k, double ridge,
                            const double* bounds4, double c, double scale, int hyps, double min_det, int refine,
                            unsigned long long seed, long long frame0, void* out, void* weight, void* resid) {
-  const char* own = (!(c > 0) || !std::isfinite(c))           ? "c must be finite, > 0"
-                    : (!(scale > 0) || !std::isfinite(scale)) ? "scale must be finite, > 0"
-                    : (hyps < 1 || hyps > RSL_CONSENSUS_MAX_H) ? "hyps outside 1..RSL_CONSENSUS_MAX_H"
-                    : (!(min_det > 0) || !(min_det <= 1))     ? "min_det outside (0, 1]"
-                    : (refine < 0 || refine > 100)            ? "refine outside 0..100"
-                    : frame0 < 0                              ? "frame0 must be >= 0"
-                                                              : nullptr;
+  Check chk(h, "rsl_velocity_consensus");
+  auto own = [&] {
+    return chk.invalid(!(c > 0) || !std::isfinite(c), "c must be finite, > 0") ||
+           chk.invalid(!(scale > 0) || !std::isfinite(scale), "scale must be finite, > 0") ||
+           chk.invalid(hyps < 1 || hyps > RSL_CONSENSUS_MAX_H, "hyps outside 1..RSL_CONSENSUS_MAX_H") ||
+           chk.invalid(!(min_det > 0) || !(min_det <= 1), "min_det outside (0, 1]") ||
+           chk.invalid(refine < 0 || refine > 100, "refine outside 0..100") ||
+           chk.invalid(frame0 < 0, "frame0 must be >= 0");
+  };
   rsl::VelProblem p;
-  const int rc = velocity_problem(h, "rsl_velocity_consensus", own, az, gidx, az_table, G, y, amask, seg, n, F, k,
-                                  ridge, bounds4, out, &p);
+  const int rc = velocity_problem(chk, own, az, gidx, az_table, G, y, amask, seg, n, F, k, ridge, bounds4, out, &p);
   if (rc || p.F == 0) return rc;
-  Scope sc(h, RSL_K_VELOCITY);
-  return hip_check(h,
-                   rsl::launch_velocity_consensus(h->stream, p, c, scale, hyps, min_det, refine, seed, frame0,
-                                                  (double*)out, (float*)weight, (double*)resid),
-                   "velocity_consensus");
+  return enter(h, RSL_K_VELOCITY, "velocity_consensus", [&] {
+    return rsl::launch_velocity_consensus(h->stream, p, c, scale, hyps, min_det, refine, seed, frame0, (double*)out,
+                                          (float*)weight, (double*)resid);
+  });
 }
 
 int rsl_scan_register(rsl_handle h, const void* points, const void* seg, int F, long long n, const void* weight,
@@ -764,26 +835,21 @@ int rsl_scan_register(rsl_handle h, const void* points, const void* seg, int F, 
                       const void* prev_rc, long long prev_n, const void* prev_n_dev, const void* init, double h_fine,
                       double h_coarse, double dtheta, int K, int iters, double shrink, double tol, double w_min,
                       double dt, void* out, void* omega) {
-  if (!h) return RSL_ERR_INVALID;
+  Check chk(h, "rsl_scan_register");
   auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
   const bool cull = rc || prev_rc;
-  const char* why = !(pos(h_fine) && pos(h_coarse) && pos(dtheta) && pos(dt))
-                        ? "h, h_coarse, dtheta and dt must be finite, > 0"
-                    : !(std::isfinite(w_min) && w_min >= 0.0)                ? "w_min must be finite, >= 0"
-                    : std::isnan(tol)                                        ? "tol is NaN"
-                    : h_coarse < h_fine                                      ? "h_coarse < h"
-                    : (K < 0 || K > RSL_REG_MAX_K)                           ? "K outside 0..RSL_REG_MAX_K"
-                    : (iters < 0 || iters > RSL_REG_MAX_ITERS)               ? "iters outside 0..RSL_REG_MAX_ITERS"
-                    : !(shrink > 0.0 && shrink <= 1.0)                       ? "shrink outside (0, 1]"
-                    : (F < 0 || n < 0 || prev_n < 0)                         ? "negative count"
-                    : (cull && (!axes4 || C <= 0 || !pos(axes4[1]) || !std::isfinite(axes4[0])))
-                        ? "rc needs C > 0 and axes4 with a finite r0 and a finite r_step > 0"
-                    : (F > 0 && (!points || !seg || !out)) ? "null points, seg or out"
-                                                           : nullptr;
-  if (why) {
-    const std::string msg = std::string("rsl_scan_register: ") + why;
-    return fail(h, RSL_ERR_INVALID, msg.c_str());
-  }
+  if (chk.invalid(!(pos(h_fine) && pos(h_coarse) && pos(dtheta) && pos(dt)),
+                  "h, h_coarse, dtheta and dt must be finite, > 0") ||
+      chk.invalid(!(std::isfinite(w_min) && w_min >= 0.0), "w_min must be finite, >= 0") ||
+      chk.invalid(std::isnan(tol), "tol is NaN") || chk.invalid(h_coarse < h_fine, "h_coarse < h") ||
+      chk.invalid(K < 0 || K > RSL_REG_MAX_K, "K outside 0..RSL_REG_MAX_K") ||
+      chk.invalid(iters < 0 || iters > RSL_REG_MAX_ITERS, "iters outside 0..RSL_REG_MAX_ITERS") ||
+      chk.invalid(!(shrink > 0.0 && shrink <= 1.0), "shrink outside (0, 1]") ||
+      chk.invalid(F < 0 || n < 0 || prev_n < 0, "negative count") ||
+      chk.invalid(cull && (!axes4 || C <= 0 || !pos(axes4[1]) || !std::isfinite(axes4[0])),
+                  "rc needs C > 0 and axes4 with a finite r0 and a finite r_step > 0") ||
+      chk.invalid(F > 0 && (!points || !seg || !out), "null points, seg or out"))
+    return chk.status;
   if (F == 0) return RSL_OK;
   const rsl::RegProblem p{cloud_view(points, seg, n, F, weight), (const int*)rc, cull ? C : 1,
                           cull ? axes4[0] : 0.0, cull ? 1.0 / axes4[1] : 0.0,
@@ -791,150 +857,127 @@ int rsl_scan_register(rsl_handle h, const void* points, const void* seg, int F, 
                           prev_points ? (const int*)prev_rc : nullptr, prev_points ? prev_n : 0,
                           prev_points ? (const long long*)prev_n_dev : nullptr, (const double*)init, h_fine, h_coarse,
                           dtheta, K, iters, shrink, tol, w_min, dt};
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h, rsl::launch_scan_register(h->stream, p, (double*)out, (double*)omega), "scan_register");
+  return enter(h, RSL_K_AUX, "scan_register",
+               [&] { return rsl::launch_scan_register(h->stream, p, (double*)out, (double*)omega); });
 }
 
 int rsl_map_update(rsl_handle h, const void* points, const void* seg, int F, long long n, const void* weight,
                    const void* poses, const double* grid4, int nx, int ny, double r_min, double r_max, double min_db,
                    void* hits, void* free_, void* stats) {
-  if (!h) return RSL_ERR_INVALID;
+  Check chk(h, "rsl_map_update");
   const bool grid_ok = grid4 && std::isfinite(grid4[0]) && std::isfinite(grid4[1]) && std::isfinite(grid4[2]) &&
                        grid4[2] > 0.0;
-  const char* why = (F < 0 || n < 0)                                      ? "negative count"
-                    : (F > 0 && (!points || !seg || !poses || !grid4 || !hits)) ? "null points, seg, poses, grid4 or hits"
-                    : (grid4 && !grid_ok)                                 ? "x0, y0 and cell must be finite, cell > 0"
-                    : !(r_min >= 0.0)                                     ? "r_min must be >= 0"
-                    : !(std::isfinite(r_max) && r_max >= r_min)           ? "r_max must be finite, >= r_min"
-                    : (std::isnan(min_db) || min_db == INFINITY)          ? "min_db is NaN or +inf"
-                    : (nx <= 0 || ny <= 0 || (long long)nx * ny >= (1ll << 31)) ? "nx, ny must be > 0, nx ny < 2^31"
-                                                                          : nullptr;
-  if (why) {
-    const std::string msg = std::string("rsl_map_update: ") + why;
-    return fail(h, RSL_ERR_INVALID, msg.c_str());
-  }
+  if (chk.invalid(F < 0 || n < 0, "negative count") ||
+      chk.invalid(F > 0 && (!points || !seg || !poses || !grid4 || !hits), "null points, seg, poses, grid4 or hits") ||
+      chk.invalid(grid4 && !grid_ok, "x0, y0 and cell must be finite, cell > 0") ||
+      chk.invalid(!(r_min >= 0.0), "r_min must be >= 0") ||
+      chk.invalid(!(std::isfinite(r_max) && r_max >= r_min), "r_max must be finite, >= r_min") ||
+      chk.invalid(std::isnan(min_db) || min_db == INFINITY, "min_db is NaN or +inf") ||
+      chk.invalid(nx <= 0 || ny <= 0 || (long long)nx * ny >= (1ll << 31), "nx, ny must be > 0, nx ny < 2^31"))
+    return chk.status;
   if (!grid4) return RSL_OK;  // only with F = 0
   const double inv = 1.0 / grid4[2], rw = std::ceil(r_max * inv) + 1.0;
-  if (!(rw <= (double)RSL_MAP_MAX_RW))
-    return fail(h, RSL_ERR_UNSUPPORTED, "rsl_map_update: ceil(r_max / cell) + 1 above RSL_MAP_MAX_RW");
+  if (chk.unsupported(!(rw <= (double)RSL_MAP_MAX_RW), "ceil(r_max / cell) + 1 above RSL_MAP_MAX_RW"))
+    return chk.status;
   if (F == 0) return RSL_OK;
   const rsl::MapProblem p{cloud_view(points, seg, n, F, weight), (const double*)poses, grid4[0], grid4[1], inv, nx, ny,
                           (int)rw, r_min * r_min, r_max * r_max, min_db};
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h, rsl::launch_map_update(h->stream, p, (unsigned*)hits, (unsigned*)free_, (int*)stats),
-                   "map_update");
+  return enter(h, RSL_K_AUX, "map_update", [&] {
+    return rsl::launch_map_update(h->stream, p, (unsigned*)hits, (unsigned*)free_, (int*)stats);
+  });
 }
 
 int rsl_map_logodds(rsl_handle h, const void* hits, const void* free_, long long ncells, double l_occ, double l_free,
                     double l_min, double l_max, void* out) {
-  if (!h) return RSL_ERR_INVALID;
-  if (!(std::isfinite(l_occ) && std::isfinite(l_free) && std::isfinite(l_min) && std::isfinite(l_max)))
-    return fail(h, RSL_ERR_INVALID, "rsl_map_logodds: l_occ, l_free, l_min and l_max must be finite");
-  if (l_min > l_max) return fail(h, RSL_ERR_INVALID, "rsl_map_logodds: l_min > l_max");
-  if (ncells < 0 || (ncells > 0 && (!hits || !out)))
-    return fail(h, RSL_ERR_INVALID, "rsl_map_logodds: negative count, or null hits or out");
+  Check chk(h, "rsl_map_logodds");
+  if (chk.invalid(!(std::isfinite(l_occ) && std::isfinite(l_free) && std::isfinite(l_min) && std::isfinite(l_max)),
+                  "l_occ, l_free, l_min and l_max must be finite") ||
+      chk.invalid(l_min > l_max, "l_min > l_max") ||
+      chk.invalid(ncells < 0 || (ncells > 0 && (!hits || !out)), "negative count, or null hits or out"))
+    return chk.status;
   if (ncells == 0) return RSL_OK;
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_map_logodds(h->stream, (const unsigned*)hits, (const unsigned*)free_, ncells, l_occ,
-                                           l_free, l_min, l_max, (float*)out),
-                   "map_logodds");
+  return enter(h, RSL_K_AUX, "map_logodds", [&] {
+    return rsl::launch_map_logodds(h->stream, (const unsigned*)hits, (const unsigned*)free_, ncells, l_occ, l_free,
+                                   l_min, l_max, (float*)out);
+  });
 }
 
 int rsl_preprocess_rows(rsl_handle h, const void* in, long long rows, int S, const void* table, int dc, void* out) {
-  if (!h) return RSL_ERR_INVALID;
-  if (rows < 0 || S <= 0 || !in || !table || !out) return fail(h, RSL_ERR_INVALID, "rsl_preprocess_rows: bad argument");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h, rsl::launch_preprocess_rows(h->stream, (const float2*)in, rows, S, (const float2*)table, dc,
-                                                  (float2*)out),
-                   "preprocess_rows");
+  Check chk(h, "rsl_preprocess_rows");
+  if (chk.invalid(rows < 0 || S <= 0 || !in || !table || !out, "bad argument")) return chk.status;
+  return enter(h, RSL_K_AUX, "preprocess_rows", [&] {
+    return rsl::launch_preprocess_rows(h->stream, (const float2*)in, rows, S, (const float2*)table, dc, (float2*)out);
+  });
 }
 
 int rsl_phase_model(rsl_handle h, const void* pos, const void* ang, long long n, const void* x, double k,
                     const void* y, int wrap, double ridge, void* pred, void* resid, void* cost) {
-  if (!h) return RSL_ERR_INVALID;
-  if (n < 0 || !pos || !ang || !x) return fail(h, RSL_ERR_INVALID, "rsl_phase_model: bad argument");
-  if ((resid || cost) && !y) return fail(h, RSL_ERR_INVALID, "rsl_phase_model: residual/cost need y");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h, rsl::launch_phase_model(h->stream, (const double*)pos, (const double*)ang, n, (const double*)x,
-                                              k, (const double*)y, wrap, ridge, (double*)pred, (double*)resid,
-                                              (double*)cost),
-                   "phase_model");
+  Check chk(h, "rsl_phase_model");
+  if (chk.invalid(n < 0 || !pos || !ang || !x, "bad argument") ||
+      chk.invalid((resid || cost) && !y, "residual/cost need y"))
+    return chk.status;
+  return enter(h, RSL_K_AUX, "phase_model", [&] {
+    return rsl::launch_phase_model(h->stream, (const double*)pos, (const double*)ang, n, (const double*)x, k,
+                                   (const double*)y, wrap, ridge, (double*)pred, (double*)resid, (double*)cost);
+  });
 }
 
 int rsl_bvls(rsl_handle h, const void* pos, const void* ang, long long n, const void* y, double k, int nv,
              double ridge, const void* lo, const void* hi, void* out) {
-  if (!h) return RSL_ERR_INVALID;
-  if (n < 0 || (nv != 3 && nv != 6) || !pos || !ang || !y || !lo || !hi || !out || ridge < 0)
-    return fail(h, RSL_ERR_INVALID, "rsl_bvls: bad argument");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h, rsl::launch_bvls(h->stream, (const double*)pos, (const double*)ang, n, (const double*)y, k, nv,
-                                       ridge, (const double*)lo, (const double*)hi, (double*)out),
-                   "bvls");
+  Check chk(h, "rsl_bvls");
+  if (chk.invalid(n < 0 || (nv != 3 && nv != 6) || !pos || !ang || !y || !lo || !hi || !out || ridge < 0,
+                  "bad argument"))
+    return chk.status;
+  return enter(h, RSL_K_AUX, "bvls", [&] {
+    return rsl::launch_bvls(h->stream, (const double*)pos, (const double*)ang, n, (const double*)y, k, nv, ridge,
+                            (const double*)lo, (const double*)hi, (double*)out);
+  });
 }
 
 int rsl_associate(rsl_handle h, const void* cur_xy, int nc, const void* prev_xy, int np, double thr, void* scratch,
                   void* match, void* dist) {
-  if (!h) return RSL_ERR_INVALID;
-  if (nc < 0 || np < 0 || !(thr >= 0)) return fail(h, RSL_ERR_INVALID, "rsl_associate: bad argument");
-  if (nc > 0 && (!cur_xy || !match || !dist || (np > 0 && (!prev_xy || !scratch))))
-    return fail(h, RSL_ERR_INVALID, "rsl_associate: null pointer");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_associate(h->stream, (const double*)cur_xy, nc, (const double*)prev_xy, np, thr,
-                                         (unsigned*)scratch, (int*)match, (double*)dist),
-                   "associate");
+  Check chk(h, "rsl_associate");
+  if (chk.invalid(nc < 0 || np < 0 || !(thr >= 0), "bad argument") ||
+      chk.invalid(nc > 0 && (!cur_xy || !match || !dist || (np > 0 && (!prev_xy || !scratch))), "null pointer"))
+    return chk.status;
+  return enter(h, RSL_K_AUX, "associate", [&] {
+    return rsl::launch_associate(h->stream, (const double*)cur_xy, nc, (const double*)prev_xy, np, thr,
+                                 (unsigned*)scratch, (int*)match, (double*)dist);
+  });
 }
 
 int rsl_peak_topk(rsl_handle h, const void* entry_base, long long entry_cap, int ncube, const void* e_coord,
                   const void* e_pdb, double thr_db, int kmax, int C, void* sel_entry, void* sel_frame, void* sel_rc,
                   void* sel_n) {
-  if (!h) return RSL_ERR_INVALID;
-  if (ncube < 0 || entry_cap < 0 || C <= 0 || C > 8192) return fail(h, RSL_ERR_INVALID, "rsl_peak_topk: bad argument");
-  if (kmax < 1 || kmax > 256) return fail(h, RSL_ERR_UNSUPPORTED, "rsl_peak_topk: kmax must be 1..256");
+  Check chk(h, "rsl_peak_topk");
+  if (chk.invalid(ncube < 0 || entry_cap < 0 || C <= 0 || C > 8192, "bad argument") ||
+      chk.unsupported(kmax < 1 || kmax > 256, "kmax must be 1..256"))
+    return chk.status;
   if (ncube == 0) return RSL_OK;
-  if (!entry_base || !sel_entry || !sel_frame || !sel_rc || !sel_n || (entry_cap > 0 && (!e_coord || !e_pdb)))
-    return fail(h, RSL_ERR_INVALID, "rsl_peak_topk: null pointer");
-  Scope sc(h, RSL_K_AUX);
+  if (chk.invalid(!entry_base || !sel_entry || !sel_frame || !sel_rc || !sel_n ||
+                      (entry_cap > 0 && (!e_coord || !e_pdb)),
+                  "null pointer"))
+    return chk.status;
   // the reference compares float64 power_db > thr_db; the entries' power_db is f32, so compare against the largest
   // float <= thr_db (identical decisions for every f32 value)
-  return hip_check(h,
-                   rsl::launch_topk_entries(h->stream, (const long long*)entry_base, entry_cap, ncube,
-                                            (const unsigned*)e_coord, (const float*)e_pdb,
-                                            rsl::threshold_as_float(thr_db), kmax, C, (int*)sel_entry,
-                                            (int*)sel_frame, (int*)sel_rc, (int*)sel_n),
-                   "peak_topk");
+  return enter(h, RSL_K_AUX, "peak_topk", [&] {
+    return rsl::launch_topk_entries(h->stream, (const long long*)entry_base, entry_cap, ncube,
+                                    (const unsigned*)e_coord, (const float*)e_pdb, rsl::threshold_as_float(thr_db),
+                                    kmax, C, (int*)sel_entry, (int*)sel_frame, (int*)sel_rc, (int*)sel_n);
+  });
 }
 
 int rsl_associate_nearest(rsl_handle h, const void* range_m, const void* az_rad, const void* s0, const void* off,
                           int nframes, long long ntargets, double thr, void* match, void* dist, void* phase) {
-  if (!h) return RSL_ERR_INVALID;
-  if (nframes < 0 || ntargets < 0 || !(thr >= 0)) return fail(h, RSL_ERR_INVALID, "rsl_associate_nearest: bad argument");
+  Check chk(h, "rsl_associate_nearest");
+  if (chk.invalid(nframes < 0 || ntargets < 0 || !(thr >= 0), "bad argument")) return chk.status;
   if (nframes == 0 || ntargets == 0) return RSL_OK;
-  if (!range_m || !az_rad || !s0 || !off || !match || !dist || !phase)
-    return fail(h, RSL_ERR_INVALID, "rsl_associate_nearest: null pointer");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_associate_nearest(h->stream, (const double*)range_m, (const double*)az_rad,
-                                                 (const double2*)s0, (const long long*)off, nframes, ntargets, thr,
-                                                 (int*)match, (double*)dist, (double*)phase),
-                   "associate_nearest");
-}
-
-// The checks rsl_wrapped_solve and rsl_wrapped_search (fn) share, in their order: the arguments (own_bad: the entry
-// point's own conditions), the pointers (own_null: one of the entry point's own is null), the box, then the scratch
-// size (need: the entry point's *_scratch_bytes).
-static int wrapped_check(rsl_handle h, const std::string& fn, const rsl::WrapArgs& a, bool own_bad, bool own_null,
-                         const void* scratch, long long scratch_bytes, long long need, const void* out) {
-  if (!h) return RSL_ERR_INVALID;
-  if (a.n < 1 || (a.nv != 3 && a.nv != 6) || (a.mode != 0 && a.mode != 1) || own_bad || a.nextra < 0 || a.iters < 0)
-    return fail(h, RSL_ERR_INVALID, fn + ": bad argument");
-  if (!a.pos || !a.ang || !a.y || !a.lo || !a.hi || own_null || !scratch || !out || (a.nextra > 0 && !a.extra))
-    return fail(h, RSL_ERR_INVALID, fn + ": null pointer");
-  for (int c = 0; c < 6; ++c)
-    if (!(a.lo[c] <= a.hi[c])) return fail(h, RSL_ERR_INVALID, fn + ": bad bounds");
-  if (scratch_bytes < need) return fail(h, RSL_ERR_INVALID, fn + ": scratch too small");
-  return RSL_OK;
+  if (chk.invalid(!range_m || !az_rad || !s0 || !off || !match || !dist || !phase, "null pointer")) return chk.status;
+  return enter(h, RSL_K_AUX, "associate_nearest", [&] {
+    return rsl::launch_associate_nearest(h->stream, (const double*)range_m, (const double*)az_rad, (const double2*)s0,
+                                         (const long long*)off, nframes, ntargets, thr, (int*)match, (double*)dist,
+                                         (double*)phase);
+  });
 }
 
 long long rsl_wrapped_scratch_bytes(long long n, int grid_n, int nextra) {
@@ -946,28 +989,16 @@ int rsl_wrapped_solve(rsl_handle h, const void* pos, const void* ang, long long 
                       double w, double vmax, double wmax, const void* prev, const double* lo6, const double* hi6,
                       int nv, int grid_n, const void* extra, int nextra, int iters, void* scratch,
                       long long scratch_bytes, void* out) {
+  Check chk(h, "rsl_wrapped_solve");
   const rsl::WrapArgs a = {(const double*)pos, (const double*)ang, n, (const double*)y, k, mode, w, vmax, wmax,
                            (const double*)prev, lo6, hi6, nv, (const double*)extra, nextra, iters};
   const bool own_bad = grid_n < 0 || grid_n * (long long)grid_n + nextra < 1;
-  if (const int rc = wrapped_check(h, "rsl_wrapped_solve", a, own_bad, false, scratch, scratch_bytes,
+  if (const int rc = wrapped_check(chk, a, own_bad, false, scratch, scratch_bytes,
                                    rsl_wrapped_scratch_bytes(n, grid_n, nextra), out))
     return rc;
-  Scope sc(h, RSL_K_VELOCITY);
-  return hip_check(h, rsl::launch_wrapped_solve(h->stream, a, grid_n, (double*)scratch, (double*)out),
-                   "wrapped_solve");
-}
-
-// stage-1 grid of rsl_wrapped_search: ceil(width / spacing) points per axis, at least 1, at most 2^15 (so the grid
-// has < 2^30 starts)
-static void search_grid(const double* lo6, const double* hi6, double spacing, long long* gx, long long* gy) {
-  auto pts = [&](double w) {
-    double g = spacing > 0 ? ceil(w / spacing) : 1.0;
-    if (!(g >= 1.0)) g = 1.0;
-    if (g > 32768.0) g = 32768.0;
-    return (long long)g;
-  };
-  *gx = pts(hi6[0] - lo6[0]);
-  *gy = pts(hi6[1] - lo6[1]);
+  return enter(h, RSL_K_VELOCITY, "wrapped_solve", [&] {
+    return rsl::launch_wrapped_solve(h->stream, a, grid_n, (double*)scratch, (double*)out);
+  });
 }
 
 long long rsl_wrapped_search_scratch_bytes(long long n, const double* lo6, const double* hi6, double spacing,
@@ -982,88 +1013,85 @@ int rsl_wrapped_search(rsl_handle h, const void* pos, const void* ang, long long
                        double w, double vmax, double wmax, const void* prev, const double* lo6, const double* hi6,
                        int nv, const double* base6, double spacing, int nbest, const void* extra, int nextra, int iters,
                        void* scratch, long long scratch_bytes, void* out) {
+  Check chk(h, "rsl_wrapped_search");
   const rsl::WrapArgs a = {(const double*)pos, (const double*)ang, n, (const double*)y, k, mode, w, vmax, wmax,
                            (const double*)prev, lo6, hi6, nv, (const double*)extra, nextra, iters};
   const bool own_bad = !(spacing > 0) || nbest < 1 || nbest > 1024;
-  if (const int rc = wrapped_check(h, "rsl_wrapped_search", a, own_bad, !base6, scratch, scratch_bytes,
+  if (const int rc = wrapped_check(chk, a, own_bad, !base6, scratch, scratch_bytes,
                                    rsl_wrapped_search_scratch_bytes(n, lo6, hi6, spacing, nbest, nextra), out))
     return rc;
   long long gx, gy;
   search_grid(lo6, hi6, spacing, &gx, &gy);
-  Scope sc(h, RSL_K_VELOCITY);
-  return hip_check(h, rsl::launch_wrapped_search(h->stream, a, base6, gx, gy, nbest, (double*)scratch, (double*)out),
-                   "wrapped_search");
+  return enter(h, RSL_K_VELOCITY, "wrapped_search", [&] {
+    return rsl::launch_wrapped_search(h->stream, a, base6, gx, gy, nbest, (double*)scratch, (double*)out);
+  });
 }
 
 int rsl_traj_scan(rsl_handle h, const void* vel, int vstride, int nv, const void* omega, int ostride,
                   const void* timestamps, double dt, long long F, int method, void* pos, void* quat, void* summary) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || nv < 0 || nv > 3 || vstride < nv || (omega && ostride < 3) || (method != 0 && method != 1))
-    return fail(h, RSL_ERR_INVALID, "rsl_traj_scan: bad argument");
-  if (F > 0 && (!vel || !pos || !quat)) return fail(h, RSL_ERR_INVALID, "rsl_traj_scan: null pointer");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_traj_scan(h->stream, (const double*)vel, vstride, nv, (const double*)omega, ostride,
-                                         (const double*)timestamps, dt, F, method, (double*)pos, (double*)quat,
-                                         (double*)summary),
-                   "traj_scan");
+  Check chk(h, "rsl_traj_scan");
+  if (chk.invalid(F < 0 || nv < 0 || nv > 3 || vstride < nv || (omega && ostride < 3) || (method != 0 && method != 1),
+                  "bad argument") ||
+      chk.invalid(F > 0 && (!vel || !pos || !quat), "null pointer"))
+    return chk.status;
+  return enter(h, RSL_K_AUX, "traj_scan", [&] {
+    return rsl::launch_traj_scan(h->stream, (const double*)vel, vstride, nv, (const double*)omega, ostride,
+                                 (const double*)timestamps, dt, F, method, (double*)pos, (double*)quat,
+                                 (double*)summary);
+  });
 }
 
 int rsl_traj_apply(rsl_handle h, void* pos, void* quat, long long F, const void* base) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || (F > 0 && (!pos || !quat || !base))) return fail(h, RSL_ERR_INVALID, "rsl_traj_apply: bad argument");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h, rsl::launch_traj_apply(h->stream, (double*)pos, (double*)quat, F, (const double*)base),
-                   "traj_apply");
+  Check chk(h, "rsl_traj_apply");
+  if (chk.invalid(F < 0 || (F > 0 && (!pos || !quat || !base)), "bad argument")) return chk.status;
+  return enter(h, RSL_K_AUX, "traj_apply", [&] {
+    return rsl::launch_traj_apply(h->stream, (double*)pos, (double*)quat, F, (const double*)base);
+  });
 }
 
 int rsl_traj_smooth(rsl_handle h, const void* x, long long F, int ncol, int size, void* out) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || ncol < 1 || size < 1 || (F > 0 && (!x || !out)))
-    return fail(h, RSL_ERR_INVALID, "rsl_traj_smooth: bad argument");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h, rsl::launch_traj_smooth(h->stream, (const double*)x, F, ncol, size, (double*)out),
-                   "traj_smooth");
+  Check chk(h, "rsl_traj_smooth");
+  if (chk.invalid(F < 0 || ncol < 1 || size < 1 || (F > 0 && (!x || !out)), "bad argument")) return chk.status;
+  return enter(h, RSL_K_AUX, "traj_smooth", [&] {
+    return rsl::launch_traj_smooth(h->stream, (const double*)x, F, ncol, size, (double*)out);
+  });
 }
 
 int rsl_traj_stitch(rsl_handle h, const void* summaries, int R, int rank, double dt, int method, void* state,
                     void* base) {
-  if (!h) return RSL_ERR_INVALID;
-  if (R < 1 || rank < 0 || rank >= R || (method != 0 && method != 1) || !summaries || !state || !base)
-    return fail(h, RSL_ERR_INVALID, "rsl_traj_stitch: bad argument");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_traj_stitch(h->stream, (const double*)summaries, R, rank, dt, method, (double*)state,
-                                           (double*)base),
-                   "traj_stitch");
+  Check chk(h, "rsl_traj_stitch");
+  if (chk.invalid(R < 1 || rank < 0 || rank >= R || (method != 0 && method != 1) || !summaries || !state || !base,
+                  "bad argument"))
+    return chk.status;
+  return enter(h, RSL_K_AUX, "traj_stitch", [&] {
+    return rsl::launch_traj_stitch(h->stream, (const double*)summaries, R, rank, dt, method, (double*)state,
+                                   (double*)base);
+  });
 }
 
 int rsl_synth_pattern(rsl_handle h, const void* scatterers, int n, int A, int S, double fc, double bandwidth,
                       double chirp_duration, double antenna_spacing, void* pattern) {
-  if (!h) return RSL_ERR_INVALID;
-  if (n < 0 || A <= 0 || S <= 0 || !(fc > 0) || !(chirp_duration > 0))
-    return fail(h, RSL_ERR_INVALID, "rsl_synth_pattern: bad arguments");
-  if (!pattern || (n > 0 && !scatterers)) return fail(h, RSL_ERR_INVALID, "rsl_synth_pattern: null pointer");
+  Check chk(h, "rsl_synth_pattern");
+  if (chk.invalid(n < 0 || A <= 0 || S <= 0 || !(fc > 0) || !(chirp_duration > 0), "bad arguments") ||
+      chk.invalid(!pattern || (n > 0 && !scatterers), "null pointer"))
+    return chk.status;
   const double d = antenna_spacing > 0 ? antenna_spacing : 0.5 * 3e8 / fc;
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_synth_pattern(h->stream, (const double*)scatterers, n, A, S, fc, bandwidth,
-                                             chirp_duration, d, (double2*)pattern),
-                   "synth_pattern");
+  return enter(h, RSL_K_AUX, "synth_pattern", [&] {
+    return rsl::launch_synth_pattern(h->stream, (const double*)scatterers, n, A, S, fc, bandwidth, chirp_duration, d,
+                                     (double2*)pattern);
+  });
 }
 
 int rsl_synth_cube(rsl_handle h, const void* pattern, int F, int A, int C, int S, double noise_power,
                    unsigned long long seed, long long frame0, void* cube) {
-  if (!h) return RSL_ERR_INVALID;
-  if (F < 0 || A <= 0 || C <= 0 || S <= 0 || frame0 < 0 || !(noise_power >= 0))
-    return fail(h, RSL_ERR_INVALID, "rsl_synth_cube: bad arguments");
-  if (S % 2) return fail(h, RSL_ERR_UNSUPPORTED, "rsl_synth_cube: S must be even");
-  if (!pattern || !cube) return fail(h, RSL_ERR_INVALID, "rsl_synth_cube: null pointer");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_synth_cube(h->stream, (const double2*)pattern, F, A, C, S, noise_power, seed, frame0,
-                                          (float2*)cube),
-                   "synth_cube");
+  Check chk(h, "rsl_synth_cube");
+  if (chk.invalid(F < 0 || A <= 0 || C <= 0 || S <= 0 || frame0 < 0 || !(noise_power >= 0), "bad arguments") ||
+      chk.unsupported(S % 2, "S must be even") || chk.invalid(!pattern || !cube, "null pointer"))
+    return chk.status;
+  return enter(h, RSL_K_AUX, "synth_cube", [&] {
+    return rsl::launch_synth_cube(h->stream, (const double2*)pattern, F, A, C, S, noise_power, seed, frame0,
+                                  (float2*)cube);
+  });
 }
 
 long long rsl_pose_error_scratch_bytes(long long n, int nlen) {
@@ -1073,56 +1101,50 @@ long long rsl_pose_error_scratch_bytes(long long n, int nlen) {
 
 int rsl_pose_align(rsl_handle h, const void* est, const void* gt, long long n, void* scratch, void* align,
                    void* aligned, void* ape_err, void* ape_stats) {
-  if (!h) return RSL_ERR_INVALID;
-  if (n < 1) return fail(h, RSL_ERR_INVALID, "rsl_pose_align: need at least one pose");
-  if (!est || !gt || !scratch || !align || !aligned || !ape_err)
-    return fail(h, RSL_ERR_INVALID, "rsl_pose_align: null pointer");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_pose_align(h->stream, (const double*)est, (const double*)gt, n, (double*)scratch,
-                                          (double*)align, (double*)aligned, (double*)ape_err, (double*)ape_stats),
-                   "pose_align");
+  Check chk(h, "rsl_pose_align");
+  if (chk.invalid(n < 1, "need at least one pose") ||
+      chk.invalid(!est || !gt || !scratch || !align || !aligned || !ape_err, "null pointer"))
+    return chk.status;
+  return enter(h, RSL_K_AUX, "pose_align", [&] {
+    return rsl::launch_pose_align(h->stream, (const double*)est, (const double*)gt, n, (double*)scratch,
+                                  (double*)align, (double*)aligned, (double*)ape_err, (double*)ape_stats);
+  });
 }
 
 int rsl_pose_rte(rsl_handle h, const void* aligned, const void* gt, long long n, const void* lengths, int nlen,
                  void* scratch, void* err, void* counts, void* stats) {
-  if (!h) return RSL_ERR_INVALID;
-  if (n < 1 || nlen < 0 || nlen > 1024) return fail(h, RSL_ERR_INVALID, "rsl_pose_rte: bad arguments");
+  Check chk(h, "rsl_pose_rte");
+  if (chk.invalid(n < 1 || nlen < 0 || nlen > 1024, "bad arguments")) return chk.status;
   if (nlen == 0) return RSL_OK;
-  if (!aligned || !gt || !lengths || !scratch || !err || !counts || !stats)
-    return fail(h, RSL_ERR_INVALID, "rsl_pose_rte: null pointer");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_pose_rte(h->stream, (const double*)aligned, (const double*)gt, n,
-                                        (const double*)lengths, nlen, (double*)scratch, (double*)err,
-                                        (unsigned long long*)counts, (double*)stats),
-                   "pose_rte");
+  if (chk.invalid(!aligned || !gt || !lengths || !scratch || !err || !counts || !stats, "null pointer"))
+    return chk.status;
+  return enter(h, RSL_K_AUX, "pose_rte", [&] {
+    return rsl::launch_pose_rte(h->stream, (const double*)aligned, (const double*)gt, n, (const double*)lengths, nlen,
+                                (double*)scratch, (double*)err, (unsigned long long*)counts, (double*)stats);
+  });
 }
 
 int rsl_music_subspace(rsl_handle h, const void* sigs, long long n, int M, int num_sources, const void* steer_c128,
                        int G, void* spec) {
-  if (!h) return RSL_ERR_INVALID;
-  if (n < 0 || M < 1 || M > 16 || G < 1) return fail(h, RSL_ERR_INVALID, "rsl_music_subspace: bad shape");
+  Check chk(h, "rsl_music_subspace");
+  if (chk.invalid(n < 0 || M < 1 || M > 16 || G < 1, "bad shape")) return chk.status;
   if (n == 0) return RSL_OK;
-  if (!sigs || !steer_c128 || !spec) return fail(h, RSL_ERR_INVALID, "rsl_music_subspace: null pointer");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_music_subspace(h->stream, (const double*)sigs, n, M, num_sources,
-                                              (const double*)steer_c128, G, (double*)spec),
-                   "music_subspace");
+  if (chk.invalid(!sigs || !steer_c128 || !spec, "null pointer")) return chk.status;
+  return enter(h, RSL_K_AUX, "music_subspace", [&] {
+    return rsl::launch_music_subspace(h->stream, (const double*)sigs, n, M, num_sources, (const double*)steer_c128, G,
+                                      (double*)spec);
+  });
 }
 
 int rsl_esprit_subspace(rsl_handle h, const void* sigs, long long n, int M, int num_sources, double esprit_scale,
                         void* deg) {
-  if (!h) return RSL_ERR_INVALID;
-  if (n < 0 || M < 1 || M > 16) return fail(h, RSL_ERR_INVALID, "rsl_esprit_subspace: bad shape");
+  Check chk(h, "rsl_esprit_subspace");
+  if (chk.invalid(n < 0 || M < 1 || M > 16, "bad shape")) return chk.status;
   if (n == 0) return RSL_OK;
-  if (!sigs || !deg) return fail(h, RSL_ERR_INVALID, "rsl_esprit_subspace: null pointer");
-  Scope sc(h, RSL_K_AUX);
-  return hip_check(h,
-                   rsl::launch_esprit_subspace(h->stream, (const double*)sigs, n, M, num_sources, esprit_scale,
-                                               (double*)deg),
-                   "esprit_subspace");
+  if (chk.invalid(!sigs || !deg, "null pointer")) return chk.status;
+  return enter(h, RSL_K_AUX, "esprit_subspace", [&] {
+    return rsl::launch_esprit_subspace(h->stream, (const double*)sigs, n, M, num_sources, esprit_scale, (double*)deg);
+  });
 }
 
 }  // extern "C"

@@ -484,11 +484,8 @@ bool emit_compact_supported(int C, bool union_mask, bool peak_pow, bool want_pdb
 }
 
 hipError_t launch_emit_compact(hipStream_t st, const unsigned long long* mask, const unsigned long long* umask,
-                               const float* pk_pow, int pk_group, int F, int A, int S, int C,
-                               const int* entry_row_off, const int* cell_row_off, const long long* entry_base,
-                               const long long* cell_base, long long entry_cap, long long cell_cap,
-                               unsigned* e_coord, int* e_cell, float* e_pdb, int* c_frame, int* c_rc,
-                               unsigned* c_amask) {
+                               const float* pk_pow, int pk_group, int F, int A, int S, int C, const PeakOffsets& off,
+                               const PeakLists& out) {
   if (F <= 0) return hipSuccess;
   if (A > 32) return hipErrorInvalidValue;
   const int W = (C + 63) / 64;
@@ -497,11 +494,12 @@ hipError_t launch_emit_compact(hipStream_t st, const unsigned long long* mask, c
   return with_int<1, 2, 4, 8, 16, 32, 64>(W, [&](auto w) {
     constexpr int WW = decltype(w)::value;
     const auto cells = A <= 8 ? k_emit_cells<WW, 8> : A <= 16 ? k_emit_cells<WW, 16> : k_emit_cells<WW, 32>;
-    if (hipError_t e = launch(st, cells, (long long)F * nbf, 256, 0, mask, umask, nbf, A, S, C, cell_row_off, cell_base,
-                              cell_cap, c_frame, c_rc, c_amask))
+    if (hipError_t e = launch(st, cells, (long long)F * nbf, 256, 0, mask, umask, nbf, A, S, C, off.cell_row_off,
+                              off.cell_base, out.cell_cap, out.c_frame, out.c_rc, out.c_amask))
       return e;
     return launch(st, k_emit_entries<WW>, nbe, 256, 0, mask, umask, pk_pow, pk_group, (long long)F, A, S, C,
-                  entry_row_off, cell_row_off, entry_base, cell_base, entry_cap, e_coord, e_cell, e_pdb);
+                  off.entry_row_off, off.cell_row_off, off.entry_base, off.cell_base, out.entry_cap, out.e_coord,
+                  out.e_cell, out.e_pdb);
   });
 }
 
@@ -546,14 +544,13 @@ hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const 
 }
 
 hipError_t launch_emit_rows(hipStream_t st, const float2* rds, const unsigned long long* mask, int F, int A, int S,
-                            int C, const int* entry_row_off, const int* cell_row_off, const long long* entry_base,
-                            const long long* cell_base, long long entry_cap, long long cell_cap, unsigned* e_coord,
-                            int* e_cell, float* e_pdb, int* c_frame, int* c_rc, unsigned* c_amask) {
+                            int C, const PeakOffsets& off, const PeakLists& out) {
   if (F <= 0) return hipSuccess;
   const int W = (C + 63) / 64;
   const long rows = (long)F * S;
-  return launch(st, k_emit, (rows + 3) / 4, 256, 0, rds, mask, F, A, S, C, W, entry_row_off, cell_row_off, entry_base,
-                cell_base, entry_cap, cell_cap, e_coord, e_cell, e_pdb, c_frame, c_rc, c_amask);
+  return launch(st, k_emit, (rows + 3) / 4, 256, 0, rds, mask, F, A, S, C, W, off.entry_row_off, off.cell_row_off,
+                off.entry_base, off.cell_base, out.entry_cap, out.cell_cap, out.e_coord, out.e_cell, out.e_pdb,
+                out.c_frame, out.c_rc, out.c_amask);
 }
 
 }  // namespace rsl

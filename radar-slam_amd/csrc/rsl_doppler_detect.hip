@@ -753,10 +753,10 @@ bool doppler_detect_supported(int C, int S) {
 }
 
 hipError_t launch_doppler_detect(hipStream_t st, const float2* work, int F, int A, int C, int S, const float2* tw_C,
-                                 float2* rds, const DetectArgs& det, bool* supported, int* pk_group, bool packed) {
+                                 float2* rds, const DetectArgs& det, int* pk_group, bool packed) {
   *pk_group = 1;
-  *supported = doppler_detect_supported(C, S);
-  if (!*supported || F <= 0 || A <= 0) return hipSuccess;
+  if (!doppler_detect_supported(C, S)) return hipErrorInvalidValue;
+  if (F <= 0 || A <= 0) return hipSuccess;
   switch (C) {
 #define CASE(n) \
   case n:       \
@@ -764,8 +764,7 @@ hipError_t launch_doppler_detect(hipStream_t st, const float2* work, int F, int 
     CASE(8) CASE(16) CASE(32) CASE(64) CASE(128) CASE(256) CASE(512) CASE(1024)
 #undef CASE
     default:
-      *supported = false;
-      return hipSuccess;
+      return hipErrorInvalidValue;
   }
 }
 

@@ -898,9 +898,8 @@ hipError_t launch_doppler_dft(hipStream_t st, const float2* work, int F, int A, 
 }
 
 hipError_t launch_range_fft(hipStream_t st, const float2* cube, int F, int A, int Ct, int chirp0, int C, int S,
-                            const float2* table, const float2* tw_S, int dc, float2* work, bool* supported,
-                            RfQueues* queues, bool packed) {
-  *supported = true;
+                            const float2* table, const float2* tw_S, int dc, float2* work, RfQueues* queues,
+                            bool packed) {
   if (F <= 0 || A <= 0 || C <= 0) return hipSuccess;
   switch (S) {
 #define CASE(n) \
@@ -909,17 +908,13 @@ hipError_t launch_range_fft(hipStream_t st, const float2* cube, int F, int A, in
     RSL_FFT_SIZES(CASE)
 #undef CASE
     default:
-      if (S > 4096) {
-        *supported = false;
-        return hipSuccess;
-      }
+      if (S > 4096) return hipErrorInvalidValue;
       return launch_range_dft(st, cube, F, A, Ct, chirp0, C, S, table, tw_S, dc, work);
   }
 }
 
 hipError_t launch_doppler_fft(hipStream_t st, const float2* work, int F, int A, int C, int S, const float2* tw_C,
-                              float2* rds, bool* supported) {
-  *supported = true;
+                              float2* rds) {
   if (F <= 0 || A <= 0 || S <= 0) return hipSuccess;
   switch (C) {
 #define CASE(n) \
@@ -928,10 +923,7 @@ hipError_t launch_doppler_fft(hipStream_t st, const float2* work, int F, int A, 
     RSL_FFT_SIZES(CASE)
 #undef CASE
     default:
-      if (C > 4096) {
-        *supported = false;
-        return hipSuccess;
-      }
+      if (C > 4096) return hipErrorInvalidValue;
       return launch_doppler_dft(st, work, F, A, C, S, tw_C, rds);
   }
 }

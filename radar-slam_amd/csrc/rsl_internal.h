@@ -31,15 +31,17 @@ void rf_queues_free(RfQueues* s);
 // An integer knob of the development build (make dev), by its environment name: 0 when unset, and always 0 in the
 // product build.
 int dev_knob(const char* name);
+// A size that launch_range_fft, launch_doppler_fft or launch_doppler_detect cannot serve is hipErrorInvalidValue.  The
+// C ABI never lets such a call through: rsl_fft_supported and doppler_detect_supported decide beforehand (rsl_api.hip).
 // K1: dechirp * window (table), range FFT (S points), DC bin zeroing.
 // cube c64 [F, A, Ct, S] (chirps chirp0 .. chirp0+C-1 used) -> work c64 [F, A, C, S]
 hipError_t launch_range_fft(hipStream_t st, const float2* cube, int F, int A, int Ct, int chirp0, int C, int S,
-                            const float2* table, const float2* tw_S, int dc, float2* work, bool* supported,
-                            RfQueues* queues, bool packed = false);
+                            const float2* table, const float2* tw_S, int dc, float2* work, RfQueues* queues,
+                            bool packed = false);
 // K2: Doppler FFT (C points) + fftshift on both axes, transposed store.
 // work c64 [F, A, C, S] -> rds c64 [F, A, S, C]
 hipError_t launch_doppler_fft(hipStream_t st, const float2* work, int F, int A, int C, int S, const float2* tw_C,
-                              float2* rds, bool* supported);
+                              float2* rds);
 
 // K2+K3 fused (Doppler FFT + fftshift + RDS store + detection); supported when C is a power of two and the
 // block's KB range bins tile both halves of S.
@@ -58,8 +60,7 @@ struct DetectArgs {
 };
 // *pk_group: the rows per group of the compacted peak powers (1 = row-compact).
 hipError_t launch_doppler_detect(hipStream_t st, const float2* work, int F, int A, int C, int S, const float2* tw_C,
-                                 float2* rds, const DetectArgs& det, bool* supported, int* pk_group,
-                                 bool packed = false);
+                                 float2* rds, const DetectArgs& det, int* pk_group, bool packed = false);
 // packed (both launches): `work` holds packed rows (rsl_packed.h: 6 B per value in 24 KiB tiles, each bin's int8
 // exponent inside its 48-B unit) -- only where work_packed_supported(C, S).
 bool work_packed_supported(int C, int S);
@@ -96,19 +97,32 @@ hipError_t launch_offsets(hipStream_t st, const unsigned long long* mask, const 
 // computes).  The compact path serves a call with the union mask, with peak powers unless no power_db is wanted, and
 // with a power-of-two count W = ceil(C / 64) <= 64 of mask words per row; the general path serves every other call.
 bool emit_compact_supported(int C, bool union_mask, bool peak_pow, bool want_pdb);
+// What both emit paths read of rsl_peak_offsets' results and where they write the lists, typed by peak_offsets and
+// peak_lists (rsl_api.hip).  Host side only, like DetectArgs: the kernels take the members as separate `__restrict__`
+// arguments.  The caps are the lists' capacities in entries and cells; e_pdb is optional.
+struct PeakOffsets {
+  const int* entry_row_off;
+  const int* cell_row_off;
+  const long long* entry_base;
+  const long long* cell_base;
+};
+struct PeakLists {
+  long long entry_cap, cell_cap;
+  unsigned* e_coord;
+  int* e_cell;
+  float* e_pdb;
+  int* c_frame;
+  int* c_rc;
+  unsigned* c_amask;
+};
 // General path: one wave per range row, power_db from the RDS.
 hipError_t launch_emit_rows(hipStream_t st, const float2* rds, const unsigned long long* mask, int F, int A, int S,
-                            int C, const int* entry_row_off, const int* cell_row_off, const long long* entry_base,
-                            const long long* cell_base, long long entry_cap, long long cell_cap, unsigned* e_coord,
-                            int* e_cell, float* e_pdb, int* c_frame, int* c_rc, unsigned* c_amask);
+                            int C, const PeakOffsets& off, const PeakLists& out);
 // Compact path, only where emit_compact_supported: block compactions of the masks and the union masks, power_db from
 // the group-compact peak powers (pk_group rows per group, 1 = row-compact); no RDS read.
 hipError_t launch_emit_compact(hipStream_t st, const unsigned long long* mask, const unsigned long long* umask,
-                               const float* pk_pow, int pk_group, int F, int A, int S, int C,
-                               const int* entry_row_off, const int* cell_row_off, const long long* entry_base,
-                               const long long* cell_base, long long entry_cap, long long cell_cap,
-                               unsigned* e_coord, int* e_cell, float* e_pdb, int* c_frame, int* c_rc,
-                               unsigned* c_amask);
+                               const float* pk_pow, int pk_group, int F, int A, int S, int C, const PeakOffsets& off,
+                               const PeakLists& out);
 // K4..K7, the direction-of-arrival stage.  CellList (the cells of a call) and steer_layout (the sections of the
 // steering table) are in rsl_doa_common.h.
 // K5: steering scan on MFMA (f32 16x16x4), argmax; optional spectrum (spec_ld 0: cell-major [n][G], > 0: grid-major

@@ -208,6 +208,23 @@ def test_null_handle_errors():
     assert lib.rsl_sync(None) == 1
     assert lib.rsl_rds(None, None, 1, 8, 64, 0, 64, 256, None, 1, None, None) == 1
     assert lib.rsl_last_error(None) == b'null handle'
+    # every entry point that takes the handle first and returns a status, with a null handle and zero / null arguments:
+    # RSL_ERR_INVALID before anything is read, no message stored anywhere.  rsl_destroy(NULL) is a no-op by contract;
+    # rsl_timing_spans returns a count, -1 for a refusal.
+    from rsl import _lib
+    walked = []
+    for name, (res, args) in _lib.SIGNATURES.items():
+        if res is not ctypes.c_int or not args or args[0] is not ctypes.c_void_p:
+            continue
+        zeros = [None if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer) else t(0).value for t in args[1:]]
+        want = {'rsl_destroy': 0, 'rsl_timing_spans': -1}.get(name, 1)
+        assert getattr(lib, name)(None, *zeros) == want, name
+        assert lib.rsl_last_error(None) == b'null handle', name
+        walked.append(name)
+    assert walked == list(_lib.CONVERTERS) and len(walked) >= 48  # the other rows of the table take no handle
+    group = ctypes.c_int(7)  # nothing is written through a null handle either
+    assert lib.rsl_rds_detect(None, None, 0, 0, 0, 0, 0, 0, None, 0, None, None, 0.0, 0, 0, None, None, None, None,
+                              ctypes.byref(group)) == 1 and group.value == 7
 
 
 def test_steer_table_layout():
