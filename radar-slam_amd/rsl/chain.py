@@ -128,80 +128,9 @@ class ChainConfig:
     reg_w_min: float = 3.0                     # the least kernel weight a step needs
 
     def __post_init__(self):
-        if self.registration:
-            if not self.point_cloud:
-                raise ValueError('registration=True needs point_cloud=True')
-            pos = lambda v: math.isfinite(float(v)) and float(v) > 0.0
-            if not (pos(self.reg_h) and pos(self.reg_h_coarse) and pos(self.reg_dtheta) and pos(self.dt)):
-                raise ValueError('registration needs reg_h, reg_h_coarse, reg_dtheta and dt finite and > 0')
-            if float(self.reg_h_coarse) < float(self.reg_h):
-                raise ValueError(f'reg_h_coarse {self.reg_h_coarse!r} is below reg_h {self.reg_h!r}')
-            if not 0 <= int(self.reg_k) <= _lib.REG_MAX_K:
-                raise ValueError(f'reg_k must lie in [0, {_lib.REG_MAX_K}], not {self.reg_k!r}')
-            if not 0 <= int(self.reg_iters) <= _lib.REG_MAX_ITERS:
-                raise ValueError(f'reg_iters must lie in [0, {_lib.REG_MAX_ITERS}], not {self.reg_iters!r}')
-            if not 0.0 < float(self.reg_shrink) <= 1.0:
-                raise ValueError(f'reg_shrink must lie in (0, 1], not {self.reg_shrink!r}')
-            if not (math.isfinite(float(self.reg_w_min)) and float(self.reg_w_min) >= 0.0):
-                raise ValueError(f'reg_w_min must be finite and >= 0, not {self.reg_w_min!r}')
-        if self.velocity_az not in ('grid', 'refined'):
-            raise ValueError(f"velocity_az must be 'grid' or 'refined', not {self.velocity_az!r}")
-        if self.velocity_az == 'refined' and not self.point_cloud:
-            raise ValueError("velocity_az='refined' needs point_cloud=True")
-        if self.point_cloud:
-            if not 2 <= int(self.num_antennas) <= 32:
-                raise ValueError(f'point_cloud needs 2 to 32 antennas, not {self.num_antennas}')
-            tables.refine_mode_for_window(self.window_type)  # ValueError for a window without an estimator
-        if self.ra_map is not None and self.ra_map not in _lib.RA_IDS:
-            raise ValueError(f"ra_map must be None, 'bartlett' or 'capon', not {self.ra_map!r}")
-        if self.ra_doppler is not None:
-            if len(tuple(self.ra_doppler)) != 2 or not (0 <= int(self.ra_doppler[0]) < int(self.ra_doppler[1])
-                                                        <= int(self.num_chirps)):
-                raise ValueError(f'ra_doppler must be (c0, c1) with 0 <= c0 < c1 <= {int(self.num_chirps)}, '
-                                 f'not {self.ra_doppler!r}')
-        if not _lib.RA_MIN_LOADING <= float(self.ra_loading) <= 1.0:
-            raise ValueError(f'ra_loading must lie in [{_lib.RA_MIN_LOADING}, 1], not {self.ra_loading!r}')
-        if self.ra_map is not None and not 2 <= int(self.num_antennas) <= _lib.RA_MAX_A:
-            raise ValueError(f'ra_map needs 2 to {_lib.RA_MAX_A} antennas, not {self.num_antennas}')
-        if self.ss_len is not None and not 2 <= int(self.ss_len) <= _lib.SS_MAX_L:
-            raise ValueError(f'ss_len must lie in [2, {_lib.SS_MAX_L}], not {self.ss_len!r}')
-        if int(self.ss_max) < 1:
-            raise ValueError(f'ss_max must be >= 1, not {self.ss_max!r}')
-        if not 0 <= int(self.ss_sources) <= int(self.ss_max):
-            raise ValueError(f'ss_sources must lie in [0, ss_max], not {self.ss_sources!r}')
-        if not 0.0 < float(self.ss_rel) < 1.0:
-            raise ValueError(f'ss_rel must lie in (0, 1), not {self.ss_rel!r}')
-        if self.multi_source:
-            A = int(self.num_antennas)
-            if not 3 <= A <= 16:
-                raise ValueError(f'multi_source needs 3 to 16 antennas, not {A}')
-            L = self.ss_sub_len
-            if L > A:
-                raise ValueError(f'ss_len {L} exceeds the {A} antennas')
-            if int(self.ss_sources) > min(int(self.ss_max), L - 1):
-                raise ValueError(f'ss_sources {self.ss_sources} exceeds the {L - 1} angles a sub-array of {L} resolves')
-        if self.velocity_loss not in ('ls', 'huber', 'tukey', 'consensus'):
-            raise ValueError("velocity_loss must be 'ls', 'huber', 'tukey' or 'consensus', "
-                             f'not {self.velocity_loss!r}')
-        if self.velocity_loss == 'consensus':
-            if self.velocity_scale is None or not float(self.velocity_scale) > 0.0:
-                raise ValueError("velocity_loss='consensus' needs velocity_scale > 0, the phase-noise sigma in radians")
-            if not 1 <= int(self.velocity_hyps) <= _lib.CONSENSUS_MAX_H:
-                raise ValueError(f'velocity_hyps must lie in [1, {_lib.CONSENSUS_MAX_H}], not {self.velocity_hyps!r}')
-            if not 0.0 < float(self.velocity_min_det) <= 1.0:
-                raise ValueError(f'velocity_min_det must lie in (0, 1], not {self.velocity_min_det!r}')
-            if not 0 <= int(self.velocity_refine) <= 100:
-                raise ValueError(f'velocity_refine must lie in [0, 100], not {self.velocity_refine!r}')
-        if self.detector not in ('threshold', 'cfar'):
-            raise ValueError(f"detector must be 'threshold' or 'cfar', not {self.detector!r}")
-        if self.detect_on not in ('antenna', 'sum'):
-            raise ValueError(f"detect_on must be 'antenna' or 'sum', not {self.detect_on!r}")
-        if self.detect_on == 'sum' and not 1 <= int(self.num_antennas) <= 32:
-            raise ValueError(f"detect_on='sum' needs 1 to 32 antennas, not {self.num_antennas}")
-        if self.cfar_method not in tables.CFAR_METHODS:
-            raise ValueError(f"cfar_method must be 'ca' or 'os', not {self.cfar_method!r}")
-        if not 0.0 < float(self.cfar_rank) <= 1.0:
-            raise ValueError(f'cfar_rank must lie in (0, 1], not {self.cfar_rank!r}')
+        # every stage refuses its own settings; the order decides which refusal wins
+        for stage in (Registration, PointCloud, RangeAzimuth, SmoothedMusic, VelocitySolve, Detector):
+            stage.check(self)
 
     @property
     def ss_sub_len(self) -> int:
@@ -214,6 +143,348 @@ class ChainConfig:
     @property
     def lambda_c(self) -> float:
         return C_LIGHT / self.fc
+
+
+# --- the stages -------------------------------------------------------------------------------------------------------
+# A stage is a plain class that owns one step of the chain: check(cfg) is its share of ChainConfig's refusals; its
+# constructor takes the chain, allocates its buffers through chain.alloc (guarded when the chain is) and uploads its
+# tables; launch(**over) makes its Context call with its own keyword arguments, `over` laid on top -- the chain calls
+# launch(), a tool that measures a variant passes only the difference; results(nc) gives its keys of
+# RadarChain.results().  What a stage owns (settings, tables, its buffers: .kw) is bound at construction; the chain's
+# buffers are read from the chain at every launch, as a caller may swap one between runs (bench.py rotates chain.spec).
+
+class Detector:
+    """What decides the peaks after the fused front end (rds_detect, which writes .front), in one of three forms: the
+    front end's own threshold decision stands (.call is None: nothing to launch); 'cfar' rewrites its mask, counts and
+    peak powers per antenna; 'sum' decides once per frame on the antenna-summed map chain.power, by any rule."""
+
+    @staticmethod
+    def check(cfg):
+        if cfg.detector not in ('threshold', 'cfar'):
+            raise ValueError(f"detector must be 'threshold' or 'cfar', not {cfg.detector!r}")
+        if cfg.detect_on not in ('antenna', 'sum'):
+            raise ValueError(f"detect_on must be 'antenna' or 'sum', not {cfg.detect_on!r}")
+        if cfg.detect_on == 'sum' and not 1 <= int(cfg.num_antennas) <= 32:
+            raise ValueError(f"detect_on='sum' needs 1 to 32 antennas, not {cfg.num_antennas}")
+        if cfg.cfar_method not in tables.CFAR_METHODS:
+            raise ValueError(f"cfar_method must be 'ca' or 'os', not {cfg.cfar_method!r}")
+        if not 0.0 < float(cfg.cfar_rank) <= 1.0:
+            raise ValueError(f'cfar_rank must lie in (0, 1], not {cfg.cfar_rank!r}')
+
+    def __init__(self, ch, front):
+        cfg, F, S, C = ch.cfg, ch.F, ch.S, ch.C
+        self.ch, self.front, self.out, self.call, self.alpha = ch, front, front, None, None
+        if cfg.detector == 'cfar':
+            self.alpha = float(cfg.cfar_alpha) if cfg.cfar_alpha is not None else tables.cfar_design_alpha(
+                cfg.cfar_method, cfg.cfar_pfa, cfg.cfar_guard, cfg.cfar_train, cfg.cfar_rank,
+                looks=cfg.num_antennas if ch.sum else 1)
+        win = dict(guard=cfg.cfar_guard, train=cfg.cfar_train, rank=cfg.cfar_rank, thr_power=ch.thr_p, i_lo=ch.i_lo,
+                   i_hi=ch.i_hi)
+        if ch.sum:
+            # the fused front end still writes its per-antenna outputs; what it wrote is not read, and the detector of
+            # the summed map puts its own (one map per frame) at the start of the same buffers
+            W = front['mask'].shape[-1]
+            self.out = dict(mask=front['mask'].view(-1)[:F * S * W].view(F, 1, S, W),
+                            row_count=front['row_count'].view(-1)[:F * S].view(F, 1, S),
+                            peak_pow=front['peak_pow'].view(-1)[:F * S * C].view(F, 1, S, C))
+            self.call, self.reads = 'detect_power', 'power'  # the launcher, and the chain buffer it decides on
+            self.kw = dict(win, rule='threshold' if cfg.detector == 'threshold' else cfg.cfar_method,
+                           alpha=self.alpha if self.alpha is not None else 1.0, out=self.out)
+        elif cfg.detector == 'cfar':
+            self.call, self.reads = 'detect_cfar', 'rds'
+            self.kw = dict(win, alpha=self.alpha, method=cfg.cfar_method, out=self.out)
+
+    def launch(self, **over):
+        ch = self.ch
+        return getattr(ch.ctx, self.call)(**{self.reads: getattr(ch, self.reads), **self.kw, **over})
+
+
+class FusedDoa:
+    """DoA argmax, ESPRIT and phase from one signature gather (doa_extras): the uniform linear array's path."""
+    spec, spec_contiguous = None, False
+
+    def __init__(self, ch, spec_out=None):
+        self.ch = ch
+        self.kw = dict(steer=ch.steer, method=ch.method, esprit_scale=ch.esprit_scale)
+
+    def launch(self, esprit=True, velocity=True, **over):
+        ch = self.ch
+        ch.ctx.doa_extras(**{**ch.cells(), **self.kw, 'out_idx': ch.gidx,
+                             'esprit': ch.ext['esprit'] if esprit else None,
+                             'phase': ch.ext['phase'] if velocity else None, **over})
+
+
+class ScanDoa:
+    """The steering scan (doa), with the cell-blocked spectrum where cfg.spectrum asks for it, then ESPRIT and phase
+    (cell_extras) where either is wanted."""
+
+    def __init__(self, ch, spec_out=None):
+        ctx, torch = ch.ctx, ch.ctx.torch
+        self.ch, self.spec, self.spec_contiguous = ch, None, False  # spec: as allocated; the chain's is the live one
+        if ch.cfg.spectrum:
+            shp = ch.spectrum_shape()
+            if isinstance(spec_out, str):
+                if spec_out != 'contiguous':
+                    raise ValueError("spec_out: a tensor, 'contiguous' or None")
+                spec_out = ctx.empty_contiguous(shp, torch.float32)  # None: the driver could not provide it
+                self.spec_contiguous = spec_out is not None
+            if spec_out is not None:
+                if tuple(spec_out.shape) != shp or spec_out.dtype != torch.float32 or not spec_out.is_contiguous():
+                    raise ValueError(f'spec_out must be a contiguous float32 tensor of shape {shp}')
+                self.spec = spec_out
+            else:
+                self.spec = ch.alloc(shp, torch.float32)
+        self.kw = dict(steer=ch.steer, method=ch.method, spec_blocked=True)
+
+    def launch(self, esprit=True, velocity=True, **over):
+        ch = self.ch
+        cells = ch.cells()
+        ch.ctx.doa(**{**cells, **self.kw, 'out_idx': ch.gidx, 'want_spec': ch.spec is not None, 'out_spec': ch.spec,
+                      **over})
+        if esprit or velocity:
+            ch.ctx.cell_extras(**cells, esprit_scale=ch.esprit_scale, want_esprit=esprit, want_phase=velocity,
+                               bufs=ch.ext)
+
+
+class SmoothedMusic:
+    """cfg.multi_source: the spatially smoothed MUSIC (doa_smoothed) on the chain's cell lists, up to nmax angles per
+    cell in its own outputs."""
+
+    @staticmethod
+    def check(cfg):
+        if cfg.ss_len is not None and not 2 <= int(cfg.ss_len) <= _lib.SS_MAX_L:
+            raise ValueError(f'ss_len must lie in [2, {_lib.SS_MAX_L}], not {cfg.ss_len!r}')
+        if int(cfg.ss_max) < 1:
+            raise ValueError(f'ss_max must be >= 1, not {cfg.ss_max!r}')
+        if not 0 <= int(cfg.ss_sources) <= int(cfg.ss_max):
+            raise ValueError(f'ss_sources must lie in [0, ss_max], not {cfg.ss_sources!r}')
+        if not 0.0 < float(cfg.ss_rel) < 1.0:
+            raise ValueError(f'ss_rel must lie in (0, 1), not {cfg.ss_rel!r}')
+        if cfg.multi_source:
+            A = int(cfg.num_antennas)
+            if not 3 <= A <= 16:
+                raise ValueError(f'multi_source needs 3 to 16 antennas, not {A}')
+            L = cfg.ss_sub_len
+            if L > A:
+                raise ValueError(f'ss_len {L} exceeds the {A} antennas')
+            if int(cfg.ss_sources) > min(int(cfg.ss_max), L - 1):
+                raise ValueError(f'ss_sources {cfg.ss_sources} exceeds the {L - 1} angles a sub-array of {L} resolves')
+
+    def __init__(self, ch):
+        cfg, e, torch, cc, L = ch.cfg, ch.alloc, ch.ctx.torch, ch.cell_cap, ch.cfg.ss_sub_len
+        self.ch = ch
+        self.nmax = min(int(cfg.ss_max), L - 1)
+        self.steer = ch.ctx.steering_sub(ch.steer_c128, L)
+        self.out = dict(nsrc=e((cc,), torch.int32), idx=e((cc, self.nmax), torch.int32),
+                        den=e((cc, self.nmax), torch.float32))
+        self.kw = dict(steer_sub=self.steer, nmax=self.nmax, num_sources=cfg.ss_sources, rel=cfg.ss_rel, out=self.out)
+
+    def launch(self, **over):
+        return self.ch.ctx.doa_smoothed(**{**self.ch.cells(), **self.kw, **over})
+
+    def results(self, nc):
+        o = self.out
+        return dict(ss_nsrc=o['nsrc'][:nc].cpu().numpy(), ss_gidx=o['idx'][:nc].cpu().numpy().astype(np.int64),
+                    ss_den=o['den'][:nc].cpu().numpy().astype(np.float64))
+
+
+class RangeAzimuth:
+    """cfg.ra_map: every range bin's spatial covariance over its Doppler window (cov(): range_cov), then its Bartlett
+    or Capon power over the chain's grid (launch(): range_azimuth on that covariance)."""
+
+    @staticmethod
+    def check(cfg):
+        if cfg.ra_map is not None and cfg.ra_map not in _lib.RA_IDS:
+            raise ValueError(f"ra_map must be None, 'bartlett' or 'capon', not {cfg.ra_map!r}")
+        if cfg.ra_doppler is not None:
+            if len(tuple(cfg.ra_doppler)) != 2 or not (0 <= int(cfg.ra_doppler[0]) < int(cfg.ra_doppler[1])
+                                                       <= int(cfg.num_chirps)):
+                raise ValueError(f'ra_doppler must be (c0, c1) with 0 <= c0 < c1 <= {int(cfg.num_chirps)}, '
+                                 f'not {cfg.ra_doppler!r}')
+        if not _lib.RA_MIN_LOADING <= float(cfg.ra_loading) <= 1.0:
+            raise ValueError(f'ra_loading must lie in [{_lib.RA_MIN_LOADING}, 1], not {cfg.ra_loading!r}')
+        if cfg.ra_map is not None and not 2 <= int(cfg.num_antennas) <= _lib.RA_MAX_A:
+            raise ValueError(f'ra_map needs 2 to {_lib.RA_MAX_A} antennas, not {cfg.num_antennas}')
+
+    def __init__(self, ch):
+        cfg, e, torch, F, A, S = ch.cfg, ch.alloc, ch.ctx.torch, ch.F, ch.A, ch.S
+        self.ch = ch
+        self.steer = ch.ctx.steering_c64(ch.steer_c128)
+        self.win = (0, ch.C) if cfg.ra_doppler is None else (int(cfg.ra_doppler[0]), int(cfg.ra_doppler[1]))
+        self.cov_out = e((F, S, A, A), torch.complex64)
+        self.out = dict(map=e((F, S, len(ch.grid)), torch.float32), arg=e((F, S), torch.int32))
+        self.kw = dict(cov=self.cov_out, steer_c64=self.steer, method=cfg.ra_map, loading=cfg.ra_loading, out=self.out)
+
+    def cov(self, **over):
+        return self.ch.ctx.range_cov(**{'rds': self.ch.rds, 'doppler': self.win, 'out': self.cov_out, **over})
+
+    def launch(self, with_cov=True, **over):
+        """with_cov=False: the map alone, on the covariance as it stands."""
+        if with_cov:
+            self.cov()
+        return self.ch.ctx.range_azimuth(**{**self.kw, **over})
+
+    def results(self, nc):  # f32 [F, S, G] and i32 [F, S]: every range bin of every frame
+        return dict(ra_map=self.out['map'].cpu().numpy(), ra_arg=self.out['arg'].cpu().numpy())
+
+
+class PowerSum:
+    """The antenna-summed power map chain.power (integrate_power): what the 'sum' detector decides on and what the
+    point cloud refines on, integrated once per run, before whichever comes first."""
+
+    def __init__(self, ch):
+        self.ch = ch
+        self.out = ch.alloc((ch.F, ch.S, ch.C), ch.ctx.torch.float32)
+
+    def launch(self, **over):
+        return self.ch.ctx.integrate_power(**{'rds': self.ch.rds, 'out': self.ch.power, **over})
+
+
+class PointCloud:
+    """cfg.point_cloud: one row and one refined azimuth per cell (cell_refine, after the DoA scan), from the
+    antenna-summed power map chain.power."""
+
+    @staticmethod
+    def check(cfg):
+        if cfg.velocity_az not in ('grid', 'refined'):
+            raise ValueError(f"velocity_az must be 'grid' or 'refined', not {cfg.velocity_az!r}")
+        if cfg.velocity_az == 'refined' and not cfg.point_cloud:
+            raise ValueError("velocity_az='refined' needs point_cloud=True")
+        if cfg.point_cloud:
+            if not 2 <= int(cfg.num_antennas) <= 32:
+                raise ValueError(f'point_cloud needs 2 to 32 antennas, not {cfg.num_antennas}')
+            tables.refine_mode_for_window(cfg.window_type)  # ValueError for a window without an estimator
+
+    def __init__(self, ch):
+        cfg, e, torch, cc = ch.cfg, ch.alloc, ch.ctx.torch, ch.cell_cap
+        self.ch = ch
+        self.steer = ch.ctx.steering_c64(ch.steer_c128)
+        self.modes = (tables.refine_mode_for_window(cfg.window_type), 'rect')
+        self.axes = tables.point_axes(cfg, ch.S, ch.C, velocity=cfg.pc_velocity)
+        self.out = dict(points=e((cc, 8), torch.float32), az=e((cc,), torch.float64))
+        self.kw = dict(az_table=ch.az_table, steer_c64=self.steer, range_mode=self.modes[0],
+                       doppler_mode=self.modes[1], axes=self.axes, out=self.out)
+
+    def launch(self, **over):
+        ch = self.ch
+        return ch.ctx.cell_refine(**{**ch.cells(), 'gidx': ch.gidx, 'power': ch.power, **self.kw, **over})
+
+    def results(self, nc):
+        return dict(points=self.out['points'][:nc].cpu().numpy(), az_refined=self.out['az'][:nc].cpu().numpy())
+
+
+class VelocitySolve:
+    """The ego-velocity solve: one of the three solvers on the one problem they share, the chain's own lists, with
+    the azimuths of the grid (az_table[gidx]) or the point cloud's refined ones."""
+
+    @staticmethod
+    def check(cfg):
+        if cfg.velocity_loss not in ('ls', 'huber', 'tukey', 'consensus'):
+            raise ValueError("velocity_loss must be 'ls', 'huber', 'tukey' or 'consensus', "
+                             f'not {cfg.velocity_loss!r}')
+        if cfg.velocity_loss == 'consensus':
+            if cfg.velocity_scale is None or not float(cfg.velocity_scale) > 0.0:
+                raise ValueError("velocity_loss='consensus' needs velocity_scale > 0, the phase-noise sigma in radians")
+            if not 1 <= int(cfg.velocity_hyps) <= _lib.CONSENSUS_MAX_H:
+                raise ValueError(f'velocity_hyps must lie in [1, {_lib.CONSENSUS_MAX_H}], not {cfg.velocity_hyps!r}')
+            if not 0.0 < float(cfg.velocity_min_det) <= 1.0:
+                raise ValueError(f'velocity_min_det must lie in (0, 1], not {cfg.velocity_min_det!r}')
+            if not 0 <= int(cfg.velocity_refine) <= 100:
+                raise ValueError(f'velocity_refine must lie in [0, 100], not {cfg.velocity_refine!r}')
+
+    def __init__(self, ch):
+        cfg, loss = ch.cfg, ch.cfg.velocity_loss
+        self.ch = ch
+        # IRLS weight of every cell ('consensus': the inlier mask)
+        self.weight = ch.alloc((ch.cell_cap,), ch.ctx.torch.float32) if loss != 'ls' else None
+        prob = dict(k=ch.k, ridge=cfg.ridge, bounds=cfg.bounds, n=ch.cell_cap)
+        if cfg.velocity_az == 'refined':  # the point cloud's azimuths in place of the grid's
+            prob.update(az=ch.pc.out['az'], gidx=None, az_table=None)
+        if loss == 'consensus':
+            # vel columns 2-7 become {cost, rmse_in, n_in, n, best_h, n_valid} (include/rsl.h)
+            self.call = 'velocity_consensus'
+            prob.update(scale=cfg.velocity_scale, c=cfg.velocity_c, hyps=cfg.velocity_hyps, seed=cfg.velocity_seed,
+                        min_det=cfg.velocity_min_det, refine=cfg.velocity_refine, frame0=0, want_weight=self.weight)
+        elif loss != 'ls':
+            # vel columns 2-7 become {cost, rmse_w, n_in, n, sigma, it} (include/rsl.h)
+            self.call = 'velocity_robust'
+            prob.update(loss=loss, c=cfg.velocity_c, scale=cfg.velocity_scale, iters=cfg.velocity_iters,
+                        tol=cfg.velocity_tol, want_weight=self.weight)
+        else:
+            self.call = 'velocity'
+        self.kw = prob
+
+    def launch(self, **over):
+        ch = self.ch  # the chain's own lists, on the grid-index path unless .kw says otherwise
+        return getattr(ch.ctx, self.call)(**{
+            'az': None, 'gidx': ch.gidx, 'az_table': ch.az_table, 'y': ch.ext['phase'], 'seg': ch.offs['cell_base'],
+            'amask': ch.lists['c_amask'], 'out': ch.vel, **self.kw, **over})
+
+    def results(self, nc):
+        return dict(vel_weight=self.weight[:nc].cpu().numpy()) if self.weight is not None else {}
+
+
+class Registration:
+    """cfg.registration: every frame's point cloud against the frame before it (scan_register, after the velocity
+    solve), from the start (0, v_x dt, v_y dt) of the velocity rows; the batch's last frame is kept as the next run's
+    reference (.prev: None until a run has filled .keep)."""
+
+    @staticmethod
+    def check(cfg):
+        if not cfg.registration:
+            return
+        if not cfg.point_cloud:
+            raise ValueError('registration=True needs point_cloud=True')
+        pos = lambda v: math.isfinite(float(v)) and float(v) > 0.0
+        if not (pos(cfg.reg_h) and pos(cfg.reg_h_coarse) and pos(cfg.reg_dtheta) and pos(cfg.dt)):
+            raise ValueError('registration needs reg_h, reg_h_coarse, reg_dtheta and dt finite and > 0')
+        if float(cfg.reg_h_coarse) < float(cfg.reg_h):
+            raise ValueError(f'reg_h_coarse {cfg.reg_h_coarse!r} is below reg_h {cfg.reg_h!r}')
+        if not 0 <= int(cfg.reg_k) <= _lib.REG_MAX_K:
+            raise ValueError(f'reg_k must lie in [0, {_lib.REG_MAX_K}], not {cfg.reg_k!r}')
+        if not 0 <= int(cfg.reg_iters) <= _lib.REG_MAX_ITERS:
+            raise ValueError(f'reg_iters must lie in [0, {_lib.REG_MAX_ITERS}], not {cfg.reg_iters!r}')
+        if not 0.0 < float(cfg.reg_shrink) <= 1.0:
+            raise ValueError(f'reg_shrink must lie in (0, 1], not {cfg.reg_shrink!r}')
+        if not (math.isfinite(float(cfg.reg_w_min)) and float(cfg.reg_w_min) >= 0.0):
+            raise ValueError(f'reg_w_min must be finite and >= 0, not {cfg.reg_w_min!r}')
+
+    def __init__(self, ch):
+        cfg, e, torch, F = ch.cfg, ch.alloc, ch.ctx.torch, ch.F
+        fc = ch.S * ch.C  # the most cells of one frame
+        self.ch = ch
+        self.out = dict(rows=e((F, 8), torch.float64), omega=e((F, 3), torch.float64))
+        self.init = e((F, 3), torch.float64)
+        self.keep = dict(points=e((fc, 8), torch.float32), rc=e((fc,), torch.int32), n_dev=e((1,), torch.int64),
+                         weight=e((fc,), torch.float32) if ch.vel_weight is not None else None)
+        self.prev = None
+        self.idx = torch.arange(fc, dtype=torch.int64, device=ch.ctx.device)
+        self.kw = dict(points=ch.pc.out['points'], C=ch.C, axes=ch.pc.axes, init=self.init, h=cfg.reg_h,
+                       h_coarse=cfg.reg_h_coarse, dtheta=cfg.reg_dtheta, k=cfg.reg_k, iters=cfg.reg_iters,
+                       shrink=cfg.reg_shrink, tol=cfg.reg_tol, w_min=cfg.reg_w_min, dt=cfg.dt, n=ch.cell_cap,
+                       out=self.out)
+
+    def launch(self, **over):
+        """The start from the velocity rows, the registration of the batch (prev: the kept cloud unless `over` says
+        otherwise), then the batch's last frame into .keep."""
+        ch, keep, torch = self.ch, self.keep, self.ch.ctx.torch
+        points, seg, rc, weight = self.kw['points'], ch.offs['cell_base'], ch.lists['c_rc'], ch.vel_weight
+        self.init[:, 0] = 0.0
+        torch.mul(ch.vel[:, :2], float(ch.cfg.dt), out=self.init[:, 1:])  # the Doppler displacement v dt
+        ch.ctx.scan_register(**{'seg': seg, 'weight': weight, 'rc': rc, 'prev': self.prev, **self.kw, **over})
+        # the last frame's rows, by device-side indices (no host synchronisation): rows past the frame's end are
+        # copies of the list's last slot and lie beyond n_dev
+        base = seg.clamp(0, ch.cell_cap)
+        idx = (self.idx + base[ch.F - 1]).clamp_(max=ch.cell_cap - 1)
+        torch.index_select(points, 0, idx, out=keep['points'])
+        torch.index_select(rc, 0, idx, out=keep['rc'])
+        if keep['weight'] is not None:
+            torch.index_select(weight, 0, idx, out=keep['weight'])
+        torch.sub(base[ch.F:ch.F + 1], base[ch.F - 1:ch.F], out=keep['n_dev'])
+        self.prev = keep
+
+    def results(self, nc):
+        return dict(registration=self.out['rows'].cpu().numpy())
 
 
 GUARD_BYTES = 256 * 1024  # sentinel pad on each side of a guarded buffer (RadarChain(guard=True))
@@ -241,15 +512,10 @@ class RadarChain:
         self.table = ctx.to_dev(tab.astype(np.complex64))
         self.i_lo, self.i_hi = tables.range_gate(cfg.bandwidth, S, cfg.min_range, cfg.max_range)
         self.thr_p = tables.power_threshold(cfg.threshold_db)
-        self.cfar_alpha = None
-        if cfg.detector == 'cfar':
-            self.cfar_alpha = float(cfg.cfar_alpha) if cfg.cfar_alpha is not None else tables.cfar_design_alpha(
-                cfg.cfar_method, cfg.cfar_pfa, cfg.cfar_guard, cfg.cfar_train, cfg.cfar_rank,
-                looks=cfg.num_antennas if cfg.detect_on == 'sum' else 1)
         d = cfg.antenna_spacing or cfg.lambda_c / 2
         self.grid = tables.azimuth_grid(cfg.search_range, cfg.search_resolution)
-        steer_c128 = tables.steering_matrix(self.grid, np.arange(A) * d, cfg.lambda_c)
-        self.steer = ctx.steering(steer_c128)
+        self.steer_c128 = tables.steering_matrix(self.grid, np.arange(A) * d, cfg.lambda_c)  # host; the stages' tables
+        self.steer = ctx.steering(self.steer_c128)
         self.az_table = ctx.to_dev(np.radians(self.grid).astype(np.float64))
         self.esprit_scale = cfg.lambda_c / (2 * np.pi * d)
         lam_v = cfg.velocity_lambda or cfg.lambda_c
@@ -259,22 +525,18 @@ class RadarChain:
         DA = 1 if self.sum else A  # antenna maps the detector decides on per frame
         self.entry_cap = int(math.ceil(cfg.entry_frac * F * DA * S * C)) + 64
         self.cell_cap = (int(math.ceil(cfg.cell_frac * F * S * C)) + 64 + 3) & ~3  # a multiple of 4 (16-B rows)
-        e = self._guarded_empty if guard else ctx.empty
+        e = self.alloc = self._guarded_empty if guard else ctx.empty  # the stages allocate through it too
         W = (C + 63) // 64
         self.work = e((F, A, C, S), torch.complex64)
         self.rds = e((F, A, S, C), torch.complex64)
-        self.mask = e((F, A, S, W), torch.int64)
-        self.row_count = e((F, A, S), torch.int32)
-        self.peak_pow = e((F, A, S, C), torch.float32)  # row-compact peak powers (detect -> emit)
-        self.power = None
-        if self.sum:
-            # the fused front end still writes its per-antenna outputs; what it wrote is not read, and the detector of
-            # the summed map puts its own (one map per frame) at the start of the same buffers
-            self.power = e((F, S, C), torch.float32)  # the antenna-summed map (the integrated range-Doppler map)
-            self._front = dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow)
-            self.mask = self.mask.view(-1)[:F * S * W].view(F, 1, S, W)
-            self.row_count = self.row_count.view(-1)[:F * S].view(F, 1, S)
-            self.peak_pow = self.peak_pow.view(-1)[:F * S * C].view(F, 1, S, C)
+        # mask, per-row counts and row-compact peak powers (detect -> emit): rds_detect's, then the detector's
+        front = dict(mask=e((F, A, S, W), torch.int64), row_count=e((F, A, S), torch.int32),
+                     peak_pow=e((F, A, S, C), torch.float32))
+        integrate = PowerSum(self) if self.sum or cfg.point_cloud else None
+        self.power = integrate.out if integrate is not None else None
+        self.det = Detector(self, front)
+        self.mask, self.row_count, self.peak_pow = (self.det.out[k] for k in ('mask', 'row_count', 'peak_pow'))
+        self.cfar_alpha = self.det.alpha
         self.offs = dict(entry_row_off=e((F * DA * S,), torch.int32), cell_row_off=e((F * S,), torch.int32),
                          scratch=e((F * S,), torch.int32), entry_base=e((F + 1,), torch.int64),
                          cell_base=e((F + 1,), torch.int64), frame_counts=e((2 * F,), torch.int64),
@@ -285,58 +547,28 @@ class RadarChain:
         self.gidx = e((cc,), torch.int32)
         self.ext = dict(esprit=e((cc,), torch.float64), phase=e((cc,), torch.float64), az=e((cc,), torch.float64))
         self.vel = vel_out if vel_out is not None else e((F, 8), torch.float64)
-        # IRLS weight of every cell ('consensus': the inlier mask)
-        self.vel_weight = e((cc,), torch.float32) if cfg.velocity_loss != 'ls' else None
         self.ncell_dev = self.offs['cell_base'][F:F + 1]
-        self.ss = None
-        if cfg.multi_source:  # smoothed MUSIC: its own outputs on the same cell lists
-            L = cfg.ss_sub_len
-            self.ss_nmax = min(int(cfg.ss_max), L - 1)
-            self.ss_steer = ctx.steering_sub(steer_c128, L)
-            self.ss = dict(nsrc=e((cc,), torch.int32), idx=e((cc, self.ss_nmax), torch.int32),
-                           den=e((cc, self.ss_nmax), torch.float32))
-        self.ra = None
-        if cfg.ra_map is not None:  # range-azimuth map: per-range covariance, then its power over the grid
-            self.ra_steer = ctx.steering_c64(steer_c128)
-            self.ra_win = (0, C) if cfg.ra_doppler is None else (int(cfg.ra_doppler[0]), int(cfg.ra_doppler[1]))
-            self.ra_cov = e((F, S, A, A), torch.complex64)
-            self.ra = dict(map=e((F, S, len(self.grid)), torch.float32), arg=e((F, S), torch.int32))
-        self.pc = None
-        if cfg.point_cloud:  # point cloud: one row and one refined azimuth per cell, from the antenna-summed power
-            self.pc_steer = ctx.steering_c64(steer_c128)
-            self.pc_modes = (tables.refine_mode_for_window(cfg.window_type), 'rect')
-            self.pc_axes = tables.point_axes(cfg, S, C, velocity=cfg.pc_velocity)
-            if self.power is None:  # detect_on='antenna': no summed map yet, run_back integrates it
-                self.power = e((F, S, C), torch.float32)
-            self.pc = dict(points=e((cc, 8), torch.float32), az=e((cc,), torch.float64))
-        self.reg = None
-        self.omega = None
-        if cfg.registration:  # scan registration: one row per frame, and the last frame's cloud kept for the next run
-            fc = S * C  # the most cells of one frame
-            self.reg = dict(rows=e((F, 8), torch.float64), omega=e((F, 3), torch.float64))
-            self.omega = self.reg['omega']
-            self.reg_init = e((F, 3), torch.float64)
-            self.reg_keep = dict(points=e((fc, 8), torch.float32), rc=e((fc,), torch.int32), n_dev=e((1,), torch.int64),
-                                 weight=e((fc,), torch.float32) if self.vel_weight is not None else None)
-            self.reg_prev = None  # reg_keep once a run has filled it
-            self.reg_idx = torch.arange(fc, dtype=torch.int64, device=ctx.device)
-        # one signature gather for DoA + ESPRIT + phase when the Toeplitz path applies (uniform linear array)
+        # the stages, in launch order.  One signature gather for DoA + ESPRIT + phase when the Toeplitz path applies
+        # (uniform linear array)
         self.fused_doa = bool(self.steer['toeplitz']) and A >= 2 and not cfg.spectrum
-        self.spec = None
-        self.spec_contiguous = False
-        if cfg.spectrum:
-            shp = self.spectrum_shape()
-            if isinstance(spec_out, str):
-                if spec_out != 'contiguous':
-                    raise ValueError("spec_out: a tensor, 'contiguous' or None")
-                spec_out = ctx.empty_contiguous(shp, torch.float32)  # None: the driver could not provide it
-                self.spec_contiguous = spec_out is not None
-            if spec_out is not None:
-                if tuple(spec_out.shape) != shp or spec_out.dtype != torch.float32 or not spec_out.is_contiguous():
-                    raise ValueError(f'spec_out must be a contiguous float32 tensor of shape {shp}')
-                self.spec = spec_out
-            else:
-                self.spec = e(shp, torch.float32)
+        self.doa = (FusedDoa if self.fused_doa else ScanDoa)(self, spec_out)
+        self.spec, self.spec_contiguous = self.doa.spec, self.doa.spec_contiguous
+        self.ss = SmoothedMusic(self) if cfg.multi_source else None
+        self.ra = RangeAzimuth(self) if cfg.ra_map is not None else None
+        self.pc = PointCloud(self) if cfg.point_cloud else None
+        self.solve = VelocitySolve(self)
+        self.vel_weight = self.solve.weight
+        self.reg = Registration(self) if cfg.registration else None
+        self.omega = self.reg.out['omega'] if self.reg is not None else None
+        on = lambda *stages: [st for st in stages if st is not None]
+        self.detect = on(integrate if self.sum else None, self.det if self.det.call else None)
+        self.before_solve = on(self.ss, self.ra, None if self.sum else integrate, self.pc)
+        self.after_solve = on(self.reg)
+
+    def cells(self):
+        """What every per-cell launch reads: the RDS, the cell lists, their capacity and true size (on the device)."""
+        L = self.lists
+        return dict(rds=self.rds, c_frame=L['c_frame'], c_rc=L['c_rc'], n=self.cell_cap, n_dev=self.ncell_dev)
 
     def spectrum_shape(self):
         """Shape of the cell-blocked spectrum buffer: [ceil(cell_cap / 32), G, 32] f32."""
@@ -367,32 +599,22 @@ class RadarChain:
         self.run_front(cube)
         self.run_back(esprit=esprit, velocity=velocity)
 
+    def _offsets(self):
+        self.ctx.offsets(self.mask, self.row_count, self.C, bufs=self.offs)
+
     def run_front(self, cube, *, emit: bool = True, offsets: bool = True):
         """Memory-bound half: RDS + detection, offsets, peak / cell compaction (current stream). With emit=False the
         compaction is left to run_back(emit=True) (a pipelining split of the same work)."""
-        ctx, cfg = self.ctx, self.cfg
         if self.F == 0:  # empty batch: only the (zeroed) bases
-            ctx.offsets(self.mask, self.row_count, self.C, bufs=self.offs)
+            self._offsets()
             return
-        front = self._front if self.sum else dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow)
-        group = ctx.rds_detect(cube, self.table, self.thr_p, self.i_lo, self.i_hi, rds=self.rds, work=self.work,
-                               dc_removal=cfg.dc_removal, **front)
-        self._group = group
-        if self.sum:  # one decision per cell, on the antenna-summed power
-            out = dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow)
-            ctx.integrate_power(self.rds, out=self.power)
-            ctx.detect_power(self.power, 'threshold' if cfg.detector == 'threshold' else cfg.cfar_method,
-                             cfg.cfar_guard, cfg.cfar_train, cfg.cfar_rank,
-                             self.cfar_alpha if self.cfar_alpha is not None else 1.0, self.thr_p, self.i_lo,
-                             self.i_hi, out=out)
-            self._group = 1
-        elif cfg.detector == 'cfar':  # the CFAR detector rewrites the fused detector's mask, counts and peak powers
-            out = dict(mask=self.mask, row_count=self.row_count, peak_pow=self.peak_pow)
-            ctx.detect_cfar(self.rds, cfg.cfar_guard, cfg.cfar_train, self.cfar_alpha, self.thr_p, self.i_lo,
-                            self.i_hi, out=out, method=cfg.cfar_method, rank=cfg.cfar_rank)
-            self._group = 1
+        group = self.ctx.rds_detect(cube, self.table, self.thr_p, self.i_lo, self.i_hi, rds=self.rds, work=self.work,
+                                    dc_removal=self.cfg.dc_removal, **self.det.front)
+        for st in self.detect:
+            st.launch()
+        self._group = 1 if self.detect else group  # peak_pow's row grouping: 1 once a detector has rewritten it
         if offsets:
-            ctx.offsets(self.mask, self.row_count, self.C, bufs=self.offs)
+            self._offsets()
         if emit:
             self._emit()
 
@@ -401,89 +623,27 @@ class RadarChain:
                       peak_pow=self.peak_pow, peak_pow_group=self._group)
 
     def run_back(self, *, esprit: bool = True, velocity: bool = True, emit: bool = False, offsets: bool = False):
-        """Compute-bound half: DoA scan (+ ESPRIT, phase) and the velocity solve, on run_front's lists (emit=True:
-        the compaction first, after run_front(emit=False))."""
-        ctx, cfg = self.ctx, self.cfg
-        L = self.lists
+        """Compute-bound half: DoA scan (+ ESPRIT, phase), the optional stages and the velocity solve, on run_front's
+        lists (emit=True: the compaction first, after run_front(emit=False))."""
         if self.F == 0:
             return
         if offsets:
-            ctx.offsets(self.mask, self.row_count, self.C, bufs=self.offs)
+            self._offsets()
         if emit:
             self._emit()
-        if self.fused_doa:
-            ctx.doa_extras(self.rds, L['c_frame'], L['c_rc'], self.steer, self.method, n=self.cell_cap,
-                           n_dev=self.ncell_dev, esprit_scale=self.esprit_scale, out_idx=self.gidx,
-                           esprit=self.ext['esprit'] if esprit else None, phase=self.ext['phase'] if velocity else None)
-        else:
-            ctx.doa(self.rds, L['c_frame'], L['c_rc'], self.steer, self.method, n=self.cell_cap,
-                    n_dev=self.ncell_dev, out_idx=self.gidx, want_spec=self.spec is not None, spec_blocked=True,
-                    out_spec=self.spec)
-            if esprit or velocity:
-                ctx.cell_extras(self.rds, L['c_frame'], L['c_rc'], n=self.cell_cap, n_dev=self.ncell_dev,
-                                esprit_scale=self.esprit_scale, want_esprit=esprit, want_phase=velocity,
-                                bufs=self.ext)
-        if self.ss is not None:
-            ctx.doa_smoothed(self.rds, L['c_frame'], L['c_rc'], self.ss_steer, n=self.cell_cap, n_dev=self.ncell_dev,
-                             nmax=self.ss_nmax, num_sources=cfg.ss_sources, rel=cfg.ss_rel, out=self.ss)
-        if self.ra is not None:
-            ctx.range_cov(self.rds, self.ra_win, out=self.ra_cov)
-            ctx.range_azimuth(self.ra_cov, self.ra_steer, cfg.ra_map, loading=cfg.ra_loading, out=self.ra)
-        if self.pc is not None:
-            if not self.sum:
-                ctx.integrate_power(self.rds, out=self.power)
-            ctx.cell_refine(self.rds, L['c_frame'], L['c_rc'], self.gidx, self.az_table, self.pc_steer,
-                            n=self.cell_cap, n_dev=self.ncell_dev, power=self.power, range_mode=self.pc_modes[0],
-                            doppler_mode=self.pc_modes[1], axes=self.pc_axes, out=self.pc)
+        self.doa.launch(esprit=esprit, velocity=velocity)
+        for st in self.before_solve:
+            st.launch()
         if not velocity:
             return
-        # the problem the three solvers share: the chain's own lists, on the grid-index path
-        prob = dict(az=None, y=self.ext['phase'], seg=self.offs['cell_base'], k=self.k, ridge=cfg.ridge,
-                    bounds=cfg.bounds, amask=L['c_amask'], out=self.vel, gidx=self.gidx, az_table=self.az_table,
-                    n=self.cell_cap)
-        if cfg.velocity_az == 'refined':  # the point cloud's azimuths in place of the grid's
-            prob.update(az=self.pc['az'], gidx=None, az_table=None)
-        if cfg.velocity_loss == 'consensus':
-            # vel columns 2-7 become {cost, rmse_in, n_in, n, best_h, n_valid} (include/rsl.h)
-            ctx.velocity_consensus(**prob, scale=cfg.velocity_scale, c=cfg.velocity_c, hyps=cfg.velocity_hyps,
-                                   min_det=cfg.velocity_min_det, refine=cfg.velocity_refine, seed=cfg.velocity_seed,
-                                   frame0=0, want_weight=self.vel_weight)
-        elif cfg.velocity_loss != 'ls':
-            # vel columns 2-7 become {cost, rmse_w, n_in, n, sigma, it} (include/rsl.h)
-            ctx.velocity_robust(**prob, loss=cfg.velocity_loss, c=cfg.velocity_c, scale=cfg.velocity_scale,
-                                iters=cfg.velocity_iters, tol=cfg.velocity_tol, want_weight=self.vel_weight)
-        else:
-            ctx.velocity(**prob)
-        if self.reg is not None:
-            self._register()
-
-    def _register(self):
-        """Scan registration of the batch (after the velocity solve), then the batch's last frame into reg_keep."""
-        ctx, cfg, torch = self.ctx, self.cfg, self.ctx.torch
-        init = self.reg_init
-        init[:, 0] = 0.0
-        torch.mul(self.vel[:, :2], float(cfg.dt), out=init[:, 1:])  # the Doppler displacement v dt
-        ctx.scan_register(self.pc['points'], self.offs['cell_base'], weight=self.vel_weight, rc=self.lists['c_rc'],
-                          C=self.C, axes=self.pc_axes, prev=self.reg_prev, init=init, h=cfg.reg_h,
-                          h_coarse=cfg.reg_h_coarse, dtheta=cfg.reg_dtheta, k=cfg.reg_k, iters=cfg.reg_iters,
-                          shrink=cfg.reg_shrink, tol=cfg.reg_tol, w_min=cfg.reg_w_min, dt=cfg.dt, n=self.cell_cap,
-                          out=self.reg)
-        # the last frame's rows, by device-side indices (no host synchronisation): rows past the frame's end are
-        # copies of the list's last slot and lie beyond n_dev
-        base = self.offs['cell_base'].clamp(0, self.cell_cap)
-        keep = self.reg_keep
-        idx = (self.reg_idx + base[self.F - 1]).clamp_(max=self.cell_cap - 1)
-        torch.index_select(self.pc['points'], 0, idx, out=keep['points'])
-        torch.index_select(self.lists['c_rc'], 0, idx, out=keep['rc'])
-        if keep['weight'] is not None:
-            torch.index_select(self.vel_weight, 0, idx, out=keep['weight'])
-        torch.sub(base[self.F:self.F + 1], base[self.F - 1:self.F], out=keep['n_dev'])
-        self.reg_prev = keep
+        self.solve.launch()
+        for st in self.after_solve:
+            st.launch()
 
     def reset_registration(self):
         """Forget the cloud kept from the last run: the next run's frame 0 has no reference (flag 2)."""
         if self.reg is not None:
-            self.reg_prev = None
+            self.reg.prev = None
 
     def totals(self):
         eb = self.offs['entry_base'][self.F].item()
@@ -497,16 +657,9 @@ class RadarChain:
             raise RuntimeError(f"peak capacity exceeded: entries {ne}/{self.entry_cap}, cells {nc}/{self.cell_cap}")
         L = self.lists
         h = lambda t, n: t[:n].cpu().numpy()
-        extra = dict(vel_weight=h(self.vel_weight, nc)) if self.vel_weight is not None else {}
-        if self.ss is not None:
-            extra.update(ss_nsrc=h(self.ss['nsrc'], nc), ss_gidx=h(self.ss['idx'], nc).astype(np.int64),
-                         ss_den=h(self.ss['den'], nc).astype(np.float64))
-        if self.ra is not None:  # f32 [F, S, G] and i32 [F, S]: every range bin of every frame
-            extra.update(ra_map=self.ra['map'].cpu().numpy(), ra_arg=self.ra['arg'].cpu().numpy())
-        if self.reg is not None:
-            extra.update(registration=self.reg['rows'].cpu().numpy())
-        if self.pc is not None:
-            extra.update(points=h(self.pc['points'], nc), az_refined=h(self.pc['az'], nc))
+        extra = {}
+        for st in (self.ss, self.ra, self.pc, self.solve, self.reg):
+            extra.update(st.results(nc) if st is not None else {})
         return dict(entry_base=self.offs['entry_base'].cpu().numpy(), cell_base=self.offs['cell_base'].cpu().numpy(),
                     **dict(zip(('e_ant', 'e_rbin', 'e_dbin'), unpack_coord(h(L['e_coord'], ne)))),
                     e_cell=h(L['e_cell'], ne), e_pdb=h(L['e_pdb'], ne).astype(np.float64), c_frame=h(L['c_frame'], nc),

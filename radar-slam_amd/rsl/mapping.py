@@ -89,7 +89,7 @@ class GridMap:
         points, cell_base and cell capacity and, where its velocity solver made one, vel_weight (movers at 0)."""
         if chain.pc is None:
             raise ValueError('GridMap.update_chain needs a chain built with point_cloud=True')
-        return self.update(chain.pc['points'], chain.offs['cell_base'], poses, weight=chain.vel_weight, n=chain.cell_cap)
+        return self.update(chain.pc.out['points'], chain.offs['cell_base'], poses, weight=chain.vel_weight, n=chain.cell_cap)
 
     def logodds(self):
         """Device f32 [ny, nx]: clamp(hits l_occ - free l_free, l_min, l_max)."""

@@ -354,27 +354,29 @@ class Context:
         return dict(e_coord=e_co, e_cell=e_c, e_pdb=e_pdb, c_frame=c_f, c_rc=c_rc, c_amask=c_am)
 
     # -- steering tables -------------------------------------------------------------------------
+    def _steer_cached(self, kind, steer_c128, build):
+        """The one cache of everything uploaded from a steering matrix: build() runs once per (kind, matrix).  The key
+        holds the matrix's bytes themselves, not their hash: two matrices with one hash must not share a table."""
+        key = (kind, steer_c128.dtype.str, steer_c128.shape, steer_c128.tobytes())
+        if key not in self._steer_cache:
+            self._steer_cache[key] = build()
+        return self._steer_cache[key]
+
     def steering(self, steer_c128: np.ndarray):
         """Upload a [G, M] complex128 steering matrix: MFMA operand table (f32), fp64 copy, np.angle copy."""
-        key = (steer_c128.shape, hash(steer_c128.tobytes()))
-        hit = self._steer_cache.get(key)
-        if hit is not None:
-            return hit
-        G, M = steer_c128.shape
-        n = self.lib.rsl_steer_table_floats(G, M)
-        host = np.zeros(n, dtype=np.float32)
-        flat = np.ascontiguousarray(steer_c128.astype(np.complex128)).view(np.float64)
-        nt, fl = c_int(), c_int()
-        rc = self.lib.rsl_steer_table_build(flat.ctypes.data_as(ctypes.POINTER(c_double)), G, M,
-                                            host.ctypes.data_as(ctypes.POINTER(c_float)), byref(nt), byref(fl))
-        if rc != 0:
-            raise ValueError(f"rsl_steer_table_build failed (G={G}, M={M})")
-        torch = self.torch
-        ent = dict(G=G, M=M, tab=self.to_dev(host), c128=self.to_dev(flat.copy()),
-                   toeplitz=bool(fl.value & _lib.STEER_TOEPLITZ),
-                   phase=self.to_dev(np.angle(steer_c128).astype(np.float64)))
-        self._steer_cache[key] = ent
-        return ent
+        def build():
+            G, M = steer_c128.shape
+            host = np.zeros(self.lib.rsl_steer_table_floats(G, M), dtype=np.float32)
+            flat = np.ascontiguousarray(steer_c128.astype(np.complex128)).view(np.float64)
+            nt, fl = c_int(), c_int()
+            rc = self.lib.rsl_steer_table_build(flat.ctypes.data_as(ctypes.POINTER(c_double)), G, M,
+                                                host.ctypes.data_as(ctypes.POINTER(c_float)), byref(nt), byref(fl))
+            if rc != 0:
+                raise ValueError(f"rsl_steer_table_build failed (G={G}, M={M})")
+            return dict(G=G, M=M, tab=self.to_dev(host), c128=self.to_dev(flat.copy()),
+                        toeplitz=bool(fl.value & _lib.STEER_TOEPLITZ),
+                        phase=self.to_dev(np.angle(steer_c128).astype(np.float64)))
+        return self._steer_cached('mfma', steer_c128, build)
 
     # -- a11-a16 ----------------------------------------------------------------------------------
     def doa(self, rds, c_frame, c_rc, steer, method: int, *, n: Optional[int] = None, n_dev=None,
@@ -417,12 +419,8 @@ class Context:
     def steering_sub(self, steer_c128: np.ndarray, L: int):
         """Upload the sub-array steering vectors of rsl_doa_smoothed: device c64 [G, L] (tables.subarray_steering;
         ValueError for a non-uniform array)."""
-        key = ('sub', int(L), steer_c128.shape, hash(steer_c128.tobytes()))
-        hit = self._steer_cache.get(key)
-        if hit is None:
-            hit = self.to_dev(tables.subarray_steering(steer_c128, L).astype(np.complex64))
-            self._steer_cache[key] = hit
-        return hit
+        return self._steer_cached(('sub', int(L)), steer_c128,
+                                  lambda: self.to_dev(tables.subarray_steering(steer_c128, L).astype(np.complex64)))
 
     def doa_smoothed(self, rds, c_frame, c_rc, steer_sub, *, n: Optional[int] = None, n_dev=None, nmax: int = 3,
                      num_sources: int = 0, rel: float = 0.05, want_den: bool = True, want_eig: bool = False,
@@ -464,12 +462,7 @@ class Context:
     def steering_c64(self, steer_c128: np.ndarray):
         """Upload a steering matrix [G, A] rounded to complex64 (the table of rsl_range_azimuth), cached."""
         st = np.ascontiguousarray(np.asarray(steer_c128, dtype=np.complex128))
-        key = ('c64', st.shape, hash(st.tobytes()))
-        hit = self._steer_cache.get(key)
-        if hit is None:
-            hit = self.to_dev(st.astype(np.complex64))
-            self._steer_cache[key] = hit
-        return hit
+        return self._steer_cached('c64', st, lambda: self.to_dev(st.astype(np.complex64)))
 
     def range_azimuth(self, cov, steer_c64, method, loading: float = 1e-2, want_arg: bool = False, out=None):
         """cov complex64 [.., A, A] (Hermitian) -> the Bartlett or Capon power over the grid of steer_c64 (device c64

@@ -480,11 +480,11 @@ def test_chain_guard_and_multi_source(chains):
     assert ch.guard_violations() == []
     K.chain_same_results(chains['ca'], r)
     nc = int(r['cell_base'][-1])
-    assert nc > 0 and r['ss_nsrc'].shape == (nc,) and r['ss_gidx'].shape == (nc, ch.ss_nmax)
-    assert ((r['ss_nsrc'] >= 1) & (r['ss_nsrc'] <= ch.ss_nmax)).all()
+    assert nc > 0 and r['ss_nsrc'].shape == (nc,) and r['ss_gidx'].shape == (nc, ch.ss.nmax)
+    assert ((r['ss_nsrc'] >= 1) & (r['ss_nsrc'] <= ch.ss.nmax)).all()
     # ... of every cell: what a per-call smoothed MUSIC on the chain's own lists gives
     L = ch.lists
-    nsrc, idx, den, _, _ = ch.ctx.doa_smoothed(ch.rds, L['c_frame'], L['c_rc'], ch.ss_steer, n=nc, nmax=ch.ss_nmax,
+    nsrc, idx, den, _, _ = ch.ctx.doa_smoothed(ch.rds, L['c_frame'], L['c_rc'], ch.ss.steer, n=nc, nmax=ch.ss.nmax,
                                                num_sources=ch.cfg.ss_sources, rel=ch.cfg.ss_rel)
     assert (r['ss_nsrc'] == nsrc[:nc].cpu().numpy()).all() and (r['ss_gidx'] == idx[:nc].cpu().numpy()).all()
     assert np.array_equal(r['ss_den'], den[:nc].cpu().numpy().astype(np.float64), equal_nan=True)

@@ -361,7 +361,7 @@ def test_chain_velocity_on_refined_azimuths(ctx, refined_chains, loss):
     nc = int(r['cell_base'][-1])
     az, y, m, seg = r['az_refined'], r['phase'], VR.popcount(r['c_amask']), r['cell_base']
     assert nc >= 6 and not np.isnan(az).any()
-    d = dict(az=ch.pc['az'], y=ch.ext['phase'], seg=ch.offs['cell_base'], amask=ch.lists['c_amask'], k=ch.k,
+    d = dict(az=ch.pc.out['az'], y=ch.ext['phase'], seg=ch.offs['cell_base'], amask=ch.lists['c_amask'], k=ch.k,
              n=ch.cell_cap)
     print()
     if loss == 'ls':

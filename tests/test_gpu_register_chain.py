@@ -102,11 +102,11 @@ def test_registration_rows(runs):
     ch = runs['chain']
     # what the chain kept is its last frame
     res = runs['results'][1][0]
-    k = int(ch.reg_keep['n_dev'].item())
+    k = int(ch.reg.keep['n_dev'].item())
     last = slice(int(res['cell_base'][-2]), int(res['cell_base'][-1]))
     assert k == last.stop - last.start
-    assert np.array_equal(ch.reg_keep['points'][:k].cpu().numpy(), res['points'][last])
-    assert np.array_equal(ch.reg_keep['rc'][:k].cpu().numpy(), res['c_rc'][last])
+    assert np.array_equal(ch.reg.keep['points'][:k].cpu().numpy(), res['points'][last])
+    assert np.array_equal(ch.reg.keep['rc'][:k].cpu().numpy(), res['c_rc'][last])
 
 
 def test_reset_forgets_the_kept_cloud(runs):
@@ -145,8 +145,8 @@ def test_robust_solver_weights_vote(ctx, runs):
         assert np.array_equal(rows[:, 6:], ref[:, 6:]) and (err <= tol).all(), (err, tol)
         last = slice(int(res['cell_base'][-2]), int(res['cell_base'][-1]))
         prev = dict(points=res['points'][last], weight=w[last])
-        k = int(ch.reg_keep['n_dev'].item())
-        assert np.array_equal(ch.reg_keep['weight'][:k].cpu().numpy(), w[last])
+        k = int(ch.reg.keep['n_dev'].item())
+        assert np.array_equal(ch.reg.keep['weight'][:k].cpu().numpy(), w[last])
     plain = runs['results'][1][0]['registration']
     assert not np.array_equal(rows[:, :3], plain[:, :3])  # the weights reach the estimator
 

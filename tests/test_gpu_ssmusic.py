@@ -313,7 +313,7 @@ def test_chain_multi_source(ctx, chains, name):
     st = tables.steering_matrix(ch.grid, np.arange(8) * lam / 2, lam)
     r = ops.doa_smoothed(st, sigs=sigs, sub_len=cfg.ss_len, num_sources=cfg.ss_sources, rel=cfg.ss_rel,
                          nmax=cfg.ss_max, ctx=ctx)
-    assert b['ss_gidx'].shape == (nc, ch.ss_nmax)
+    assert b['ss_gidx'].shape == (nc, ch.ss.nmax)
     for k, kk in (('ss_nsrc', 'nsrc'), ('ss_gidx', 'gidx'), ('ss_den', 'den')):
         x, y = np.ascontiguousarray(b[k]), np.ascontiguousarray(r[kk])
         assert x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes(), k

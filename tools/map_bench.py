@@ -52,7 +52,6 @@ def part_standalone(det, F, reps):
     red.step(ch.vel, vstride=8)
     torch.cuda.synchronize()
     _, nc = ch.totals()
-    L = ch.lists
     poses = red.poses.cpu().numpy()
     kw = map_around(poses)
     res = {'detector': det, 'frames': F, 'reps': reps, 'cells': nc, 'cells_per_frame': nc / F, 'map': kw,
@@ -62,10 +61,6 @@ def part_standalone(det, F, reps):
     def update(gm, poses_dev):
         return lambda: gm.update_chain(ch, poses_dev)
 
-    def refine():
-        return ctx.cell_refine(ch.rds, L['c_frame'], L['c_rc'], ch.gidx, ch.az_table, ch.pc_steer, n=ch.cell_cap,
-                               n_dev=ch.ncell_dev, power=ch.power, range_mode=ch.pc_modes[0],
-                               doppler_mode=ch.pc_modes[1], axes=ch.pc_axes, out=ch.pc)
     same = red.poses[:1].expand(F, 7).contiguous()
     for name, free, pd in (('k_map_update', True, red.poses), ('k_map_update_no_free', False, red.poses),
                            ('k_map_update_same_pose', True, same)):
@@ -81,7 +76,7 @@ def part_standalone(det, F, reps):
         if name == 'k_map_update':
             res['k_map_logodds'] = B.timed(ctx, torch, gm.logodds, reps, 'aux')
             res['k_map_logodds']['bytes_per_s'] = 12 * gm.hits.numel() / (res['k_map_logodds']['ms_rsl_timing'] * 1e-3)
-    res['k_cell_refine'] = B.timed(ctx, torch, refine, reps, 'cell_extras')
+    res['k_cell_refine'] = B.timed(ctx, torch, ch.pc.launch, reps, 'cell_extras')
     for k in ('k_map_update', 'k_map_update_no_free', 'k_map_update_same_pose', 'k_map_logodds'):
         res[k + '_over_refine'] = res[k]['ms_rsl_timing'] / res['k_cell_refine']['ms_rsl_timing']
     return res

@@ -37,14 +37,13 @@ def part_standalone(F, reps):
     power = ctx.empty((F, S, C), torch.float32)
     r = B.timed(ctx, torch, lambda: ctx.integrate_power(ch.rds, out=power), reps, 'detect')
     res['k_power_integrate'] = {**r, 'read_tb_per_s': rds_bytes / (r['ms_rsl_timing'] * 1e-3) / 1e12}
-    r = B.timed(ctx, torch, lambda: ctx.range_cov(ch.rds, ch.ra_win, out=ch.ra_cov), reps, 'doa_scan')
+    r = B.timed(ctx, torch, ch.ra.cov, reps, 'doa_scan')
     res['k_range_cov'] = {**r, 'read_tb_per_s': rds_bytes / (r['ms_rsl_timing'] * 1e-3) / 1e12,
                           'mfma_per_range_bin': C // 4}
     res['cov_rate_over_integrate_rate'] = (res['k_range_cov']['read_tb_per_s'] /
                                            res['k_power_integrate']['read_tb_per_s'])
     for m in METHODS:
-        r = B.timed(ctx, torch, lambda: ctx.range_azimuth(ch.ra_cov, ch.ra_steer, m, loading=cfg.ra_loading,
-                                                          out=ch.ra), reps, 'doa_scan')
+        r = B.timed(ctx, torch, lambda: ch.ra.launch(with_cov=False, method=m), reps, 'doa_scan')
         res[f'k_range_azimuth_{m}'] = {**r, 'rows_per_s': F * S / (r['ms_rsl_timing'] * 1e-3),
                                        'grid_points_per_s': F * S * G / (r['ms_rsl_timing'] * 1e-3)}
     return res

@@ -37,24 +37,17 @@ def part_standalone(F, reps):
     torch.cuda.synchronize()
     _, nc = ch.totals()
     G = len(ch.grid)
-    L = ch.lists
     # what the algorithm needs per cell: the signature (A c64), 5 powers, frame + rc + gidx, one row and one double
     refine_bytes = nc * (8 * A + 5 * 4 + 3 * 4 + 32 + 8)
     extras_bytes = nc * (8 * A + 2 * 4 + 2 * 8)  # the signature, frame + rc, esprit + phase
     res = {'frames': F, 'reps': reps, 'cells': nc, 'cells_per_frame': nc / F, 'grid_points': G,
            'steer_table_bytes': G * A * 8, 'refine_bytes_needed': refine_bytes, 'extras_bytes_needed': extras_bytes}
 
-    def refine(power):
-        return ctx.cell_refine(ch.rds, L['c_frame'], L['c_rc'], ch.gidx, ch.az_table, ch.pc_steer, n=ch.cell_cap,
-                               n_dev=ch.ncell_dev, power=power, range_mode=ch.pc_modes[0],
-                               doppler_mode=ch.pc_modes[1], axes=ch.pc_axes, out=ch.pc)
-
     def extras():
-        return ctx.cell_extras(ch.rds, L['c_frame'], L['c_rc'], n=ch.cell_cap, n_dev=ch.ncell_dev,
-                               esprit_scale=ch.esprit_scale, want_esprit=True, want_phase=True, bufs=ch.ext)
-    for name, fn, nbytes in (('k_cell_refine', lambda: refine(ch.power), refine_bytes),
-                             ('k_cell_extras', extras, extras_bytes),
-                             ('k_cell_refine_null_power', lambda: refine(None), None)):
+        return ctx.cell_extras(**ch.cells(), esprit_scale=ch.esprit_scale, want_esprit=True, want_phase=True,
+                               bufs=ch.ext)
+    for name, fn, nbytes in (('k_cell_refine', ch.pc.launch, refine_bytes), ('k_cell_extras', extras, extras_bytes),
+                             ('k_cell_refine_null_power', lambda: ch.pc.launch(power=None), None)):
         r = B.timed(ctx, torch, fn, reps, 'cell_extras')
         r['cells_per_s'] = nc / (r['ms_rsl_timing'] * 1e-3)
         if nbytes:

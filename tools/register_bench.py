@@ -1,10 +1,11 @@
 """Scan-registration measurements at configs[2] (A8 C128 S512), F frames per step, one GPU, one stream, for the
 threshold detector (the reference's rule: about 35.5 k cells per frame) and for detector='cfar', detect_on='sum':
 
-* standalone, on the point cloud, cell_base, c_rc and velocity rows of one chain batch: rsl_scan_register with the
-  chain's settings (ms per launch from rsl_timing_* and from stream events, frame pairs per second), the same without
-  rc (every pair tested: only where the cloud is small enough, --dense-limit cells per frame), and rsl_cell_refine on
-  the same list in the same run (the yardstick);
+* standalone, on the point cloud, cell_base, c_rc and velocity rows of one chain batch: the chain's own registration
+  launch (ch.reg.launch: ms per launch of rsl_scan_register from rsl_timing_*, and from stream events with the stage's
+  start row and its copy of the last frame, frame pairs per second), the same without rc (every pair tested: only where
+  the cloud is small enough, --dense-limit cells per frame), and the chain's rsl_cell_refine launch on the same list in
+  the same run (the yardstick);
 * whole step: ms per ch.run() and frames/s with the point cloud and with the point cloud and the registration;
 * the default step under the parent commit's library (radar-slam_amd/lib/librsl_ab.so, tools/build_ab.sh <parent>)
   and under the tree's, alternating, --rounds times each: the tree's values against the parent's run-to-run range.
@@ -38,34 +39,22 @@ def part_standalone(det, F, reps, dense_limit):
     ch.run(cube)  # fills the lists, the point cloud, the velocity rows and the registration rows
     torch.cuda.synchronize()
     _, nc = ch.totals()
-    L = ch.lists
-    rows = ch.reg['rows'].cpu().numpy()
+    rows = ch.reg.out['rows'].cpu().numpy()
     res = {'detector': det, 'frames': F, 'reps': reps, 'cells': nc, 'cells_per_frame': nc / F,
            'settings': dict(h=cfg.reg_h, h_coarse=cfg.reg_h_coarse, dtheta=cfg.reg_dtheta, k=cfg.reg_k,
                             iters=cfg.reg_iters, shrink=cfg.reg_shrink, tol=cfg.reg_tol, w_min=cfg.reg_w_min),
            'flags': {str(k): int((rows[:, 7] == k).sum()) for k in (0, 1, 2)},
            'updates_mean': float(rows[rows[:, 7] == 0, 6].mean()) if (rows[:, 7] == 0).any() else 0.0}
-    init = ch.reg_init.clone()
-
-    def register(rc):
-        kw = dict(rc=L['c_rc'], C=ch.C, axes=ch.pc_axes) if rc else {}
-        return ctx.scan_register(ch.pc['points'], ch.offs['cell_base'], weight=ch.vel_weight, init=init, h=cfg.reg_h,
-                                 h_coarse=cfg.reg_h_coarse, dtheta=cfg.reg_dtheta, k=cfg.reg_k, iters=cfg.reg_iters,
-                                 shrink=cfg.reg_shrink, tol=cfg.reg_tol, w_min=cfg.reg_w_min, dt=cfg.dt,
-                                 n=ch.cell_cap, out=ch.reg, **kw)
-
-    def refine():
-        return ctx.cell_refine(ch.rds, L['c_frame'], L['c_rc'], ch.gidx, ch.az_table, ch.pc_steer, n=ch.cell_cap,
-                               n_dev=ch.ncell_dev, power=ch.power, range_mode=ch.pc_modes[0],
-                               doppler_mode=ch.pc_modes[1], axes=ch.pc_axes, out=ch.pc)
-    r = B.timed(ctx, torch, lambda: register(True), reps, 'aux')
+    # the chain's own launches: frame 0 without a reference, as in a first run (the stream-event time includes the
+    # stage's start row and its copy of the last frame; rsl_timing_* times the kernel alone)
+    r = B.timed(ctx, torch, lambda: ch.reg.launch(prev=None), reps, 'aux')
     r['frame_pairs_per_s'] = (F - 1) / (r['ms_rsl_timing'] * 1e-3)
     res['k_scan_register'] = r
     if nc / F <= dense_limit:
-        r = B.timed(ctx, torch, lambda: register(False), reps, 'aux')
+        r = B.timed(ctx, torch, lambda: ch.reg.launch(prev=None, rc=None, C=0, axes=None), reps, 'aux')
         res['k_scan_register_no_rc'] = r
         res['no_rc_over_rc'] = r['ms_rsl_timing'] / res['k_scan_register']['ms_rsl_timing']
-    res['k_cell_refine'] = B.timed(ctx, torch, refine, reps, 'cell_extras')
+    res['k_cell_refine'] = B.timed(ctx, torch, ch.pc.launch, reps, 'cell_extras')
     res['register_over_refine'] = res['k_scan_register']['ms_rsl_timing'] / res['k_cell_refine']['ms_rsl_timing']
     return res
 
